@@ -10,8 +10,11 @@ gradient all-reduce + Adam) of the 3-level GNN on synthetic Erdos-Renyi graphs o
 
 One process per GPU; graphs are sharded by rank (weak scaling: 64 graphs per GPU); the only
 collective is ONE RCCL all-reduce of the flat gradient bucket per step.  Rank 0 prints one JSON
-line.  ``roofline`` is the live HIP-event timing of the CSR aggregation kernels over the timed
-region; ``cpu_baseline`` is the CPU oracle (reference-semantics op sequence) on a bounded sample.
+line.  A plain run sets up, warms up, times the ``--steps`` steps and prints the headline line.
+``--full`` adds the rest: ``roofline`` is the live HIP-event timing of the CSR aggregation kernels
+over the timed region; ``also_aggr`` the max / mean aggregators; ``cpu_baseline`` the CPU oracle
+(reference-semantics op sequence) on a bounded sample.  ``--dump-outputs DIR`` writes the loss,
+parameters and gradient of the last timed step as ``.npy`` files.
 """
 import argparse
 import json
@@ -30,7 +33,7 @@ import torch.distributed as dist  # noqa: E402
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -56,7 +59,14 @@ def parse():
                          "batch, so only the BCE step of N ranks equals the single-process step on the global batch)")
     ap.add_argument("--dump-params", help="rank 0 saves {'params', 'grads'} (flat fp32 tensors: its parameters after the "
                                           "timed run, the all-reduced gradient of the last step) here")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last timed step computed as DIR/<name>.npy: "
+                         "loss, params (flat, after the optimizer step), grads (flat, all-reduced)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel HIP-event times and the roofline of "
+                         "the aggregation kernels, the stream-copy ceiling, the max / mean aggregators and the in-line "
+                         "topology build (--no-extras drops these two), the CPU oracle baseline (--no-cpu-baseline)")
+    return ap.parse_args(argv)
 
 
 def _cpu_model():
@@ -100,6 +110,25 @@ def cpu_baseline(args, model_sd):
             "sample": "%d graphs of the same synthetic workload, forward and backward timed separately, median of %d "
                       "after 1 warm-up (oracle: materialised [E,d] gather -> elementwise -> scatter, no optimizer "
                       "step)" % (nb, len(fwd))}
+
+
+DUMP_MAX_ELEMENTS = 1 << 22          # per array: 16 MB of fp32; a larger output is dumped as a fixed, seeded sample
+
+
+def dump_outputs(directory, arrays):
+    """``arrays``: name -> tensor.  Each one is written as ``directory/<name>.npy``, float64 tensors as float64 and
+    everything else as float32.  An array of more than DUMP_MAX_ELEMENTS entries is flattened and sampled at the same
+    seeded, sorted positions on every run, so that two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            gen = torch.Generator().manual_seed(0)
+            pick = torch.randperm(t.numel(), generator=gen)[:DUMP_MAX_ELEMENTS].sort()[0]
+            t = t.reshape(-1)[pick]
+        np.save(os.path.join(directory, name + ".npy"), t.numpy())
 
 
 PROFILED_WORKLOAD = "64x10000x160000x128"     # graphs per GPU x nodes x edges x hidden of the PMC passes (bench.py defaults)
@@ -172,6 +201,10 @@ def stream_copy_ceiling(dev, mib=1024, reps=10):
 
 def main():
     args = parse()
+    # a plain run does what the headline figure needs; everything else is measured under --full
+    use_timer = args.full and not args.no_kernel_timer
+    extras = args.full and not args.no_extras
+    baseline = args.full and not args.no_cpu_baseline
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -298,7 +331,7 @@ def main():
         return elapsed, (timer.summary() if timer is not None else None), ar_events, float(loss.detach()), bucket, model
 
     elapsed, summ, ar_events, final_loss, bucket, model = run(args.aggr, args.steps, args.warmup, not args.no_overlap,
-                                                               not args.no_kernel_timer)
+                                                               use_timer)
     if world > 1:
         tmax = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -306,6 +339,10 @@ def main():
     if rank == 0 and args.dump_params:
         torch.save({"params": torch.cat([p.detach().reshape(-1).float() for p in bucket.params]).cpu(),
                     "grads": torch.cat([v.reshape(-1).float() for v in bucket.views]).cpu()}, args.dump_params)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": torch.tensor(final_loss, dtype=torch.float32),
+                                         "params": torch.cat([p.detach().reshape(-1) for p in bucket.params]),
+                                         "grads": torch.cat([v.reshape(-1) for v in bucket.views])})
 
     if rank == 0:
         ms = elapsed / args.steps * 1e3
@@ -333,7 +370,7 @@ def main():
                        "allreduce_bytes": bucket.flat_all.numel() * 4,      # gradients + one reached flag per parameter
                        "final_loss": final_loss},
         }
-        blob, tsrc = load_traffic("%dx%dx%dx%d" % (B, args.nodes, args.edges, args.hidden))
+        blob, tsrc = load_traffic("%dx%dx%dx%d" % (B, args.nodes, args.edges, args.hidden)) if args.full else (None, None)
         N_all, E_all = B * args.nodes, B * args.edges
 
         def kernel_table(summary):
@@ -396,7 +433,7 @@ def main():
                 out["roofline"]["stream_copy_variants_GBps"] = variants
                 out["roofline"]["frac_of_stream_copy"] = v["achieved"] / ceil
             out["kernels"] = kernels
-        if world == 1 and not args.no_extras:
+        if world == 1 and extras:
             # "aggr in {softmax, max, mean} -- report all three, headline = softmax": the same step with
             # the other aggregators, a few steps each after the timed headline run, same process, same batches
             del model, bucket
@@ -413,7 +450,7 @@ def main():
             # the same headline step with the topology built in line (a caller without a second stream)
             el, _, _, _, _, _ = run(args.aggr, args.extra_steps, 2, args.no_overlap, False)
             out["no_overlap_ms_per_step" if not args.no_overlap else "overlap_ms_per_step"] = el / args.extra_steps * 1e3
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and baseline:
             torch.manual_seed(1234)
             out["cpu_baseline"] = cpu_baseline(args, W.ThreeLevelGNN(hidden=args.hidden, num_layers=3, aggr=args.aggr,
                                                                        n_members=args.members).state_dict())

@@ -1,13 +1,15 @@
 """bench.py's own line, produced by fresh child processes (never an exec of this GPU-holding process): the N=1 schema
 the driver parses, and -- when the box has two GPUs -- the N=2 launch exactly as the driver starts it
 (``python -m torch.distributed.run --nproc-per-node 2 ... bench.py --gpus 2``), whose line must have the N=1 line's
-schema with ``world_size == 2`` and a measured all-reduce.  Reduced sizes: this checks the plumbing, not the rate."""
+schema with ``world_size == 2`` and a measured all-reduce.  Those schemas are of ``--full`` runs; a plain run's line
+holds the headline alone.  Reduced sizes: this checks the plumbing, not the rate."""
 import json
 import os
 import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -43,7 +45,7 @@ def _keys(d, prefix=""):
 
 @pytest.fixture(scope="module")
 def line_n1():
-    return _line([sys.executable, "bench.py", "--gpus", "1", "--cpu-baseline-graphs", "1"] + SMALL)
+    return _line([sys.executable, "bench.py", "--gpus", "1", "--full", "--cpu-baseline-graphs", "1"] + SMALL)
 
 
 def test_bench_line_n1_schema(line_n1):
@@ -70,6 +72,27 @@ def test_bench_line_n1_schema(line_n1):
     assert out["no_overlap_ms_per_step"] > 0
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """Without ``--full`` the run measures the headline only: the line has the contract's headline keys and none of the
+    figures that take measurements of their own.  ``--dump-outputs`` writes the loss, parameters and all-reduced gradient
+    of the last timed step: the values ``--dump-params`` saves in the same run and the line's ``final_loss``."""
+    dump, saved = tmp_path / "out", str(tmp_path / "saved.pt")
+    out = _line([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", str(dump), "--dump-params", saved] + SMALL)
+    assert CONTRACT - {"roofline", "kernels"} <= set(out)
+    assert not {"roofline", "kernels", "cpu_baseline", "also_aggr", "no_overlap_ms_per_step"} & set(out)
+    assert out["n_gpus"] == 1 and out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert abs(out["value"] - 4 * 2 / (out["ms_per_step"] * 2e-3)) <= 1e-6 * out["value"]
+    names = sorted(p.name for p in dump.iterdir())
+    assert names == ["grads.npy", "loss.npy", "params.npy"]
+    got = {n[:-4]: np.load(dump / n) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    ref = torch.load(saved, weights_only=True)
+    assert np.array_equal(got["params"], ref["params"].numpy()) and np.array_equal(got["grads"], ref["grads"].numpy())
+    assert float(got["loss"]) == out["config"]["final_loss"]
+    assert np.isfinite(got["grads"]).all() and float(np.abs(got["grads"]).max()) > 0
+
+
 def test_bench_two_gpus_as_the_driver_launches_it(line_n1):
     if torch.cuda.device_count() < 2:
         pytest.skip("one GPU on this box: the 2-rank RCCL launch of bench.py needs two")
@@ -79,7 +102,7 @@ def test_bench_two_gpus_as_the_driver_launches_it(line_n1):
     s.close()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = _line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                 "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2"] + SMALL, env)
+                 "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--full"] + SMALL, env)
     single_only = {"cpu_baseline", "also_aggr", "no_overlap_ms_per_step", "roofline.stream_copy_GBps",
                    "roofline.frac_of_stream_copy", "roofline.stream_copy_variants_GBps"}
     want = {k for k in _keys(line_n1) if not any(k == s or k.startswith(s + ".") for s in single_only)}
@@ -109,7 +132,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(line_n1, tmp_path):
     small = [a for a in SMALL]
     small[small.index("--graphs-per-gpu") + 1] = "4"
     out = _line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                 "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2"] + small, env)
+                 "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--full"] + small, env)
     single_only = {"cpu_baseline", "also_aggr", "no_overlap_ms_per_step", "roofline.stream_copy_GBps",
                    "roofline.frac_of_stream_copy", "roofline.stream_copy_variants_GBps"}
     want = {k for k in _keys(line_n1) if not any(k == s or k.startswith(s + ".") for s in single_only)}

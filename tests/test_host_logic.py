@@ -255,3 +255,24 @@ def test_membership_cache_hits_for_views_of_one_table():
     assert a is b
     c = project.membership_tables(match[None, :].repeat(4, 1), seg[None, :].repeat(4, 1), 30, 12, 120)
     assert c is not a and torch.equal(c.seg_mem, a.seg_mem) and torch.equal(c.node_ptr, a.node_ptr)
+
+
+def test_bench_plain_defaults_and_dump_outputs(tmp_path):
+    """bench.py: a plain run measures the headline only (everything else needs ``--full``); ``dump_outputs`` writes
+    float32 / float64 ``.npy`` files and cuts an oversized array down to the same seeded sample on every call."""
+    import numpy as np
+    import bench
+    args = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert args.steps == 7 and args.warmup == 2 and not args.full and args.dump_outputs is None
+    assert bench.parse(["--full", "--dump-outputs", str(tmp_path)]).full
+    big = torch.arange(bench.DUMP_MAX_ELEMENTS + 5, dtype=torch.float32)
+    arrays = {"loss": torch.tensor(1.5), "w": torch.ones(3, 2, dtype=torch.bfloat16),
+              "x": torch.tensor([0.25], dtype=torch.float64), "big": big}
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), arrays)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in arrays}
+    assert got["loss"].dtype == np.float32 and got["loss"].shape == () and float(got["loss"]) == 1.5
+    assert got["w"].dtype == np.float32 and got["w"].shape == (3, 2) and (got["w"] == 1).all()
+    assert got["x"].dtype == np.float64 and got["x"].tolist() == [0.25]
+    assert got["big"].shape == (bench.DUMP_MAX_ELEMENTS,) and (np.diff(got["big"]) > 0).all()
+    assert np.array_equal(got["big"], np.load(tmp_path / "b" / "big.npy"))

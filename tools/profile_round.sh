@@ -38,26 +38,26 @@ jsonblob() {   # jsonblob <log> <destination>: everything from the first '{' (a 
 }
 
 if want headline; then
-  BENCH="python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline"
+  BENCH="python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline"
   prof prof_stats_$TAG $STATS -d $R/gpurun_out/prof_stats_$TAG -- $BENCH
   prof prof_fetch_$TAG --pmc FETCH_SIZE --output-format csv -d $R/gpurun_out/prof_fetch_$TAG -- $BENCH
   prof prof_write_$TAG --pmc WRITE_SIZE --output-format csv -d $R/gpurun_out/prof_write_$TAG -- $BENCH
   prof prof_csr_$TAG $STATS -d $R/gpurun_out/prof_csr_$TAG -- python3 $R/tools/bench_csr.py
   echo "headline passes done"
   python3 tools/summarize_prof.py --stats "gpurun_out/prof_stats_$TAG/**/*kernel_stats.csv" --tag $TAG --commit "$MLGNN_COMMIT" \
-    --cmd "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline" \
-    --pmc-cmd "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (one pass each) --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline" \
+    --cmd "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline" \
+    --pmc-cmd "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (one pass each) --output-format csv -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline" \
     --pmc-fetch "gpurun_out/prof_fetch_$TAG/**/*counter_collection.csv" --pmc-write "gpurun_out/prof_write_$TAG/**/*counter_collection.csv"
   python3 tools/bench_csr.py > gpurun_out/csr_$TAG.log 2>&1
   jsonline gpurun_out/csr_$TAG.log profiles/${TAG}_csr_build.json
   python3 tools/summarize_prof.py --stats "gpurun_out/prof_csr_$TAG/**/*kernel_stats.csv" --tag ${TAG}_csr --commit "$MLGNN_COMMIT" \
     --cmd "rocprofv3 --kernel-trace --stats --output-format csv -- python3 tools/bench_csr.py   (topology build of a configs[1] batch on its own: 64 graphs x 10k nodes / 160k edges, both CSR orderings + the rank-1 edge table)"
   python3 tools/bench_dense.py --iters 30 --json profiles/${TAG}_dense_kernels.json > gpurun_out/dense_$TAG.log 2>&1
-  python3 bench.py --gpus 1 --global-batch 512 --steps 4 --warmup 2 --pool-batches 2 --no-cpu-baseline --no-extras > gpurun_out/strong_n1_$TAG.log 2>&1
-  jsonline gpurun_out/strong_n1_$TAG.log profiles/${TAG}_strong_n1.json
+  python3 bench.py --full --gpus 1 --global-batch 512 --steps 4 --warmup 2 --pool-batches 2 --no-cpu-baseline --no-extras > $TMPDIR/strong_n1_$TAG.log 2>&1
+  jsonline $TMPDIR/strong_n1_$TAG.log profiles/${TAG}_strong_n1.json
   # the un-profiled bench line LAST: it picks up the traffic.json written above (same kernel sources -> not stale)
-  python3 bench.py > gpurun_out/bench_$TAG.log 2>&1
-  jsonline gpurun_out/bench_$TAG.log profiles/${TAG}_bench.json
+  python3 bench.py --full > $TMPDIR/bench_$TAG.log 2>&1
+  jsonline $TMPDIR/bench_$TAG.log profiles/${TAG}_bench.json
 fi
 
 if want stress; then
