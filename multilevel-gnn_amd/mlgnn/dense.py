@@ -346,6 +346,7 @@ class _FusedMLP2(torch.autograd.Function):
             # residual may have parked that branch's gradient there
             tag, folded, pending = ctx.post_tag, None, None
             if tag is not None:
+                tag.claim()
                 folded, tag.folded = tag.folded, None
                 if tag.extra is not None and not (folded is not None and tag.extra_used):
                     pending = tag.extra
@@ -419,7 +420,7 @@ class _FusedMLP2(torch.autograd.Function):
                     gx = tall_matmul_nt(gh, w1, row_max=gh_max, bt_transposed=True)
         g_res = go if ctx.needs_input_grad[7] else None
         if g_res is not None and ctx.res_tag is not None:
-            ctx.res_tag.extra, g_res = g_res, None           # added by the LayerNorm backward of the residual's producer
+            ctx.res_tag.claim().extra, g_res = g_res, None           # added by the LayerNorm backward of the residual's producer
         return (gx, gw1, gb1 if has_b1 else None, ggamma, gbeta, gw2, gb2 if has_b2 else None,
                 g_res, None, gpg, gpb, None, None)
 
@@ -499,6 +500,24 @@ WIDE_F32 = os.environ.get("MLGNN_WIDE_F32", "1") != "0"
 SKINNY_MIN_K = 8192            # below this the weight is a few MB and the library's GEMM is not a stream problem
 
 
+def _claim_grad_slot(param):
+    """True when a backward may write ``param``'s weight gradient into its bucket slot and hand autograd the alias: the
+    running backward accumulates into ``param.grad`` (not ``torch.autograd.grad``, which would return the slot itself to
+    the caller -- and the next backward would overwrite it), and no other node of the same backward has claimed the slot
+    already (a weight used twice in one graph: two aliases of one buffer would sum to twice the second use)."""
+    try:
+        node = torch.autograd.graph.get_gradient_edge(param).node
+        if not torch._C._will_engine_execute_node(node):
+            return False
+    except RuntimeError:                             # (raised under torch.autograd.grad(..., inputs=[param]))
+        return False
+    task = torch._C._current_graph_task_id()
+    if task < 0 or getattr(param, "_mlgnn_slot_task", None) == task:
+        return False
+    param._mlgnn_slot_task = task
+    return True
+
+
 class _SkinnyLinear(torch.autograd.Function):
     """``y = x W^T + b`` for at most 64 rows with a very long input (the first Linear of MultilevelGNN's head,
     multilevel_gnn.py:121-127: ``[B, 84 096] -> 512`` at config/kirc.yaml): forward, input gradient and weight gradient as
@@ -536,7 +555,7 @@ class _SkinnyLinear(torch.autograd.Function):
             # (only when this backward DEFINES the gradient -- .grad released before the step; a gradient that is being
             # accumulated into must arrive in memory of its own)
             if (slot is not None and ctx.param.grad is None and slot.numel() == J * K and slot.dtype == torch.float32
-                    and slot.device == x.device and slot.data_ptr() % 16 == 0):
+                    and slot.device == x.device and slot.data_ptr() % 16 == 0 and _claim_grad_slot(ctx.param)):
                 gw = slot.view(J, K)                      # (a fresh alias: autograd adopts it as .grad without a copy)
             else:
                 gw = torch.empty((J, K), dtype=torch.float32, device=x.device)

@@ -174,6 +174,16 @@ class PostLN:
         self.extra = None
         self.extra_used = False
         self.folded = None
+        self.task = None           # the backward (autograd graph task) that wrote extra / folded
+
+    def claim(self):
+        """Called by every backward that reads or writes a field: what another backward left is dropped (one that ran the
+        aggregation but not the producer, e.g. ``torch.autograd.grad`` for other inputs)."""
+        task = torch._C._current_graph_task_id()
+        if self.task is not None and task != self.task:      # (fields set outside any backward are taken over)
+            self.extra, self.extra_used, self.folded = None, False, None
+        self.task = task
+        return self
 
 
 # Off by default.  Measured at BASELINE configs[1] (same-box A/B, bench.py): the epilogue costs the aggregation backward
@@ -363,6 +373,17 @@ class _GradSink:
         # csrc/embedding.hip) -- `total` collects the layers of one backward
         self.fix = None
         self.total = None
+        self.task = None           # the backward (autograd graph task) that wrote buf / total
+
+    def claim(self):
+        """Called by every backward that reads or adds into the sink: contents left by another backward are dropped.  A
+        backward that runs the consumers but not the fan-out node (``torch.autograd.grad`` for other inputs) would
+        otherwise leave its edge gradient here for the next one to add on top of."""
+        task = torch._C._current_graph_task_id()
+        if self.task is not None and task != self.task:
+            self.buf = self.total = None
+        self.task = task
+        return self
 
 
 class _EdgeFanout(torch.autograd.Function):
@@ -380,6 +401,7 @@ class _EdgeFanout(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        ctx.sink.claim()
         total, ctx.sink.buf = ctx.sink.buf, None
         if g is not None:                       # a consumer outside the aggregation kernels contributed as well
             total = g if total is None else total + g
@@ -399,6 +421,7 @@ class _TableFanout(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        ctx.sink.claim()
         per_edge, ctx.sink.buf = ctx.sink.buf, None
         direct, ctx.sink.total = ctx.sink.total, None
         total = None
@@ -630,6 +653,8 @@ class _GenAggregate(torch.autograd.Function):
         gx = torch.empty_like(x)
         ge, ge_accumulate, sink, te = None, 0, ctx.grad_sink, ctx.table_edge
         eid_t, geid_t = g.eid_t, None
+        if sink is not None:
+            sink.claim()
         if te is not None:                                   # read the table row, write the edge's own gradient row
             _, eid_t, geid_t = te.rows_for(g)                # (gradient rows in by-source order: a streamed write)
             if sink is not None:
@@ -735,6 +760,7 @@ class _GenAggregate(torch.autograd.Function):
         hub, hub_keep = g.hub_arg("src", d)
         tag = ctx.post_ln if (hub is None and ctx.needs_input_grad[0]) else None
         if tag is not None:
+            tag.claim()
             # d loss / d y goes through the LayerNorm backward of y = relu?(LayerNorm(h)) in the row epilogue; gx is then
             # d loss / d h (+ the identity-branch gradient the block's MLP left in tag.extra)
             f32 = dict(dtype=torch.float32, device=x.device)
