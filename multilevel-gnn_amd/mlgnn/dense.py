@@ -5,8 +5,10 @@ import os
 import torch
 import torch.nn.functional as F
 
-from . import _lib
-from .ops import _DTYPE_IDS, f32_cached, row_max_of
+from . import _lib, ops
+from .norm import ln_backward_normalised, ln_backward_saved
+from .ops import _DTYPE_IDS, _stream
+from .tags import PostLN, backward_of, f32_cached, row_max_of, softmax_lse_of, tag_post_ln, tag_row_max, tag_shifted
 
 DIFFPOOL_EPS = 1e-15
 WGRAD_MIN_ROWS = 8192          # below this the library's TN GEMM is not the bottleneck
@@ -23,7 +25,7 @@ def _aligned(t):
 def tall_matmul_nt(a, bt, bias=None, residual=None, row_max=None, ln=None, bt_transposed=False):
     """``a [N,R] @ bt[J,R]^T (+ bias) (+ residual [N,J])`` through the scaled split-precision fp16-MFMA kernel
     (``csrc/tallgemm.hip``).  The caller checks :func:`tall_matmul_supported` first.  ``row_max`` [N]: ``max |a[i]|``
-    when the producer of ``a`` supplied it (see :func:`mlgnn.ops.tag_row_max`).
+    when the producer of ``a`` supplied it (see :func:`mlgnn.tags.tag_row_max`).
     ``ln = ("out", gamma, beta, eps)``: returns ``(xhat, rstd, row_max_y)`` -- the layer-normalised result without
     the affine map, its 1/sigma and ``max relu(gamma xhat + beta)`` per row.  ``ln = ("in", gamma, beta)``: ``a`` is
     such an ``xhat``; ``relu(gamma a + beta)`` is applied as it is loaded."""
@@ -51,10 +53,8 @@ def tall_matmul_nt(a, bt, bias=None, residual=None, row_max=None, ln=None, bt_tr
             rstd = torch.empty(N, dtype=torch.float32, device=a.device)
             rmax = torch.empty(N, dtype=torch.float32, device=a.device)
     rc = _lib.lib.mlgnn_tallgemm_nt(a.data_ptr(), bt.data_ptr(), int(bt_transposed), _lib.ptr(bias), _lib.ptr(residual),
-                                    _lib.ptr(row_max),
-                                    mode, _lib.ptr(gamma), _lib.ptr(beta), eps, _lib.ptr(rstd), _lib.ptr(rmax),
-                                    out.data_ptr(), ws.data_ptr(), nbytes, N, R, J, dt,
-                                    torch.cuda.current_stream().cuda_stream)
+                                    _lib.ptr(row_max), mode, _lib.ptr(gamma), _lib.ptr(beta), eps, _lib.ptr(rstd),
+                                    _lib.ptr(rmax), out.data_ptr(), ws.data_ptr(), nbytes, N, R, J, dt, _stream())
     _lib.check(rc, "mlgnn_tallgemm_nt")
     return (out, rstd, rmax) if mode == 1 else out
 
@@ -82,7 +82,7 @@ def tall_matmul_lnin_postln(xhat, w, bias, residual, row_max, gamma, beta, post)
                                              beta.contiguous().data_ptr(), g2.contiguous().data_ptr(),
                                              b2.contiguous().data_ptr(), float(eps2), int(bool(relu)), out.data_ptr(),
                                              y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(), nbytes,
-                                             N, R, J, torch.cuda.current_stream().cuda_stream)
+                                             N, R, J, _stream())
     _lib.check(rc, "mlgnn_tallgemm_lnin_postln")
     return out, y, mean, rstd
 
@@ -102,7 +102,7 @@ def tall_matmul_nt_shift(a, w, row_max, lse, rowptr):
     ROW_MAX_STATS["given" if row_max is not None else "computed"] += 1
     rc = _lib.lib.mlgnn_tallgemm_nt_shift(a.data_ptr(), w.data_ptr(), 1, _lib.ptr(row_max), lse.data_ptr(),
                                           rowptr.data_ptr(), gx.data_ptr(), gt.data_ptr(), flag.data_ptr(),
-                                          ws.data_ptr(), nbytes, N, R, J, torch.cuda.current_stream().cuda_stream)
+                                          ws.data_ptr(), nbytes, N, R, J, _stream())
     _lib.check(rc, "mlgnn_tallgemm_nt_shift")
     return gx, gt, flag
 
@@ -120,8 +120,7 @@ def tall_matmul_bf16_shift(go, weight, lse):
     nbytes = int(_lib.lib.mlgnn_tallgemm_workspace_bytes(M, K, 1))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=go.device)
     rc = _lib.lib.mlgnn_tallgemm_bf16_shift(go.data_ptr(), bt.data_ptr(), lse.data_ptr(), gx.data_ptr(), gt.data_ptr(),
-                                            flag.data_ptr(), ws.data_ptr(), nbytes, N, M, K,
-                                            torch.cuda.current_stream().cuda_stream)
+                                            flag.data_ptr(), ws.data_ptr(), nbytes, N, M, K, _stream())
     _lib.check(rc, "mlgnn_tallgemm_bf16_shift")
     return gx, gt, flag
 
@@ -141,8 +140,7 @@ def tall_matmul_ln_backward(go, w, xhat, rstd, gamma, beta, row_max=None):
     ROW_MAX_STATS["given" if row_max is not None else "computed"] += 1
     rc = _lib.lib.mlgnn_tallgemm_lnbwd(go.data_ptr(), w.data_ptr(), 1, _lib.ptr(row_max), xhat.data_ptr(), rstd.data_ptr(),
                                        gamma.contiguous().data_ptr(), beta.contiguous().data_ptr(), gh.data_ptr(),
-                                       rmax.data_ptr(), ggb.data_ptr(), ws.data_ptr(), nbytes, N, R, J,
-                                       torch.cuda.current_stream().cuda_stream)
+                                       rmax.data_ptr(), ggb.data_ptr(), ws.data_ptr(), nbytes, N, R, J, _stream())
     _lib.check(rc, "mlgnn_tallgemm_lnbwd")
     return gh, ggb[0], ggb[1], rmax
 
@@ -187,7 +185,7 @@ def linear_backward(go, w, x, go_max, x_max, epilogue, rstd=None, gamma=None, be
     rc = _lib.lib.mlgnn_linear_bwd(go.data_ptr(), w.data_ptr(), x.data_ptr(), go_max.data_ptr(), int(go_max_is_parts),
                                    x_max.data_ptr(), epilogue, _lib.ptr(rstd), _lib.ptr(gamma), _lib.ptr(beta),
                                    _lib.ptr(lse), dx.data_ptr(), _lib.ptr(gt), _lib.ptr(flag), gwb.data_ptr(),
-                                   parts.data_ptr(), ws.data_ptr(), n, N, M, K, torch.cuda.current_stream().cuda_stream)
+                                   parts.data_ptr(), ws.data_ptr(), n, N, M, K, _stream())
     _lib.check(rc, "mlgnn_linear_bwd")
     out = dict(dx=dx, gw=gwb[:M * K].view(M, K), gb=gwb[M * K:M * K + M], parts=parts, gt=gt, flag=flag)
     if epilogue == LB_LN:
@@ -221,8 +219,7 @@ def _wgrad(go, x, x_gamma=None, x_beta=None, go_max=None, x_max=None, out_dtype=
             or go_max.shape[0] != N or x_max.shape[0] != N):
         go_max = x_max = None
     rc = _lib.lib.mlgnn_linear_wgrad(go.data_ptr(), x.data_ptr(), _lib.ptr(x_gamma), _lib.ptr(x_beta), _lib.ptr(go_max),
-                                     _lib.ptr(x_max), out.data_ptr(), ws.data_ptr(), n, N, M, K, dt,
-                                     torch.cuda.current_stream().cuda_stream)
+                                     _lib.ptr(x_max), out.data_ptr(), ws.data_ptr(), n, N, M, K, dt, _stream())
     _lib.check(rc, "mlgnn_linear_wgrad")
     if out_dtype is not None and out_dtype != torch.float32:
         out = out.to(out_dtype)                      # weight and bias gradient of a bf16 model: ONE converting copy
@@ -237,7 +234,6 @@ class _TallLinear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, residual):
-        from .ops import softmax_lse_of
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         # bf16: x is the output of a softmax aggregation -> its backward wants go * 2^(-lse), which the input-gradient
@@ -266,7 +262,6 @@ class _TallLinear(torch.autograd.Function):
             src = ctx.shift_src
             if (_BF16_SHIFT and src is not None and go.dtype == torch.bfloat16 and src[0].shape == (N, K)
                     and _lib.lib.mlgnn_tallgemm_bf16_shift_supported(N, M, K)):
-                from .ops import tag_shifted
                 gx, gt, flag = tall_matmul_bf16_shift(go, weight, src[0])
                 tag_shifted(gx, gt, flag, src[0])
             elif tall_matmul_supported(N, M, K, go.dtype):
@@ -301,21 +296,20 @@ class _FusedMLP2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, b1, gamma, beta, w2, b2, residual, eps, post_gamma=None, post_beta=None, post_eps=0.0,
                 post_relu=False):
-        from .ops import LN_FOLD, PostLN, row_max_of as _rm, softmax_lse_of
         # x is the output of a softmax aggregation: its backward wants go * 2^(-lse), which the input-gradient GEMM
         # below can write next to go
         ctx.shift_src = softmax_lse_of(x) if x.is_contiguous() else None
         # the residual is the `h` of an earlier op's (h, relu(LayerNorm(h))): its gradient can ride that LayerNorm's
-        # backward instead of being returned (mlgnn.ops.PostLN)
-        ctx.res_tag = getattr(residual, "_mlgnn_post_ln_of", None) if (LN_FOLD and residual is not None) else None
+        # backward instead of being returned (mlgnn.tags.PostLN)
+        ctx.res_tag = getattr(residual, "_mlgnn_post_ln_of", None) if (ops.LN_FOLD and residual is not None) else None
         ctx.post_tag = None
         x = x.contiguous()
-        xhat, rstd, rmax = tall_matmul_nt(x, w1, b1, None, _rm(x), ln=("out", gamma, beta, eps))
+        xhat, rstd, rmax = tall_matmul_nt(x, w1, b1, None, row_max_of(x), ln=("out", gamma, beta, eps))
         fuse = residual is not None and w2.shape[0] <= 128
         ctx.post = post_gamma is not None
         ctx.flags = (b1 is not None, b2 is not None)
         # row maxima of the weight-gradient operands (x; the activated hidden layer): their scales in the backward
-        ctx.maxima = (_rm(x), rmax)
+        ctx.maxima = (row_max_of(x), rmax)
         if ctx.post:
             out, y, mean2, rstd2 = tall_matmul_lnin_postln(xhat, w2, b2, residual, rmax, gamma, beta,
                                                            (post_gamma, post_beta, post_eps, post_relu))
@@ -323,7 +317,7 @@ class _FusedMLP2(torch.autograd.Function):
             ctx.post_dtype = post_gamma.dtype
             ctx.set_materialize_grads(False)
             ctx.save_for_backward(x, xhat, rstd, w1, w2, gamma, beta, out, mean2, rstd2, post_gamma, post_beta)
-            if LN_FOLD and post_gamma.dtype == torch.float32:
+            if ops.LN_FOLD and post_gamma.dtype == torch.float32:
                 # (detached alias of `out`: the tag is held by this node, and `out` itself points back to it)
                 ctx.post_tag = PostLN(out.detach(), mean2, rstd2, post_gamma.detach(), post_beta.detach(), post_relu)
             return out, y
@@ -335,13 +329,10 @@ class _FusedMLP2(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, go, go_y=None):
-        from .norm import ln_backward_normalised, ln_backward_saved
-        from .ops import row_max_of as _rm
-        from .ops import tag_row_max
         gpg = gpb = None
         if ctx.post:
             x, xhat, rstd, w1, w2, gamma, beta, out, mean2, rstd2, pg, pb = ctx.saved_tensors
-            # what the consumers of (out, y) left in the side channel (mlgnn.ops.PostLN): the aggregation that read y
+            # what the consumers of (out, y) left in the side channel (mlgnn.tags.PostLN): the aggregation that read y
             # may already have taken its gradient through this LayerNorm's backward, and the op that added `out` as its
             # residual may have parked that branch's gradient there
             tag, folded, pending = ctx.post_tag, None, None
@@ -380,20 +371,21 @@ class _FusedMLP2(torch.autograd.Function):
         x_max, act_max = ctx.maxima
         N = go.shape[0]
         gh_parts = None
-        if (_ONE_PASS and _rm(go) is not None and act_max is not None
+        if (_ONE_PASS and row_max_of(go) is not None and act_max is not None
                 and linear_backward_supported(N, w2.shape[0], w2.shape[1], LB_LN)):
             # second Linear: dW2, db2 and dA = go W2 from ONE pass over go and xhat, dA taken through ReLU + LayerNorm
             # backward in the same kernel (csrc/linear_bwd.hip)
-            r2 = linear_backward(go, w2, xhat, _rm(go), act_max, LB_LN, rstd=rstd, gamma=gamma, beta=beta)
+            r2 = linear_backward(go, w2, xhat, row_max_of(go), act_max, LB_LN, rstd=rstd, gamma=gamma, beta=beta)
             gh, gw2, gb2, ggamma, gbeta, gh_parts, gh_max = r2["dx"], r2["gw"], r2["gb"], r2["ggamma"], r2["gbeta"], r2["parts"], None
             LINEAR_BWD_STATS["ln"] += 1
         else:
-            gw2, gb2 = _wgrad(go, xhat, gamma.contiguous(), beta.contiguous(), go_max=_rm(go), x_max=act_max)   # go^T relu(gamma xhat + beta)
+            # go^T relu(gamma xhat + beta)
+            gw2, gb2 = _wgrad(go, xhat, gamma.contiguous(), beta.contiguous(), go_max=row_max_of(go), x_max=act_max)
             if tall_matmul_ln_backward_supported(go.shape[0], go.shape[1], w2.shape[1]):
                 # dA = go W2 never reaches memory: ReLU + LayerNorm backward run in the product's epilogue
-                gh, ggamma, gbeta, gh_max = tall_matmul_ln_backward(go, w2, xhat, rstd, gamma, beta, _rm(go))
+                gh, ggamma, gbeta, gh_max = tall_matmul_ln_backward(go, w2, xhat, rstd, gamma, beta, row_max_of(go))
             else:
-                gy = tall_matmul_nt(go, w2, row_max=_rm(go), bt_transposed=True)
+                gy = tall_matmul_nt(go, w2, row_max=row_max_of(go), bt_transposed=True)
                 gh, ggamma, gbeta, gh_max = ln_backward_normalised(gy, xhat, gamma, beta, rstd, relu=True)
         src = ctx.shift_src if ctx.needs_input_grad[0] else None
         gx = None
@@ -401,7 +393,6 @@ class _FusedMLP2(torch.autograd.Function):
                 and linear_backward_supported(N, w1.shape[0], w1.shape[1], LB_SHIFT)):
             # first Linear: dW1, db1, the input gradient and -- behind a softmax aggregation -- its rescaled cotangent
             # from one pass over gh and x
-            from .ops import tag_shifted
             epi = LB_SHIFT if src is not None else LB_PLAIN
             r1 = linear_backward(gh, w1, x, gh_parts if gh_parts is not None else gh_max, x_max, epi,
                                  lse=src[0] if src is not None else None, go_max_is_parts=gh_parts is not None)
@@ -413,7 +404,6 @@ class _FusedMLP2(torch.autograd.Function):
             gw1, gb1 = _wgrad(gh, x, go_max=gh_max, x_max=x_max)
             if ctx.needs_input_grad[0]:
                 if src is not None and _lib.lib.mlgnn_tallgemm_nt_shift_supported(gh.shape[0], gh.shape[1], w1.shape[1]):
-                    from .ops import tag_shifted
                     gx, gt, flag = tall_matmul_nt_shift(gh, w1, gh_max, src[0], src[1])
                     tag_shifted(gx, gt, flag, src[0])
                 else:
@@ -446,7 +436,6 @@ def fused_mlp2(x, w1, b1, gamma, beta, eps, w2, b2, residual=None, post_norm=Non
     out, y = _FusedMLP2.apply(x, w1, b1, gamma, beta, w2, b2, residual, float(eps), pw, pb, float(peps), bool(prelu))
     tag = getattr(out.grad_fn, "post_tag", None) if out.grad_fn is not None else None
     if tag is not None:
-        from .ops import tag_post_ln
         tag_post_ln(y, out, tag)
     return out, y
 
@@ -472,7 +461,7 @@ class _WideLinearF32(torch.autograd.Function):
         ws = torch.empty(int(_lib.lib.mlgnn_linear_f32x3_fwd_workspace_bytes(N, R, J)), dtype=torch.uint8, device=x.device)
         b = bias.contiguous() if bias is not None else None
         rc = _lib.lib.mlgnn_linear_f32x3_fwd(x.data_ptr(), weight.data_ptr(), _lib.ptr(b), y.data_ptr(), ws.data_ptr(),
-                                             ws.numel(), N, R, J, torch.cuda.current_stream().cuda_stream)
+                                             ws.numel(), N, R, J, _stream())
         _lib.check(rc, "mlgnn_linear_f32x3_fwd")
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
@@ -490,8 +479,7 @@ class _WideLinearF32(torch.autograd.Function):
         ws = torch.empty(int(_lib.lib.mlgnn_linear_f32x3_bwd_workspace_bytes(N, R, J)), dtype=torch.uint8, device=x.device)
         gb = torch.empty(J, dtype=torch.float32, device=x.device) if ctx.has_bias else None
         rc = _lib.lib.mlgnn_linear_f32x3_bwd(go.data_ptr(), x.data_ptr(), weight.data_ptr(), _lib.ptr(gx), gw.data_ptr(),
-                                             _lib.ptr(gb), ws.data_ptr(), ws.numel(), N, R, J,
-                                             torch.cuda.current_stream().cuda_stream)
+                                             _lib.ptr(gb), ws.data_ptr(), ws.numel(), N, R, J, _stream())
         _lib.check(rc, "mlgnn_linear_f32x3_bwd")
         return (gx[:N] if gx is not None else None), gw, gb
 
@@ -511,11 +499,8 @@ def _claim_grad_slot(param):
             return False
     except RuntimeError:                             # (raised under torch.autograd.grad(..., inputs=[param]))
         return False
-    task = torch._C._current_graph_task_id()
-    if task < 0 or getattr(param, "_mlgnn_slot_task", None) == task:
-        return False
-    param._mlgnn_slot_task = task
-    return True
+    task, last = backward_of(param)
+    return task >= 0 and task != last
 
 
 class _SkinnyLinear(torch.autograd.Function):
@@ -535,7 +520,7 @@ class _SkinnyLinear(torch.autograd.Function):
         ws = torch.empty(n, dtype=torch.float32, device=x.device)
         b = bias.contiguous() if bias is not None else None
         rc = _lib.lib.mlgnn_skinny_linear_fwd(x.data_ptr(), w.data_ptr(), _lib.ptr(b), y.data_ptr(), ws.data_ptr(), n, M, J, K,
-                                              torch.cuda.current_stream().cuda_stream)
+                                              _stream())
         _lib.check(rc, "mlgnn_skinny_linear_fwd")
         ctx.save_for_backward(x, w)
         ctx.has_bias = bias is not None
@@ -561,7 +546,7 @@ class _SkinnyLinear(torch.autograd.Function):
                 gw = torch.empty((J, K), dtype=torch.float32, device=x.device)
         gb = torch.empty(J, dtype=torch.float32, device=x.device) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
         rc = _lib.lib.mlgnn_skinny_linear_bwd(go.data_ptr(), x.data_ptr(), w.data_ptr(), _lib.ptr(gx), _lib.ptr(gw),
-                                              _lib.ptr(gb), M, J, K, torch.cuda.current_stream().cuda_stream)
+                                              _lib.ptr(gb), M, J, K, _stream())
         _lib.check(rc, "mlgnn_skinny_linear_bwd")
         return gx, gw, gb
 
@@ -579,8 +564,7 @@ class _NarrowLinear(torch.autograd.Function):
         J = w.shape[0]
         y = torch.empty((N, J), dtype=torch.float32, device=x.device)
         b = bias.contiguous() if bias is not None else None
-        rc = _lib.lib.mlgnn_narrow_linear_fwd(x.data_ptr(), w.data_ptr(), _lib.ptr(b), y.data_ptr(), N, R, J,
-                                              torch.cuda.current_stream().cuda_stream)
+        rc = _lib.lib.mlgnn_narrow_linear_fwd(x.data_ptr(), w.data_ptr(), _lib.ptr(b), y.data_ptr(), N, R, J, _stream())
         _lib.check(rc, "mlgnn_narrow_linear_fwd")
         ctx.save_for_backward(x, w)
         ctx.has_bias = bias is not None
@@ -598,7 +582,7 @@ class _NarrowLinear(torch.autograd.Function):
             ws = torch.empty(n, dtype=torch.float32, device=x.device)
             out = torch.empty(J * R + J, dtype=torch.float32, device=x.device)
             rc = _lib.lib.mlgnn_narrow_linear_bwd(go.data_ptr(), x.data_ptr(), out.data_ptr(), ws.data_ptr(), n, N, R, J,
-                                                  torch.cuda.current_stream().cuda_stream)
+                                                  _stream())
             _lib.check(rc, "mlgnn_narrow_linear_bwd")
             gw, gb = out[:J * R].view(J, R), (out[J * R:] if ctx.has_bias else None)
         gx = go.matmul(w) if ctx.needs_input_grad[0] else None
@@ -653,9 +637,8 @@ class _DenseSageFused(torch.autograd.Function):
         ctx.bias_dtype = bias.dtype if bias is not None else None
         bias32 = f32_cached(bias) if bias is not None else None           # the kernels add the bias in fp32
         rc = _lib.lib.mlgnn_dense_sage_fwd(x.data_ptr(), adj.data_ptr(), w_rel.data_ptr(), w_root.data_ptr(),
-                                           _lib.ptr(bias32), y.data_ptr(),
-                                           rinv.data_ptr(), B, n, C, O, int(batched), int(normalize), _dt(x),
-                                           torch.cuda.current_stream().cuda_stream)
+                                           _lib.ptr(bias32), y.data_ptr(), rinv.data_ptr(), B, n, C, O, int(batched),
+                                           int(normalize), _DTYPE_IDS[x.dtype], _stream())
         _lib.check(rc, "mlgnn_dense_sage_fwd")
         ctx.save_for_backward(x, adj, w_rel, w_root, y, rinv)
         ctx.cfg = (batched, bool(normalize), bias is not None)
@@ -677,7 +660,7 @@ class _DenseSageFused(torch.autograd.Function):
         rc = _lib.lib.mlgnn_dense_sage_bwd(gy.data_ptr(), y.data_ptr(), rinv.data_ptr(), x.data_ptr(), adj.data_ptr(),
                                            w_rel.data_ptr(), w_root.data_ptr(), gx.data_ptr(), _lib.ptr(gadj),
                                            gw.data_ptr(), ws.data_ptr(), ws_n, B, n, C, O, int(batched),
-                                           int(normalize), _dt(x), torch.cuda.current_stream().cuda_stream)
+                                           int(normalize), _DTYPE_IDS[x.dtype], _stream())
         _lib.check(rc, "mlgnn_dense_sage_bwd")
         if need_adj and not batched:
             gadj = gadj.float().sum(0, keepdim=True).to(adj.dtype).reshape(adj.shape)          # shared adjacency
@@ -729,7 +712,7 @@ class _DiffPoolFused(torch.autograd.Function):
         partial = torch.empty((B, 2), dtype=torch.float32, device=z.device)
         rc = _lib.lib.mlgnn_diffpool_fwd(z.data_ptr(), adj_k.data_ptr(), s.data_ptr(), S.data_ptr(),
                                          x_out.data_ptr(), a_out.data_ptr(), partial.data_ptr(), B, N, K, C,
-                                         int(batched), _dt(z), torch.cuda.current_stream().cuda_stream)
+                                         int(batched), _DTYPE_IDS[z.dtype], _stream())
         _lib.check(rc, "mlgnn_diffpool_fwd")
         tot = partial.sum(0)
         norm = torch.sqrt(tot[0])
@@ -752,7 +735,7 @@ class _DiffPoolFused(torch.autograd.Function):
         gx, ga = gx.to(z.dtype).contiguous(), ga.to(z.dtype).contiguous()
         rc = _lib.lib.mlgnn_diffpool_bwd(z.data_ptr(), adj.data_ptr(), S.data_ptr(), gx.data_ptr(), ga.data_ptr(),
                                          coef.data_ptr(), gz.data_ptr(), gs.data_ptr(), _lib.ptr(gadj), B, N, K, C,
-                                         int(batched), _dt(z), torch.cuda.current_stream().cuda_stream)
+                                         int(batched), _DTYPE_IDS[z.dtype], _stream())
         _lib.check(rc, "mlgnn_diffpool_bwd")
         if need_adj and not batched:
             gadj = gadj.float().sum(0, keepdim=True).to(adj.dtype).reshape(adj.shape)          # shared adjacency
@@ -780,10 +763,10 @@ class _DiffPoolLarge(torch.autograd.Function):
         stats = torch.empty(3, dtype=torch.float32, device=dev)
         scal = torch.empty(2, dtype=out_dtype, device=dev)
         ws = torch.empty(B * int(_lib.lib.mlgnn_diffpool_large_workspace_bytes(N, K, C)), dtype=torch.uint8, device=dev)
-        rc = _lib.lib.mlgnn_diffpool_large_fwd(zb.data_ptr(), ab.data_ptr(), s.data_ptr(), _dt(s), S.data_ptr(),
-                                               x_out.data_ptr(), a_out.data_ptr(), scal.data_ptr(), _dt(x_out),
-                                               stats.data_ptr(), ws.data_ptr(), ws.numel(), N, K, C, B, adj_batched,
-                                               torch.cuda.current_stream().cuda_stream)
+        rc = _lib.lib.mlgnn_diffpool_large_fwd(
+            zb.data_ptr(), ab.data_ptr(), s.data_ptr(), _DTYPE_IDS[s.dtype], S.data_ptr(), x_out.data_ptr(), a_out.data_ptr(),
+            scal.data_ptr(), _DTYPE_IDS[out_dtype], stats.data_ptr(), ws.data_ptr(), ws.numel(), N, K, C, B, adj_batched,
+            _stream())
         _lib.check(rc, "mlgnn_diffpool_large_fwd")
         ctx.save_for_backward(zb, ab, s, S, ws, stats)
         ctx.cfg = (bool(adj_symmetric), z.dtype, adj_batched)
@@ -808,21 +791,16 @@ class _DiffPoolLarge(torch.autograd.Function):
         gadj = torch.empty((B, N, N), dtype=s.dtype, device=dev) if ctx.needs_input_grad[1] else None
         wb = torch.empty(B * int(_lib.lib.mlgnn_diffpool_large_bwd_workspace_bytes(N, K, C, int(sym))), dtype=torch.uint8,
                          device=dev)
-        rc = _lib.lib.mlgnn_diffpool_large_bwd(zb.data_ptr(), ab.data_ptr(), s.data_ptr(), _dt(s), S.data_ptr(), ws.data_ptr(),
-                                               gx.data_ptr(), ga.data_ptr(), _dt(gx), g_link.data_ptr(), g_ent.data_ptr(),
-                                               _dt(g_link), stats.data_ptr(), gz.data_ptr(), gs.data_ptr(), _lib.ptr(gadj),
-                                               int(sym), wb.data_ptr(), wb.numel(), N, K, C, B, adj_batched,
-                                               torch.cuda.current_stream().cuda_stream)
+        rc = _lib.lib.mlgnn_diffpool_large_bwd(
+            zb.data_ptr(), ab.data_ptr(), s.data_ptr(), _DTYPE_IDS[s.dtype], S.data_ptr(), ws.data_ptr(), gx.data_ptr(),
+            ga.data_ptr(), _DTYPE_IDS[gdt], g_link.data_ptr(), g_ent.data_ptr(), _DTYPE_IDS[g_link.dtype], stats.data_ptr(),
+            gz.data_ptr(), gs.data_ptr(), _lib.ptr(gadj), int(sym), wb.data_ptr(), wb.numel(), N, K, C, B, adj_batched, _stream())
         _lib.check(rc, "mlgnn_diffpool_large_bwd")
         if gadj is not None:
             if not adj_batched and B > 1:
                 gadj = gadj.float().sum(0, keepdim=True)         # shared adjacency: the sum over the graphs that read it
             gadj = gadj.to(ctx.adj_dtype).reshape(ctx.adj_shape)
         return gz.to(z_dtype), gadj, gs, None
-
-
-def _dt(t):
-    return 1 if t.dtype == torch.bfloat16 else 0
 
 
 class _DiffPoolLargeFP32(torch.autograd.Function):
@@ -846,8 +824,7 @@ class _DiffPoolLargeFP32(torch.autograd.Function):
         ws = torch.empty(B * int(_lib.lib.mlgnn_diffpool_large_f32_workspace_bytes(N, K, C)), dtype=torch.uint8, device=dev)
         rc = _lib.lib.mlgnn_diffpool_large_f32_fwd(z.data_ptr(), adj.data_ptr(), s.data_ptr(), S.data_ptr(), x_out.data_ptr(),
                                                    a_out.data_ptr(), scal.data_ptr(), stats.data_ptr(), ws.data_ptr(),
-                                                   ws.numel(), N, K, C, B, adj_batched,
-                                                   torch.cuda.current_stream().cuda_stream)
+                                                   ws.numel(), N, K, C, B, adj_batched, _stream())
         _lib.check(rc, "mlgnn_diffpool_large_f32_fwd")
         ctx.save_for_backward(adj, s, ws, stats)
         ctx.cfg = (bool(adj_symmetric), adj_batched, (B, N, K, C))
@@ -870,7 +847,7 @@ class _DiffPoolLargeFP32(torch.autograd.Function):
         rc = _lib.lib.mlgnn_diffpool_large_f32_bwd(adj.data_ptr(), s.data_ptr(), ws.data_ptr(), gx.data_ptr(), ga.data_ptr(),
                                                    g_link.data_ptr(), g_ent.data_ptr(), stats.data_ptr(), gz.data_ptr(),
                                                    gs.data_ptr(), _lib.ptr(gadj), int(sym), wb.data_ptr(), wb.numel(),
-                                                   N, K, C, B, adj_batched, torch.cuda.current_stream().cuda_stream)
+                                                   N, K, C, B, adj_batched, _stream())
         _lib.check(rc, "mlgnn_diffpool_large_f32_bwd")
         if gadj is not None:
             if not adj_batched and B > 1:

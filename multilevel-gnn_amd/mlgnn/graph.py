@@ -9,6 +9,8 @@ import os
 
 import torch
 
+from . import _lib
+
 # rows (in-edges of a node for the forward, out-edges for the backward) longer than this are cut into chunks that
 # run as rows of their own and are combined in order (csrc/hub.hip); 0 disables
 HUB_CAP = int(os.environ.get("MLGNN_HUB_CAP", "256"))
@@ -102,7 +104,6 @@ class CSRGraph:
     def replicated(cls, single, copies):
         """``copies`` block-diagonal copies of the device graph ``single`` (``mlgnn_csr_replicate``): bit for bit the CSR
         of the batched edge list a PyG collate makes of ``copies`` samples that share one topology."""
-        from . import _lib
         n, e, B = single.num_nodes, single.num_edges, int(copies)
         if not single.rowptr.is_cuda:
             raise RuntimeError("replicated() works on device graphs")
@@ -150,7 +151,6 @@ class CSRGraph:
             self.hub_tables("src" if direction == "dst" else "dst")
             del self._hub[direction]
         if hit is None:
-            from . import _lib
             cap_rows = int(_lib.lib.mlgnn_hub_capacity(self.num_edges, cap))
             i32 = dict(dtype=torch.int32, device=self.device)
             vrows, hubs, counts = torch.empty((cap_rows, 3), **i32), torch.empty((cap_rows, 3), **i32), torch.empty(2, **i32)
@@ -193,7 +193,6 @@ class CSRGraph:
             tabs[6] = int(tabs[4][0]) > 0               # known on the host now, without ever having waited for it
         if tabs[6] is False:
             return None, ()                               # no row longer than HUB_CAP in this direction
-        from . import _lib
         vrows, hubs, counts, cap_rows = tabs[:4]
         nbytes = int(_lib.lib.mlgnn_hub_scratch_bytes(cap_rows, d))
         tmp = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
@@ -202,7 +201,6 @@ class CSRGraph:
 
     def _build_device(self, edge_index):
         """Two stable radix sorts on the GPU (``mlgnn_coo_to_csr``), enqueued on the current stream."""
-        from . import _lib
         N, E, dev = self.num_nodes, self.num_edges, self.device
         ei = edge_index.to(torch.int64).contiguous()
         i32 = dict(dtype=torch.int32, device=dev)
@@ -316,7 +314,6 @@ class CSRGraph:
         hit = ent[3] if (ent is not None and _same_view(ent[0], src) and ent[1] == src._version and ent[2] == width) else None
         if hit is None:
             if a.is_cuda and self.eid.is_cuda:
-                from . import _lib
                 rows = a if a.dtype == torch.float32 else a.to(torch.float32)
                 if rows.stride(1) != 1 and rows.shape[1] > 1:
                     rows = rows.contiguous()
@@ -375,7 +372,6 @@ def _sage_graph_device(edge_index, edge_attr, num_nodes):
     """One kernel writes the rewritten edge list (``mlgnn_sage_rewrite``: self loops parked on a spare node ``N``, the
     ``N`` unit-weight loops appended) instead of the mask / nonzero / two index / two cat launches of the torch form;
     the CSR is built over ``N + 1`` nodes and presented as an ``N``-node graph."""
-    from . import _lib
     E, N = int(edge_index.shape[1]), int(num_nodes)
     ei = edge_index.to(torch.int64).contiguous()
     attr, stride = None, 1

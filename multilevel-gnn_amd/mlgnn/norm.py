@@ -5,11 +5,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .ops import _DTYPE_IDS, DTYPE_F32, _stream, tag_row_max
-
-
-def _dtype_id(t):
-    return 1 if t.dtype == torch.bfloat16 else 0
+from .ops import _DTYPE_IDS, _stream
+from .tags import f32_cached, tag_row_max
 
 
 def fused_supported(x):
@@ -20,12 +17,6 @@ def fused_supported(x):
         d = x.shape[1]
         return (0 < d <= 256 and d % 4 == 0) or (256 < d <= 512 and d % 8 == 0)
     return x.dtype == torch.bfloat16 and 0 < x.shape[1] <= 512 and x.shape[1] % 8 == 0
-
-
-def _f32_params(weight, bias):
-    """gamma / beta as the kernels take them: fp32, contiguous (a bf16 model keeps bf16 parameters: [d] casts)."""
-    from .ops import f32_cached
-    return f32_cached(weight), f32_cached(bias)
 
 
 def _keep_mask(x, p):
@@ -46,7 +37,8 @@ class _LayerNormAct(torch.autograd.Function):
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
         ctx.param_dtype = weight.dtype
-        weight, bias = _f32_params(weight, bias)
+        # gamma / beta as the kernels take them: fp32, contiguous (a bf16 model keeps bf16 parameters: [d] casts)
+        weight, bias = f32_cached(weight), f32_cached(bias)
         # max |row| rides along for the fp32 split-precision GEMM that consumes the result; bf16 has no use for it
         ctx.row_max = torch.empty(rows, dtype=torch.float32, device=x.device) if x.dtype == torch.float32 else None
         if keep is not None and (keep.shape != x.shape or keep.dtype != torch.uint8 or not keep.is_contiguous()):
@@ -67,8 +59,9 @@ class _LayerNormAct(torch.autograd.Function):
         return gx, ggb[0], ggb[1], None, None, None, None
 
 
-def _ln_backward(ctx, go, extra):
-    x, weight, bias, mean, rstd = ctx.saved_tensors
+def _ln_bwd(go, x, weight, bias, mean, rstd, relu, extra=None, keep=None, keep_scale=1.0):
+    """The launch of ``mlgnn_layernorm_act_bwd`` (``weight`` / ``bias`` fp32, contiguous; ``mean`` None: ``x`` is stored
+    normalised): ``-> (grad_x (+ extra), [grad_gamma; grad_beta] [2, d] fp32, max |grad_x| per row -- fp32 storage only)``."""
     rows, d = x.shape
     go = go.contiguous()
     if extra is not None:
@@ -79,12 +72,16 @@ def _ln_backward(ctx, go, extra):
     n = int(_lib.lib.mlgnn_layernorm_bwd_workspace_floats(rows, d, dt))
     ws = torch.empty(n, dtype=torch.float32, device=x.device)
     row_max = torch.empty(rows, dtype=torch.float32, device=x.device) if x.dtype == torch.float32 else None
-    rc = _lib.lib.mlgnn_layernorm_act_bwd(go.data_ptr(), x.data_ptr(), weight.data_ptr(), bias.data_ptr(),
-                                          mean.data_ptr(), rstd.data_ptr(), _lib.ptr(extra), gx.data_ptr(),
-                                          _lib.ptr(row_max), ggb.data_ptr(), ws.data_ptr(), n, _lib.ptr(ctx.keep),
-                                          ctx.keep_scale, rows, d,
-                                          int(ctx.relu), dt, _stream())
+    rc = _lib.lib.mlgnn_layernorm_act_bwd(go.data_ptr(), x.data_ptr(), weight.data_ptr(), bias.data_ptr(), _lib.ptr(mean),
+                                          rstd.data_ptr(), _lib.ptr(extra), gx.data_ptr(), _lib.ptr(row_max), ggb.data_ptr(),
+                                          ws.data_ptr(), n, _lib.ptr(keep), keep_scale, rows, d, int(relu), dt, _stream())
     _lib.check(rc, "mlgnn_layernorm_act_bwd")
+    return gx, ggb, row_max
+
+
+def _ln_backward(ctx, go, extra):
+    x, weight, bias, mean, rstd = ctx.saved_tensors
+    gx, ggb, row_max = _ln_bwd(go, x, weight, bias, mean, rstd, ctx.relu, extra, ctx.keep, ctx.keep_scale)
     if row_max is not None:
         tag_row_max(gx, row_max)               # the gradient usually goes straight into a Linear's backward GEMM
     return gx, ggb.to(ctx.param_dtype)
@@ -94,22 +91,7 @@ def ln_backward_saved(go, x, weight, bias, mean, rstd, relu, extra=None):
     """LayerNorm(+ReLU) backward from the saved input and statistics, outside an autograd node of its own (the fused
     MLP's post-LayerNorm, :class:`mlgnn.dense._FusedMLP2`): ``-> (grad_x (+ extra), grad_gamma, grad_beta)``; the
     result carries its row maxima for the GEMMs that consume it."""
-    rows, d = x.shape
-    go = go.contiguous()
-    if extra is not None:
-        extra = extra.contiguous()
-    weight, bias = _f32_params(weight, bias)
-    gx = torch.empty_like(x)
-    ggb = torch.empty((2, d), dtype=torch.float32, device=x.device)
-    dt = _DTYPE_IDS[x.dtype]
-    n = int(_lib.lib.mlgnn_layernorm_bwd_workspace_floats(rows, d, dt))
-    ws = torch.empty(n, dtype=torch.float32, device=x.device)
-    row_max = torch.empty(rows, dtype=torch.float32, device=x.device) if x.dtype == torch.float32 else None
-    rc = _lib.lib.mlgnn_layernorm_act_bwd(go.data_ptr(), x.data_ptr(), weight.data_ptr(), bias.data_ptr(),
-                                          mean.data_ptr(), rstd.data_ptr(), _lib.ptr(extra), gx.data_ptr(),
-                                          _lib.ptr(row_max), ggb.data_ptr(), ws.data_ptr(), n, None, 1.0, rows, d,
-                                          int(relu), dt, _stream())
-    _lib.check(rc, "mlgnn_layernorm_act_bwd")
+    gx, ggb, row_max = _ln_bwd(go, x, f32_cached(weight), f32_cached(bias), mean, rstd, relu, extra)
     if row_max is not None:
         tag_row_max(gx, row_max)
     return gx, ggb[0], ggb[1]
@@ -117,20 +99,8 @@ def ln_backward_saved(go, x, weight, bias, mean, rstd, relu, extra=None):
 
 def ln_backward_normalised(go, xhat, weight, bias, rstd, relu=True):
     """LayerNorm(+ReLU) backward when the stored activation is already normalised (``xhat``, ``rstd`` from the
-    first GEMM of :class:`mlgnn.dense._FusedMLP2`): ``-> (grad_x, grad_gamma, grad_beta, max |grad_x| per row)``."""
-    rows, d = xhat.shape
-    go = go.contiguous()
-    gx = torch.empty_like(xhat)
-    ggb = torch.empty((2, d), dtype=torch.float32, device=xhat.device)
-    n = int(_lib.lib.mlgnn_layernorm_bwd_workspace_floats(rows, d, DTYPE_F32))
-    ws = torch.empty(n, dtype=torch.float32, device=xhat.device)
-    row_max = torch.empty(rows, dtype=torch.float32, device=xhat.device)
-    weight, bias = weight.contiguous(), bias.contiguous()
-    rc = _lib.lib.mlgnn_layernorm_act_bwd(go.data_ptr(), xhat.data_ptr(), weight.data_ptr(), bias.data_ptr(),
-                                          None, rstd.data_ptr(), None, gx.data_ptr(), row_max.data_ptr(),
-                                          ggb.data_ptr(), ws.data_ptr(), n, None, 1.0, rows, d, int(relu), DTYPE_F32,
-                                          _stream())
-    _lib.check(rc, "mlgnn_layernorm_act_bwd")
+    first GEMM of :class:`mlgnn.dense._FusedMLP2`, fp32): ``-> (grad_x, grad_gamma, grad_beta, max |grad_x| per row)``."""
+    gx, ggb, row_max = _ln_bwd(go, xhat, weight.contiguous(), bias.contiguous(), None, rstd, relu)
     return gx, ggb[0], ggb[1], row_max
 
 
@@ -188,7 +158,7 @@ class _MsgNormAdd(torch.autograd.Function):
         h = torch.empty_like(x)
         scale32 = scale if scale.dtype == torch.float32 else scale.float()       # the learnable scalar stays fp32
         rc = _lib.lib.mlgnn_msgnorm_add_fwd(x.data_ptr(), m.data_ptr(), scale32.data_ptr(), h.data_ptr(), rows, d,
-                                            _dtype_id(x), _stream())
+                                            _DTYPE_IDS[x.dtype], _stream())
         _lib.check(rc, "mlgnn_msgnorm_add_fwd")
         ctx.save_for_backward(x, m, scale32)
         ctx.scale_dtype = scale.dtype
@@ -205,7 +175,7 @@ class _MsgNormAdd(torch.autograd.Function):
         ws = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
         rc = _lib.lib.mlgnn_msgnorm_add_bwd(gh.data_ptr(), x.data_ptr(), m.data_ptr(), scale.data_ptr(),
                                             gx.data_ptr(), gm.data_ptr(), gs.data_ptr(), ws.data_ptr(), n, rows, d,
-                                            _dtype_id(x), _stream())
+                                            _DTYPE_IDS[x.dtype], _stream())
         _lib.check(rc, "mlgnn_msgnorm_add_bwd")
         return gx, gm, (gs.to(ctx.scale_dtype) if ctx.needs_input_grad[2] else None)
 

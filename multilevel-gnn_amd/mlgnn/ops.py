@@ -4,12 +4,15 @@ PyTorch owns memory and the autograd graph; every numeric step of the aggregatio
 libmlgnn.so.  All functions require CUDA(HIP) fp32 tensors and raise otherwise -- no CPU path.
 """
 import ctypes
+import functools
 import os
 
 import torch
 
 from . import _lib
-from .graph import CSRGraph
+from .graph import CSRGraph, _same_view
+from .tags import (PostLN, drop_stale, f32_cached, invalidate_param_cache, row_max_of, shifted_of,  # noqa: F401
+                   softmax_lse_of, tag_post_ln, tag_row_max, tag_shifted, tag_softmax_lse)
 
 MSG_IDENTITY, MSG_WEIGHTED, MSG_GEN = 0, 1, 2
 EDGE_NONE, EDGE_RANK1, EDGE_FULL = 0, 1, 2
@@ -117,145 +120,19 @@ def _dev_act(t, what, like=None):
     return t.contiguous()
 
 
-def tag_row_max(t, row_max):
-    """Attach ``max |row|`` ([N] fp32, written by the kernel that produced ``t``) to a 2-D tensor; the tall GEMM
-    reads it instead of streaming its operand twice.  Tied to the tensor's version: an in-place edit voids it."""
-    t._mlgnn_row_max = (row_max, t._version)
-    return t
-
-
-SHIFT_STATS = {"given": 0, "computed": 0}     # softmax backwards whose rescaled cotangent came from the producer / a pre-pass
-
-
-def tag_softmax_lse(out, lse, rowptr):
-    """Mark ``out`` as the result of a softmax aggregation with log-sum-exp ``lse`` [N,d] over the CSR ``rowptr``: the
-    Linear that consumes it can then emit, from its input-gradient GEMM, the rescaled cotangent this aggregation's
-    backward gathers (:func:`tag_shifted`)."""
-    out._mlgnn_lse = (lse, rowptr, out._version)
-    return out
-
-
-def softmax_lse_of(t):
-    tag = getattr(t, "_mlgnn_lse", None)
-    if tag is not None and tag[2] == t._version and tag[0].shape == t.shape:
-        return tag[0], tag[1]
-    return None
-
-
-def tag_shifted(grad, gt, flag, lse):
-    """Attach ``gt = grad * 2^(-lse)`` and its overflow flag to a cotangent on its way to the aggregation's backward."""
-    grad._mlgnn_gt = (gt, flag, lse.data_ptr(), grad._version)
-    return grad
-
-
-def shifted_of(grad, lse):
-    tag = getattr(grad, "_mlgnn_gt", None)
-    if (tag is not None and tag[3] == grad._version and tag[2] == lse.data_ptr() and tag[0].shape == grad.shape
-            and grad.is_contiguous() and tag[0].dtype == grad.dtype):
-        return tag[0], tag[1]
-    return None
-
-
-class PostLN:
-    """Side channel between the three nodes around a res+ block's pre-conv ``y = relu?(LayerNorm(h))``
-    (deepergcn.py:236-241) when ``y`` was written by the previous conv's last GEMM (:class:`mlgnn.dense._FusedMLP2`):
-
-    * the aggregation that consumes ``y`` takes the finished ``d loss / d y`` rows through the LayerNorm's backward in
-      its own row epilogue (``mlgnn_csr_aggregate_bwd_ln``), returns NO gradient for ``y`` and leaves
-      ``folded = (d loss / d h, d gamma, d beta, row maxima)`` here;
-    * the op that adds ``h`` as its residual (the same block's MLP) leaves the gradient of that identity branch in
-      ``extra`` instead of returning it, so that the epilogue above adds it in the same pass (``extra_used``);
-    * the producer of ``(h, y)`` picks both up in its backward -- and still runs the separate LayerNorm backward on
-      whatever gradient reaches ``y`` from other consumers.
-    Every field is consumed (reset) by the backward that reads it."""
-
-    def __init__(self, h, mean, rstd, gamma, beta, relu):
-        self.h, self.mean, self.rstd, self.gamma, self.beta, self.relu = h, mean, rstd, gamma, beta, bool(relu)
-        self.extra = None
-        self.extra_used = False
-        self.folded = None
-        self.task = None           # the backward (autograd graph task) that wrote extra / folded
-
-    def claim(self):
-        """Called by every backward that reads or writes a field: what another backward left is dropped (one that ran the
-        aggregation but not the producer, e.g. ``torch.autograd.grad`` for other inputs)."""
-        task = torch._C._current_graph_task_id()
-        if self.task is not None and task != self.task:      # (fields set outside any backward are taken over)
-            self.extra, self.extra_used, self.folded = None, False, None
-        self.task = task
-        return self
-
-
 # Off by default.  Measured at BASELINE configs[1] (same-box A/B, bench.py): the epilogue costs the aggregation backward
 # 0.13-0.27 ms per launch (per row / per pair of rows, operands prefetched or not, non-temporal or not) against the
 # 0.21 ms LayerNorm-backward launch it removes -- that kernel is bound by instruction issue and by the L2 hit rate of
 # its gather, and the epilogue adds to both; the step moved by -0.1 ... +0.1 ms.  MLGNN_LN_FOLD=1 turns it on.
 LN_FOLD = os.environ.get("MLGNN_LN_FOLD", "0") == "1"
 LN_FOLD_STATS = {"folded": 0, "separate": 0}
+SHIFT_STATS = {"given": 0, "computed": 0}     # softmax backwards whose rescaled cotangent came from the producer / a pre-pass
 
 
 if os.environ.get("MLGNN_PRINT_STATS", "0") == "1":          # development: which paths a run took
     import atexit
     import sys
     atexit.register(lambda: print("mlgnn stats: ln_fold %r" % (LN_FOLD_STATS,), file=sys.stderr))
-
-
-def tag_post_ln(y, h, tag):
-    y._mlgnn_post_ln = tag
-    h._mlgnn_post_ln_of = tag
-    return y
-
-
-_PARAM_EPOCH = [0]          # bumped after every step of ANY torch.optim.Optimizer (global post-step hook below)
-
-
-def _after_optimizer_step(optimizer, args, kwargs):
-    _PARAM_EPOCH[0] += 1
-    for group in optimizer.param_groups:
-        for p in group["params"]:
-            p._mlgnn_stepped = True
-
-
-try:                                                        # (public since torch 2.0)
-    from torch.optim.optimizer import register_optimizer_step_post_hook as _reg_post_hook
-    _reg_post_hook(_after_optimizer_step)
-except ImportError:                                         # pragma: no cover
-    pass
-
-
-def invalidate_param_cache():
-    """Call after editing parameters behind autograd's back outside an optimizer step (``p.data.copy_``, an EMA swap that
-    keeps the storage): drops every cached fp32 copy at its next use."""
-    _PARAM_EPOCH[0] += 1
-
-
-def f32_cached(t):
-    """``t`` as a contiguous fp32 tensor for a kernel argument (LayerNorm gamma / beta, a bias: the kernels read their
-    [d]-sized parameters in fp32).  A non-fp32 tensor is cast per call -- always correct -- unless it is a parameter some
-    ``torch.optim.Optimizer`` has stepped: its copy is then kept until the next optimizer step of the process (a global
-    post-step hook counts them: updates through ``p.data.copy_`` inside an optimizer, as the reference's utils/optim.py
-    does, are seen although they do not bump the version counter), a version bump, or a change of storage address /
-    device, so a bf16 model casts each parameter once per step instead of once per use (~20 tiny launches per layer at
-    BASELINE configs[4]).  Edits through ``.data`` between optimizer steps: :func:`invalidate_param_cache`.
-    Only for use inside autograd Functions (the copy is detached)."""
-    if t.dtype == torch.float32:
-        return t.contiguous()
-    if not getattr(t, "_mlgnn_stepped", False):
-        return t.detach().float().contiguous()
-    key = (_PARAM_EPOCH[0], t._version, t.data_ptr(), t.device)
-    tag = getattr(t, "_mlgnn_f32", None)
-    if tag is not None and tag[0] == key:
-        return tag[1]
-    c = t.detach().float().contiguous()
-    t._mlgnn_f32 = (key, c)
-    return c
-
-
-def row_max_of(t):
-    tag = getattr(t, "_mlgnn_row_max", None)
-    if tag is not None and tag[1] == t._version and tag[0].shape[0] == t.shape[0]:
-        return tag[0]
-    return None
 
 
 class LowRankEdge:
@@ -311,6 +188,25 @@ def padded_rank(r):
     return 1 if r <= 1 else 2 if r <= 2 else 4 if r <= 4 else 8
 
 
+def _sort_by_table_row(rows, T):
+    """``rows`` [E] (long): the table row of each edge -> ``(edge positions sorted (stably) by it, row pointer [T + 1])``, int32."""
+    order = torch.sort(rows, stable=True)[1].to(torch.int32)
+    rowptr = torch.zeros(T + 1, dtype=torch.int64, device=rows.device)
+    torch.cumsum(torch.bincount(rows, minlength=T), 0, out=rowptr[1:])
+    return order, rowptr.to(torch.int32)
+
+
+def _sum_rows_by_table_row(ge, order, rowptr, T):
+    """``out[t] = sum_{e: row(e) = t} ge[e]`` ([T, d] fp32) over a :func:`_sort_by_table_row` order: every table row
+    gathers and sums its cotangent rows in a fixed order (``csrc/embedding.hip``)."""
+    d = ge.shape[1]
+    out = torch.empty((T, d), dtype=torch.float32, device=ge.device)
+    rc = _lib.lib.mlgnn_embedding_bwd(ge.data_ptr(), order.data_ptr(), rowptr.data_ptr(), out.data_ptr(), T, d,
+                                      DTYPE_F32, _stream())
+    _lib.check(rc, "mlgnn_embedding_bwd")
+    return out
+
+
 class _EdgeTypeEmbedding(torch.autograd.Function):
     """``table[idx]`` for the per-edge type embedding of DeeperGCN (deepergcn.py:103-104,213) with the gradient
     ``grad_table[t] = sum_{e: idx[e] = t} grad_e[e]`` on ``csrc/embedding.hip``: the edge ids are sorted by type once
@@ -325,17 +221,9 @@ class _EdgeTypeEmbedding(torch.autograd.Function):
     @staticmethod
     def backward(ctx, ge):
         (idx,) = ctx.saved_tensors
-        T, d = ctx.rows, ge.shape[1]
         ge = ge.contiguous()
-        order = torch.sort(idx, stable=True)[1].to(torch.int32)
-        rowptr = torch.zeros(T + 1, dtype=torch.int64, device=idx.device)
-        torch.cumsum(torch.bincount(idx, minlength=T), 0, out=rowptr[1:])
-        rowptr = rowptr.to(torch.int32)
-        out = torch.empty((T, d), dtype=torch.float32, device=ge.device)
-        rc = _lib.lib.mlgnn_embedding_bwd(ge.data_ptr(), order.data_ptr(), rowptr.data_ptr(), out.data_ptr(), T, d,
-                                          DTYPE_F32, _stream())
-        _lib.check(rc, "mlgnn_embedding_bwd")
-        return out, None
+        order, rowptr = _sort_by_table_row(idx, ctx.rows)
+        return _sum_rows_by_table_row(ge, order, rowptr, ctx.rows), None
 
 
 def edge_type_embedding(table, idx):
@@ -373,17 +261,20 @@ class _GradSink:
         # csrc/embedding.hip) -- `total` collects the layers of one backward
         self.fix = None
         self.total = None
-        self.task = None           # the backward (autograd graph task) that wrote buf / total
 
     def claim(self):
         """Called by every backward that reads or adds into the sink: contents left by another backward are dropped.  A
         backward that runs the consumers but not the fan-out node (``torch.autograd.grad`` for other inputs) would
         otherwise leave its edge gradient here for the next one to add on top of."""
-        task = torch._C._current_graph_task_id()
-        if self.task is not None and task != self.task:
-            self.buf = self.total = None
-        self.task = task
-        return self
+        return drop_stale(self, buf=None, total=None)
+
+    def table_total(self, T, d, device):
+        """The table's gradient accumulator ``[T, d]`` of this backward, created on first use: ``(total, accumulate)``
+        -- ``accumulate`` 0 tells the kernel to overwrite it (the first layer of the backward), 1 to add."""
+        if self.total is not None:
+            return self.total, 1
+        self.total = torch.empty((T, d), dtype=torch.float32, device=device)
+        return self.total, 0
 
 
 class _EdgeFanout(torch.autograd.Function):
@@ -427,11 +318,7 @@ class _TableFanout(torch.autograd.Function):
         total = None
         if per_edge is not None:
             order, rowptr = ctx.owner.sorted_by_type(ctx.sink.graph)
-            T, d = ctx.owner.table_rows, per_edge.shape[1]
-            total = torch.empty((T, d), dtype=torch.float32, device=per_edge.device)
-            rc = _lib.lib.mlgnn_embedding_bwd(per_edge.data_ptr(), order.data_ptr(), rowptr.data_ptr(),
-                                              total.data_ptr(), T, d, DTYPE_F32, _stream())
-            _lib.check(rc, "mlgnn_embedding_bwd")
+            total = _sum_rows_by_table_row(per_edge, order, rowptr, ctx.owner.table_rows)
         if direct is not None:
             total = direct if total is None else total + direct
         if g is not None:
@@ -471,7 +358,6 @@ class TableEdge:
     def _graph_cache(self, graph):
         """The dict on ``graph`` that holds what this term derived from (``source``, graph): valid while ``source`` is the
         same view at the same version (the entry holds the tensor, so its storage cannot be recycled under it)."""
-        from .graph import _same_view
         src = self.source
         if src is None:
             return None
@@ -509,15 +395,10 @@ class TableEdge:
             if shared is not None and "sorted" in shared:
                 self._sorted = (key,) + shared["sorted"]
                 return self._sorted[1], self._sorted[2]
-            by_src = self.rows_for(graph)[1].long()
-            order = torch.sort(by_src, stable=True)[1].to(torch.int32)
-            rowptr = torch.zeros(self.table_rows + 1, dtype=torch.int64, device=self.idx.device)
-            torch.cumsum(torch.bincount(by_src, minlength=self.table_rows), 0, out=rowptr[1:])
-            self._sorted = (key, order, rowptr.to(torch.int32))
+            self._sorted = (key,) + _sort_by_table_row(self.rows_for(graph)[1].long(), self.table_rows)
             if shared is not None:
                 shared["sorted"] = (self._sorted[1], self._sorted[2])
         return self._sorted[1], self._sorted[2]
-
 
     def winners_by_type(self, graph):
         """``(by-destination edge positions sorted (stably) by table row, the destination node of each, row pointer,
@@ -527,13 +408,10 @@ class TableEdge:
         store = shared if shared is not None else self.__dict__.setdefault("_winners", {})
         key = "winners" if shared is not None else id(graph)
         if key not in store:
-            by_dst = self.rows_for(graph)[0].long()
-            order = torch.sort(by_dst, stable=True)[1]
-            rowptr = torch.zeros(self.table_rows + 1, dtype=torch.int64, device=self.idx.device)
-            torch.cumsum(torch.bincount(by_dst, minlength=self.table_rows), 0, out=rowptr[1:])
-            rp = graph.rowptr.long()
+            pos, rowptr = _sort_by_table_row(self.rows_for(graph)[0].long(), self.table_rows)
+            rp, order = graph.rowptr.long(), pos.long()
             dst = torch.searchsorted(rp, order, right=True) - 1
-            store[key] = (order.to(torch.int32), dst.to(torch.int32), rowptr.to(torch.int32), (order - rp[dst]).to(torch.int32))
+            store[key] = (pos, dst.to(torch.int32), rowptr, (order - rp[dst]).to(torch.int32))
         return store[key]
 
 
@@ -546,13 +424,50 @@ def share_edge_gradient(e):
     return out
 
 
+def _aggregate_fwd(x, graph, out, msg, aggr_id, hub, ew_pair=None, eu=None, ev=None, efull=None, eid=None, aux=None, aux2=None,
+                   argmax=None, rowmax=None, edge_mode=EDGE_NONE, rank=0, t=1.0, p=1.0, t_dev=None, p_dev=None, eps=0.0,
+                   add_root=False):
+    """The launch of ``mlgnn_csr_aggregate_fwd`` (include/mlgnn.h): ``out`` [N, d] from ``x`` over the by-destination CSR of
+    ``graph``.  ``hub``: from ``graph.hub_arg("dst", d)`` (the caller holds its second value until this returns);
+    ``ew_pair``: per-edge scalars in (by-destination, by-source) order -- the forward reads the first, the backward the second."""
+    N, d = x.shape
+    ew = ew_pair[0] if ew_pair is not None else None
+    rc = _lib.lib.mlgnn_csr_aggregate_fwd(
+        x.data_ptr(), graph.rowptr.data_ptr(), graph.col.data_ptr(), _lib.ptr(ew), _lib.ptr(eu), _lib.ptr(ev),
+        _lib.ptr(efull), _lib.ptr(eid), out.data_ptr(), _lib.ptr(aux), _lib.ptr(aux2), _lib.ptr(argmax),
+        _lib.ptr(rowmax), N, d, _DTYPE_IDS[x.dtype], msg, edge_mode, rank, aggr_id, float(t), float(p),
+        _lib.ptr(t_dev), _lib.ptr(p_dev), float(eps), int(add_root), hub, _stream())
+    _lib.check(rc, "mlgnn_csr_aggregate_fwd")
+
+
+def _aggregate_bwd(go, graph, gx, msg, aggr_id, hub, x=None, out=None, aux=None, argmax=None, ew_pair=None, eu=None, ev=None,
+                   efull=None, eid_t=None, geid_t=None, ge=None, ge_accumulate=0, guv=None, ws=None, ws_n=0,
+                   edge_mode=EDGE_NONE, rank=0, learn_t=False, t=1.0, p=1.0, t_dev=None, p_dev=None, eps=0.0,
+                   add_root=False, shifted=None, ln=None):
+    """The launch of ``mlgnn_csr_aggregate_bwd`` (include/mlgnn.h): ``gx`` [N, d] from the cotangent ``go`` over the by-source
+    CSR of ``graph``; ``hub`` from ``graph.hub_arg("src", d)``.  ``ln`` (an ``_lib.LnFoldStruct``; ``hub`` must be None, it takes
+    no hub table): ``mlgnn_csr_aggregate_bwd_ln`` -- the LayerNorm backward in the row epilogue, the struct behind the arguments."""
+    N, d = go.shape
+    ew_t = ew_pair[1] if ew_pair is not None else None
+    args = (go.data_ptr(), _lib.ptr(x), _lib.ptr(out), _lib.ptr(aux), _lib.ptr(argmax),
+            graph.rowptr_t.data_ptr(), graph.col_t.data_ptr(), graph.pos_t.data_ptr(), graph.rowptr.data_ptr(),
+            _lib.ptr(ew_t), _lib.ptr(eu), _lib.ptr(ev), _lib.ptr(efull), _lib.ptr(eid_t), _lib.ptr(geid_t),
+            gx.data_ptr(), _lib.ptr(ge), _lib.ptr(guv), _lib.ptr(ws), ws_n,
+            N, d, _DTYPE_IDS[go.dtype], msg, edge_mode, rank, aggr_id, int(learn_t), t, p,
+            _lib.ptr(t_dev), _lib.ptr(p_dev), eps, int(add_root), ge_accumulate, hub,
+            _lib.ptr(shifted[0]) if shifted else None, _lib.ptr(shifted[1]) if shifted else None)
+    if ln is None:
+        _lib.check(_lib.lib.mlgnn_csr_aggregate_bwd(*args, _stream()), "mlgnn_csr_aggregate_bwd")
+    else:
+        _lib.check(_lib.lib.mlgnn_csr_aggregate_bwd_ln(*args, ctypes.byref(ln), _stream()), "mlgnn_csr_aggregate_bwd_ln")
+
+
 class _GenAggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, eu, ev, efull, t_par, p_par, graph, ew_pair, aggr_id, t, p, eps, learn_t, learn_p, add_root,
                 table_edge=None):
         post_ln = getattr(x, "_mlgnn_post_ln", None)
         x = _dev_act(x, "x")
-        dtype_id = _DTYPE_IDS[x.dtype]
         N, d = x.shape
         # x = relu?(LayerNorm(h)) written by the previous conv's GEMM: its backward can run in this op's row epilogue
         ctx.post_ln = post_ln if (LN_FOLD and post_ln is not None and add_root and not learn_t and not learn_p
@@ -592,7 +507,6 @@ class _GenAggregate(torch.autograd.Function):
         aux2 = torch.empty((N, d), **f32) if ((aggr_id == AGGR_SOFTMAX and learn_t) or
                                               (aggr_id == AGGR_POWER and learn_p)) else None
         argmax = torch.empty((N, d), dtype=torch.int32, device=x.device) if aggr_id == AGGR_MAX else None
-        ew = ew_pair[0] if ew_pair is not None else None
         t_dev = t_par if (learn_t and t_par is not None) else None
         p_dev = p_par if (learn_p and p_par is not None) else None
         if (t_dev is not None and t_dev.dtype != torch.float32) or (p_dev is not None and p_dev.dtype != torch.float32):
@@ -604,12 +518,9 @@ class _GenAggregate(torch.autograd.Function):
         hub, hub_keep = graph.hub_arg("dst", d)
         if hub is not None and aggr_id in (AGGR_SOFTMAX, AGGR_POWER) and aux is None:
             aux = torch.empty((N, d), **f32)                  # the chunks of a long row are combined through their lse
-        rc = _lib.lib.mlgnn_csr_aggregate_fwd(
-            x.data_ptr(), graph.rowptr.data_ptr(), graph.col.data_ptr(), _lib.ptr(ew), _lib.ptr(eu), _lib.ptr(ev),
-            _lib.ptr(efull), eid_fwd.data_ptr(), out.data_ptr(), _lib.ptr(aux), _lib.ptr(aux2),
-            _lib.ptr(argmax), _lib.ptr(rowmax), N, d, dtype_id, MSG_GEN, edge_mode, rank, aggr_id, float(t), float(p),
-            _lib.ptr(t_dev), _lib.ptr(p_dev), float(eps), int(add_root), hub, _stream())
-        _lib.check(rc, "mlgnn_csr_aggregate_fwd")
+        _aggregate_fwd(x, graph, out, MSG_GEN, aggr_id, hub, ew_pair=ew_pair, eu=eu, ev=ev, efull=efull, eid=eid_fwd, aux=aux,
+                       aux2=aux2, argmax=argmax, rowmax=rowmax, edge_mode=edge_mode, rank=rank, t=t, p=p, t_dev=t_dev,
+                       p_dev=p_dev, eps=eps, add_root=add_root)
         del hub_keep
         if timer is not None:
             timer.stop("csr_aggregate_fwd/%s/%s" % (_AGGR_NAMES[aggr_id], _edge_name(edge_mode, rank)), t0,
@@ -625,17 +536,16 @@ class _GenAggregate(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, go):
-        x, out, aux, aux2, argmax, eu, ev, efull, t_dev, p_dev = ctx.saved_tensors
+        saved = ctx.saved_tensors
+        x, out, aux, aux2, argmax, eu, ev, efull, t_dev, p_dev = saved
         aggr_id, edge_mode, rank, t, p, eps, learn_t, learn_p, add_root = ctx.cfg
-        g = ctx.graph
+        g, sink, te = ctx.graph, ctx.grad_sink, ctx.table_edge
         N, d = x.shape
         # the producer of grad_out may already have written the rescaled cotangent the softmax backward gathers
         # (mlgnn.dense: the input-gradient GEMM of the Linear behind this aggregation, csrc/tallgemm.hip SHIFT)
         shifted = shifted_of(go, aux) if (aggr_id == AGGR_SOFTMAX and not learn_t and aux is not None) else None
         go = _dev_act(go, "grad_out", like=x)
-        dtype_id = _DTYPE_IDS[x.dtype]
-        grad_t = grad_p = None
-        go_k = go
+        go_k, grad_t, grad_p = go, None, None
         if aggr_id == AGGR_POWER:
             # the cotangent through the outer power and the mean (and d loss / dp): one streaming pass (csrc/power.hip)
             go_k = torch.empty_like(go)
@@ -644,186 +554,213 @@ class _GenAggregate(torch.autograd.Function):
             pw_ws = torch.empty(pw_n, dtype=torch.float32, device=x.device) if learn_p else None
             rc = _lib.lib.mlgnn_power_bwd_prologue(go.data_ptr(), aux.data_ptr(), g.rowptr.data_ptr(), _lib.ptr(out if learn_p else None),
                                                    _lib.ptr(aux2 if learn_p else None), float(p), _lib.ptr(p_dev), go_k.data_ptr(),
-                                                   _lib.ptr(gp), _lib.ptr(pw_ws), pw_n, N, d, dtype_id, _stream())
+                                                   _lib.ptr(gp), _lib.ptr(pw_ws), pw_n, N, d, _DTYPE_IDS[x.dtype], _stream())
             _lib.check(rc, "mlgnn_power_bwd_prologue")
             if learn_p:
                 grad_p = gp.to(p_dev.dtype)
         if aggr_id == AGGR_SOFTMAX and learn_t:
             grad_t = (go.float() * (aux2 - out.float() * out.float())).sum().reshape(1).to(t_dev.dtype)
         gx = torch.empty_like(x)
-        ge, ge_accumulate, sink, te = None, 0, ctx.grad_sink, ctx.table_edge
-        eid_t, geid_t = g.eid_t, None
         if sink is not None:
             sink.claim()
-        if te is not None:                                   # read the table row, write the edge's own gradient row
-            _, eid_t, geid_t = te.rows_for(g)                # (gradient rows in by-source order: a streamed write)
-            if sink is not None:
-                if sink.graph is not None and sink.graph is not g:
-                    raise RuntimeError("a TableEdge is tied to one graph (one batch)")
-                sink.graph = g
-        # max over a table edge term: only the winning edge of (i, c) has a gradient -- it goes straight to the table's
-        # fixed-point accumulator inside the kernel (no [E, d] gradient written, re-read and reduced)
-        fix_table = (TABLE_DIRECT and te is not None and sink is not None and aggr_id == AGGR_MAX and edge_mode == EDGE_FULL
-                     and x.dtype == torch.float32 and d % 4 == 0 and ctx.post_ln is None)
-        sparse = (SPARSE_MAX and not fix_table and aggr_id == AGGR_MAX and x.dtype == torch.float32 and argmax is not None
-                  and ctx.post_ln is None and g.num_edges > 0 and go_k.data_ptr() % 16 == 0 and argmax.data_ptr() % 16 == 0
-                  and (edge_mode == EDGE_NONE or (edge_mode == EDGE_FULL and te is not None and TABLE_DEST))
-                  and int(_lib.lib.mlgnn_max_sparse_records(N, d, g.num_edges)) > 0 and g.known_short_rows())
-        if sparse:
-            # every (node, channel) has ONE winning edge: its cotangent goes to that edge's source -- and to the table row
-            # the edge reads -- through compact per-edge runs of (value, channel) pairs instead of whole gathered rows
-            dev = x.device
-            recs = torch.empty((int(_lib.lib.mlgnn_max_sparse_records(N, d, g.num_edges)), 2), dtype=torch.int32, device=dev)
-            meta = torch.empty((g.num_edges, 2), dtype=torch.int32, device=dev)
-            rc = _lib.lib.mlgnn_max_winners(go_k.data_ptr(), argmax.data_ptr(), g.rowptr.data_ptr(), recs.data_ptr(),
-                                            meta.data_ptr(), N, d, _stream())
-            _lib.check(rc, "mlgnn_max_winners")
-            rc = _lib.lib.mlgnn_max_sparse_bwd(recs.data_ptr(), meta.data_ptr(), g.rowptr_t.data_ptr(), g.pos_t.data_ptr(),
-                                               go_k.data_ptr() if add_root else None, gx.data_ptr(), N, d, _stream())
-            _lib.check(rc, "mlgnn_max_sparse_bwd")
-            SPARSE_MAX_STATS["calls"] += 1
-            if te is not None and sink is not None:
-                T = te.table_rows
-                first = sink.total is None
-                if first:
-                    sink.total = torch.empty((T, d), dtype=torch.float32, device=dev)
-                if bool(_lib.lib.mlgnn_max_table_grad_supported(N, d, T)):
-                    rows_dst = te.rows_for(g)[0]              # a few table rows: the streaming pass with LDS partial tables
-                    mt_n = int(_lib.lib.mlgnn_max_table_grad_workspace_floats(N, d, T))
-                    mt_ws = torch.empty(mt_n, dtype=torch.float32, device=dev)
-                    rc = _lib.lib.mlgnn_max_table_grad(go_k.data_ptr(), argmax.data_ptr(), rows_dst.data_ptr(),
-                                                       sink.total.data_ptr(), mt_ws.data_ptr(), mt_n, N, d, T,
-                                                       0 if first else 1, _stream())
-                    _lib.check(rc, "mlgnn_max_table_grad")
-                    TABLE_DEST_STATS["streamed"] += 1
-                else:
-                    pos_s, _, rp_s, _ = te.winners_by_type(g)
-                    rc = _lib.lib.mlgnn_max_sparse_table_grad(recs.data_ptr(), meta.data_ptr(), pos_s.data_ptr(), rp_s.data_ptr(),
-                                                              sink.total.data_ptr(), N, d, T, 0 if first else 1, _stream())
-                    _lib.check(rc, "mlgnn_max_sparse_table_grad")
-                    SPARSE_MAX_STATS["table"] += 1
-                TABLE_DEST_STATS["calls"] += 1
-            return gx, None, None, None, grad_t, grad_p, None, None, None, None, None, None, None, None, None, None
-        by_type_after = False
-        dest_table = (not fix_table and TABLE_DEST and te is not None and sink is not None and aggr_id == AGGR_MAX
-                      and edge_mode == EDGE_FULL and x.dtype == torch.float32 and argmax is not None and d % 4 == 0
-                      and go_k.data_ptr() % 16 == 0 and argmax.data_ptr() % 16 == 0)
-        if dest_table:
-            T = te.table_rows
-            first = sink.total is None
-            if first:
-                sink.total = torch.empty((T, d), dtype=torch.float32, device=x.device)
-            if bool(_lib.lib.mlgnn_max_table_grad_supported(N, d, T)):
-                # a few table rows: one streaming pass, per-workgroup partial tables in LDS
-                rows_dst = te.rows_for(g)[0]
-                mt_n = int(_lib.lib.mlgnn_max_table_grad_workspace_floats(N, d, T))
-                mt_ws = torch.empty(mt_n, dtype=torch.float32, device=x.device)
-                rc = _lib.lib.mlgnn_max_table_grad(go_k.data_ptr(), argmax.data_ptr(), rows_dst.data_ptr(),
-                                                   sink.total.data_ptr(), mt_ws.data_ptr(), mt_n, N, d, T, 0 if first else 1,
-                                                   _stream())
-                _lib.check(rc, "mlgnn_max_table_grad")
-                TABLE_DEST_STATS["streamed"] += 1
-            else:
-                by_type_after = True                         # (below, behind the backward: it reads that call's winner slots)
-            TABLE_DEST_STATS["calls"] += 1
-            ge, ge_accumulate, geid_t = None, 3, None
-        elif fix_table:
-            T = te.table_rows
-            if sink.fix is None or sink.fix.numel() != int(_lib.lib.mlgnn_table_grad_bytes(T, d)):
-                sink.fix = torch.zeros(int(_lib.lib.mlgnn_table_grad_bytes(T, d)), dtype=torch.uint8, device=x.device)
-            _lib.check(_lib.lib.mlgnn_table_grad_begin(go_k.data_ptr(), N, d, sink.fix.data_ptr(), _stream()),
-                       "mlgnn_table_grad_begin")
-            ge, ge_accumulate, geid_t = sink.fix, 2, eid_t
-        elif edge_mode == EDGE_FULL and (te is None or sink is not None):
-            if sink is not None and sink.buf is not None:
-                ge, ge_accumulate = sink.buf, 1              # add this layer's share to the layers that ran before
-            else:
-                ge = torch.empty_like(efull) if te is None else torch.empty((g.num_edges, d), dtype=efull.dtype,
-                                                                            device=efull.device)
-                if sink is not None:
-                    sink.buf = ge
-        elif edge_mode == EDGE_FULL:                         # a table without gradient: scratch row space
-            ge = torch.empty((g.num_edges, d), dtype=efull.dtype, device=efull.device)
-        guv = ws = None
-        ws_n = int(_lib.lib.mlgnn_csr_aggregate_bwd_workspace_floats(N, d, dtype_id, rank,
-                                                                     AGGR_SUM if shifted is not None else aggr_id,
-                                                                     int(learn_t)))
-        if ws_n < 0:
-            _lib.check(ws_n, "mlgnn_csr_aggregate_bwd_workspace_floats")
-        if ws_n > 0:
-            ws = torch.empty(ws_n, dtype=torch.float32, device=x.device)
-        if edge_mode == EDGE_RANK1:
-            guv = torch.empty((rank + 1, d), dtype=torch.float32, device=x.device)
-        ew_t = ctx.ew_pair[1] if ctx.ew_pair is not None else None
-        timer = KERNEL_TIMER
-        t0 = timer.start() if timer is not None else None
-        hub, hub_keep = g.hub_arg("src", d)
-        tag = ctx.post_ln if (hub is None and ctx.needs_input_grad[0]) else None
-        if tag is not None:
-            tag.claim()
-            # d loss / d y goes through the LayerNorm backward of y = relu?(LayerNorm(h)) in the row epilogue; gx is then
-            # d loss / d h (+ the identity-branch gradient the block's MLP left in tag.extra)
-            f32 = dict(dtype=torch.float32, device=x.device)
-            ln_n = int(_lib.lib.mlgnn_csr_aggregate_bwd_ln_workspace_floats(N, d))
-            ln_ws, ggb, row_max = torch.empty(ln_n, **f32), torch.empty((2, d), **f32), torch.empty(N, **f32)
-            extra = tag.extra if (tag.extra is not None and tag.extra.dtype == torch.float32
-                                  and tag.extra.shape == x.shape and tag.extra.is_contiguous()) else None
-            gamma, beta = f32_cached(tag.gamma), f32_cached(tag.beta)
-            st = _lib.LnFoldStruct(tag.h.data_ptr(), tag.mean.data_ptr(), tag.rstd.data_ptr(), gamma.data_ptr(),
-                                   beta.data_ptr(), _lib.ptr(extra), row_max.data_ptr(), ggb.data_ptr(), ln_ws.data_ptr(),
-                                   ln_n, int(tag.relu))
-            rc = _lib.lib.mlgnn_csr_aggregate_bwd_ln(
-                go_k.data_ptr(), x.data_ptr(), out.data_ptr(), _lib.ptr(aux), _lib.ptr(argmax),
-                g.rowptr_t.data_ptr(), g.col_t.data_ptr(), g.pos_t.data_ptr(), g.rowptr.data_ptr(),
-                _lib.ptr(ew_t), _lib.ptr(eu), _lib.ptr(ev), _lib.ptr(efull), eid_t.data_ptr(), _lib.ptr(geid_t),
-                gx.data_ptr(), _lib.ptr(ge), _lib.ptr(guv), _lib.ptr(ws), ws_n,
-                N, d, dtype_id, MSG_GEN, edge_mode, rank, aggr_id, int(learn_t), t, p,
-                _lib.ptr(t_dev), _lib.ptr(p_dev), eps, int(add_root), ge_accumulate, None,
-                _lib.ptr(shifted[0]) if shifted else None, _lib.ptr(shifted[1]) if shifted else None,
-                ctypes.byref(st), _stream())
-            _lib.check(rc, "mlgnn_csr_aggregate_bwd_ln")
-            tag.folded = (gx, ggb[0], ggb[1], row_max)
-            tag.extra_used = extra is not None
-            LN_FOLD_STATS["folded"] += 1
-            gx = None                                        # nothing reaches y through autograd: see PostLN
+        if te is not None and sink is not None:
+            if sink.graph is not None and sink.graph is not g:
+                raise RuntimeError("a TableEdge is tied to one graph (one batch)")
+            sink.graph = g
+        route = _edge_grad_route(ctx, x, argmax, go_k)       # chosen once: the ROUTE_* list below, in order of precedence
+        ge = guv = None
+        if route == ROUTE_WINNERS:
+            _max_winners_backward(go_k, argmax, g, gx, add_root, te, sink)          # (no KERNEL_TIMER record)
         else:
-            LN_FOLD_STATS["separate"] += int(ctx.post_ln is not None)
-            rc = _lib.lib.mlgnn_csr_aggregate_bwd(
-                go_k.data_ptr(), x.data_ptr(), out.data_ptr(), _lib.ptr(aux), _lib.ptr(argmax),
-                g.rowptr_t.data_ptr(), g.col_t.data_ptr(), g.pos_t.data_ptr(), g.rowptr.data_ptr(),
-                _lib.ptr(ew_t), _lib.ptr(eu), _lib.ptr(ev), _lib.ptr(efull), eid_t.data_ptr(), _lib.ptr(geid_t),
-                gx.data_ptr(), _lib.ptr(ge), _lib.ptr(guv), _lib.ptr(ws), ws_n,
-                N, d, dtype_id, MSG_GEN, edge_mode, rank, aggr_id, int(learn_t), t, p,
-                _lib.ptr(t_dev), _lib.ptr(p_dev), eps, int(add_root), ge_accumulate, hub,
-                _lib.ptr(shifted[0]) if shifted else None, _lib.ptr(shifted[1]) if shifted else None, _stream())
-            _lib.check(rc, "mlgnn_csr_aggregate_bwd")
-        del hub_keep
-        if by_type_after:
-            # one row per KEGG membership (tens of thousands): a wavefront per table row gathers its edges' winners
-            pos_s, dst_s, rp_s, rel_s = te.winners_by_type(g)
-            off = int(_lib.lib.mlgnn_csr_aggregate_bwd_slots_offset_floats(N, d, rank))
-            slots = ws.data_ptr() + 4 * off if (ws is not None and off >= 0 and TABLE_SLOTS) else None
-            rc = _lib.lib.mlgnn_max_table_grad_by_type(go_k.data_ptr(), argmax.data_ptr(), dst_s.data_ptr(), pos_s.data_ptr(),
-                                                       rel_s.data_ptr(), rp_s.data_ptr(), slots, sink.total.data_ptr(), N, d,
-                                                       te.table_rows, 0 if first else 1, _stream())
-            _lib.check(rc, "mlgnn_max_table_grad_by_type")
-            TABLE_DEST_STATS["by_type"] += 1
-        if fix_table:
-            first = sink.total is None
-            if first:
-                sink.total = torch.empty((te.table_rows, d), dtype=torch.float32, device=x.device)
-            _lib.check(_lib.lib.mlgnn_table_grad_finish(sink.fix.data_ptr(), sink.total.data_ptr(), te.table_rows, d,
-                                                        0 if first else 1, _stream()), "mlgnn_table_grad_finish")
-        SHIFT_STATS["given" if shifted else "computed"] += int(aggr_id == AGGR_SOFTMAX and not learn_t)
-        if sink is not None or te is not None:
-            ge = None                                        # reported once, by the fan-out node of the shared term
-        if timer is not None:
-            timer.stop("csr_aggregate_bwd/%s/%s" % (_AGGR_NAMES[aggr_id], _edge_name(edge_mode, rank)), t0,
-                       algorithmic_bytes(N, g.num_edges, d, aggr_id, edge_mode, backward=True, learn_t=learn_t,
-                                         s=x.element_size(), rank=max(rank, 1)))
-        geu = guv[:ctx.uv_rows].to(ctx.uv_dtype) if guv is not None else None
-        gev = guv[rank].to(ctx.uv_dtype) if guv is not None else None
+            gx, ge, guv = _gather_backward(ctx, saved, route, go_k, gx, shifted)
+        geu, gev = (guv[:ctx.uv_rows].to(ctx.uv_dtype), guv[rank].to(ctx.uv_dtype)) if guv is not None else (None, None)
         return gx, geu, gev, ge, grad_t, grad_p, None, None, None, None, None, None, None, None, None, None
+
+
+# Where the gradient of the edge term goes in _GenAggregate.backward, in the order the routes are tried:
+ROUTE_TABLE_FIXED = "table_fixed"          # TABLE_DIRECT: max over a table, summed by fixed-point atomics inside the kernel
+ROUTE_WINNERS = "winners"                  # SPARSE_MAX: max without / over a table, from compact winner lists (no row gather)
+ROUTE_TABLE_STREAMED = "table_streamed"    # TABLE_DEST, a few table rows: one streaming pass over grad_out and argmax
+ROUTE_TABLE_BY_TYPE = "table_by_type"      # TABLE_DEST, many table rows: a pass per table row BEHIND the backward kernel
+ROUTE_EDGE_BUFFER = "edge_buffer"          # an [E, d] per-edge gradient, shared through the term's sink if it has one
+ROUTE_SCRATCH = "scratch"                  # a table without gradient (no sink): the kernel still wants [E, d] row space
+ROUTE_NONE = "none"                        # no edge term, or a factored one (its gradient is the [r + 1, d] `guv`)
+
+
+def _edge_grad_route(ctx, x, argmax, go_k):
+    aggr_id, edge_mode = ctx.cfg[0], ctx.cfg[1]
+    g, sink, te = ctx.graph, ctx.grad_sink, ctx.table_edge
+    N, d = x.shape
+    # the three facts the max-aggregator routes are made of
+    max_f32 = aggr_id == AGGR_MAX and x.dtype == torch.float32 and argmax is not None
+    aligned = max_f32 and go_k.data_ptr() % 16 == 0 and argmax.data_ptr() % 16 == 0
+    table_wants_grad = te is not None and sink is not None and edge_mode == EDGE_FULL
+    # max over a table edge term: only the winning edge of (i, c) has a gradient -- it goes straight to the table's
+    # fixed-point accumulator inside the kernel (no [E, d] gradient written, re-read and reduced)
+    if TABLE_DIRECT and table_wants_grad and max_f32 and d % 4 == 0 and ctx.post_ln is None:
+        return ROUTE_TABLE_FIXED
+    # every (node, channel) has ONE winning edge: its cotangent goes to that edge's source -- and to the table row
+    # the edge reads -- through compact per-edge runs of (value, channel) pairs instead of whole gathered rows
+    if (SPARSE_MAX and aligned and ctx.post_ln is None and g.num_edges > 0
+            and (edge_mode == EDGE_NONE or (edge_mode == EDGE_FULL and te is not None and TABLE_DEST))
+            and int(_lib.lib.mlgnn_max_sparse_records(N, d, g.num_edges)) > 0 and g.known_short_rows()):
+        return ROUTE_WINNERS
+    if TABLE_DEST and table_wants_grad and aligned and d % 4 == 0:
+        streamed = bool(_lib.lib.mlgnn_max_table_grad_supported(N, d, te.table_rows))
+        return ROUTE_TABLE_STREAMED if streamed else ROUTE_TABLE_BY_TYPE
+    if edge_mode == EDGE_FULL:
+        return ROUTE_EDGE_BUFFER if (te is None or sink is not None) else ROUTE_SCRATCH
+    return ROUTE_NONE
+
+
+def _streamed_table_grad(go_k, argmax, g, te, sink):
+    """The table's gradient from the destination side, a few table rows (the caller checks ``mlgnn_max_table_grad_supported``):
+    one streaming pass over grad_out and argmax, per-workgroup partial tables in LDS."""
+    N, d = go_k.shape
+    T = te.table_rows
+    total, accumulate = sink.table_total(T, d, go_k.device)
+    rows_dst = te.rows_for(g)[0]
+    mt_n = int(_lib.lib.mlgnn_max_table_grad_workspace_floats(N, d, T))
+    mt_ws = torch.empty(mt_n, dtype=torch.float32, device=go_k.device)
+    rc = _lib.lib.mlgnn_max_table_grad(go_k.data_ptr(), argmax.data_ptr(), rows_dst.data_ptr(), total.data_ptr(),
+                                       mt_ws.data_ptr(), mt_n, N, d, T, accumulate, _stream())
+    _lib.check(rc, "mlgnn_max_table_grad")
+    TABLE_DEST_STATS["streamed"] += 1
+
+
+def _max_winners_backward(go_k, argmax, g, gx, add_root, te, sink):
+    """ROUTE_WINNERS: ``gx`` -- and the table's gradient, if the table wants one -- from compact winner lists
+    (csrc/max_sparse.hip) instead of the row-gather kernel."""
+    (N, d), dev = go_k.shape, go_k.device
+    recs = torch.empty((int(_lib.lib.mlgnn_max_sparse_records(N, d, g.num_edges)), 2), dtype=torch.int32, device=dev)
+    meta = torch.empty((g.num_edges, 2), dtype=torch.int32, device=dev)
+    rc = _lib.lib.mlgnn_max_winners(go_k.data_ptr(), argmax.data_ptr(), g.rowptr.data_ptr(), recs.data_ptr(),
+                                    meta.data_ptr(), N, d, _stream())
+    _lib.check(rc, "mlgnn_max_winners")
+    rc = _lib.lib.mlgnn_max_sparse_bwd(recs.data_ptr(), meta.data_ptr(), g.rowptr_t.data_ptr(), g.pos_t.data_ptr(),
+                                       go_k.data_ptr() if add_root else None, gx.data_ptr(), N, d, _stream())
+    _lib.check(rc, "mlgnn_max_sparse_bwd")
+    SPARSE_MAX_STATS["calls"] += 1
+    if te is None or sink is None:
+        return
+    T = te.table_rows
+    if bool(_lib.lib.mlgnn_max_table_grad_supported(N, d, T)):
+        _streamed_table_grad(go_k, argmax, g, te, sink)
+    else:
+        total, accumulate = sink.table_total(T, d, dev)
+        pos_s, _, rp_s, _ = te.winners_by_type(g)
+        rc = _lib.lib.mlgnn_max_sparse_table_grad(recs.data_ptr(), meta.data_ptr(), pos_s.data_ptr(), rp_s.data_ptr(),
+                                                  total.data_ptr(), N, d, T, accumulate, _stream())
+        _lib.check(rc, "mlgnn_max_sparse_table_grad")
+        SPARSE_MAX_STATS["table"] += 1
+    TABLE_DEST_STATS["calls"] += 1
+
+
+def _fixed_point_begin(go_k, te, sink):
+    """ROUTE_TABLE_FIXED, before the kernel: the fixed-point accumulator (kept on the sink), scaled for this cotangent."""
+    N, d = go_k.shape
+    nbytes = int(_lib.lib.mlgnn_table_grad_bytes(te.table_rows, d))
+    if sink.fix is None or sink.fix.numel() != nbytes:
+        sink.fix = torch.zeros(nbytes, dtype=torch.uint8, device=go_k.device)
+    _lib.check(_lib.lib.mlgnn_table_grad_begin(go_k.data_ptr(), N, d, sink.fix.data_ptr(), _stream()), "mlgnn_table_grad_begin")
+    return sink.fix
+
+
+def _by_type_table_grad(go_k, argmax, g, te, sink, ws, rank):
+    """ROUTE_TABLE_BY_TYPE, behind the backward kernel (it reads that call's winner slots in ``ws``): one row per KEGG
+    membership (tens of thousands) -- a wavefront per table row gathers its edges' winners."""
+    N, d = go_k.shape
+    total, accumulate = sink.table_total(te.table_rows, d, go_k.device)
+    pos_s, dst_s, rp_s, rel_s = te.winners_by_type(g)
+    off = int(_lib.lib.mlgnn_csr_aggregate_bwd_slots_offset_floats(N, d, rank))
+    slots = ws.data_ptr() + 4 * off if (ws is not None and off >= 0 and TABLE_SLOTS) else None
+    rc = _lib.lib.mlgnn_max_table_grad_by_type(go_k.data_ptr(), argmax.data_ptr(), dst_s.data_ptr(), pos_s.data_ptr(),
+                                               rel_s.data_ptr(), rp_s.data_ptr(), slots, total.data_ptr(), N, d,
+                                               te.table_rows, accumulate, _stream())
+    _lib.check(rc, "mlgnn_max_table_grad_by_type")
+    TABLE_DEST_STATS["by_type"] += 1
+
+
+def _ln_fold_backward(tag, x, gx, launch):
+    """The backward kernel with the LayerNorm backward of ``x = y = relu?(LayerNorm(h))`` in its row epilogue: d loss / d y
+    goes through it as each row is finished; ``gx`` is then d loss / d h (+ the identity-branch gradient the block's MLP
+    left in ``tag.extra``) and is left in ``tag.folded`` -- nothing reaches y through autograd: see PostLN."""
+    tag.claim()
+    N, d = x.shape
+    f32 = dict(dtype=torch.float32, device=x.device)
+    ln_n = int(_lib.lib.mlgnn_csr_aggregate_bwd_ln_workspace_floats(N, d))
+    ln_ws, ggb, row_max = torch.empty(ln_n, **f32), torch.empty((2, d), **f32), torch.empty(N, **f32)
+    extra = tag.extra if (tag.extra is not None and tag.extra.dtype == torch.float32
+                          and tag.extra.shape == x.shape and tag.extra.is_contiguous()) else None
+    gamma, beta = f32_cached(tag.gamma), f32_cached(tag.beta)
+    st = _lib.LnFoldStruct(tag.h.data_ptr(), tag.mean.data_ptr(), tag.rstd.data_ptr(), gamma.data_ptr(),
+                           beta.data_ptr(), _lib.ptr(extra), row_max.data_ptr(), ggb.data_ptr(), ln_ws.data_ptr(),
+                           ln_n, int(tag.relu))
+    launch(hub=None, ln=st)
+    tag.folded = (gx, ggb[0], ggb[1], row_max)
+    tag.extra_used = extra is not None
+    LN_FOLD_STATS["folded"] += 1
+
+
+def _gather_backward(ctx, saved, route, go_k, gx, shifted):
+    """Every route but ROUTE_WINNERS: the row-gather kernel (``mlgnn_csr_aggregate_bwd``) writes ``gx`` and puts the edge
+    term's gradient where ``route`` says.  -> ``(gx, ge, guv)`` as autograd gets them."""
+    x, out, aux, aux2, argmax, eu, ev, efull, t_dev, p_dev = saved
+    aggr_id, edge_mode, rank, t, p, eps, learn_t, learn_p, add_root = ctx.cfg
+    g, sink, te = ctx.graph, ctx.grad_sink, ctx.table_edge
+    N, d = x.shape
+    eid_t, geid_t = g.eid_t, None
+    if te is not None:                                   # read the table row, write the edge's own gradient row
+        _, eid_t, geid_t = te.rows_for(g)                # (gradient rows in by-source order: a streamed write)
+    ge, ge_accumulate = None, 0
+    if route == ROUTE_TABLE_FIXED:
+        ge, ge_accumulate, geid_t = _fixed_point_begin(go_k, te, sink), 2, eid_t
+    elif route in (ROUTE_TABLE_STREAMED, ROUTE_TABLE_BY_TYPE):
+        if route == ROUTE_TABLE_STREAMED:
+            _streamed_table_grad(go_k, argmax, g, te, sink)
+        TABLE_DEST_STATS["calls"] += 1
+        ge_accumulate, geid_t = 3, None                  # (the kernel writes nothing per edge)
+    elif route == ROUTE_EDGE_BUFFER and sink is not None and sink.buf is not None:
+        ge, ge_accumulate = sink.buf, 1                  # add this layer's share to the layers that ran before
+    elif route in (ROUTE_EDGE_BUFFER, ROUTE_SCRATCH):
+        ge = torch.empty((g.num_edges, d), dtype=efull.dtype, device=efull.device)
+        if sink is not None:
+            sink.buf = ge
+    ws_n = int(_lib.lib.mlgnn_csr_aggregate_bwd_workspace_floats(
+        N, d, _DTYPE_IDS[x.dtype], rank, AGGR_SUM if shifted is not None else aggr_id, int(learn_t)))
+    if ws_n < 0:
+        _lib.check(ws_n, "mlgnn_csr_aggregate_bwd_workspace_floats")
+    ws = torch.empty(ws_n, dtype=torch.float32, device=x.device) if ws_n > 0 else None
+    guv = torch.empty((rank + 1, d), dtype=torch.float32, device=x.device) if edge_mode == EDGE_RANK1 else None
+    timer = KERNEL_TIMER
+    t0 = timer.start() if timer is not None else None
+    hub, hub_keep = g.hub_arg("src", d)
+    launch = functools.partial(
+        _aggregate_bwd, go_k, g, gx, MSG_GEN, aggr_id, x=x, out=out, aux=aux, argmax=argmax,
+        ew_pair=ctx.ew_pair, eu=eu, ev=ev, efull=efull, eid_t=eid_t, geid_t=geid_t,
+        ge=ge, ge_accumulate=ge_accumulate, guv=guv, ws=ws, ws_n=ws_n, edge_mode=edge_mode, rank=rank, learn_t=learn_t,
+        t=t, p=p, t_dev=t_dev, p_dev=p_dev, eps=eps, add_root=add_root, shifted=shifted)
+    if ctx.post_ln is not None and hub is None and ctx.needs_input_grad[0]:
+        _ln_fold_backward(ctx.post_ln, x, gx, launch)
+        gx = None
+    else:
+        LN_FOLD_STATS["separate"] += int(ctx.post_ln is not None)
+        launch(hub=hub)
+    del hub_keep
+    if route == ROUTE_TABLE_BY_TYPE:
+        _by_type_table_grad(go_k, argmax, g, te, sink, ws, rank)
+    if route == ROUTE_TABLE_FIXED:
+        total, accumulate = sink.table_total(te.table_rows, d, x.device)
+        _lib.check(_lib.lib.mlgnn_table_grad_finish(sink.fix.data_ptr(), total.data_ptr(), te.table_rows, d, accumulate,
+                                                    _stream()), "mlgnn_table_grad_finish")
+    SHIFT_STATS["given" if shifted else "computed"] += int(aggr_id == AGGR_SOFTMAX and not learn_t)
+    if sink is not None or te is not None:
+        ge = None                                        # reported once, by the fan-out node of the shared term
+    if timer is not None:
+        timer.stop("csr_aggregate_bwd/%s/%s" % (_AGGR_NAMES[aggr_id], _edge_name(edge_mode, rank)), t0,
+                   algorithmic_bytes(N, g.num_edges, d, aggr_id, edge_mode, backward=True, learn_t=learn_t,
+                                     s=x.element_size(), rank=max(rank, 1)))
+    return gx, ge, guv
 
 
 def gen_aggregate(x, graph, edge=None, aggr="softmax", t=1.0, p=1.0, eps=1e-7, learn_t=False, learn_p=False,
@@ -882,13 +819,8 @@ class _WeightedAggregate(torch.autograd.Function):
         out = torch.empty_like(x)
         msg = MSG_WEIGHTED if ew_pair is not None else MSG_IDENTITY
         aggr_id = AGGR_MEAN if mean else AGGR_SUM
-        ew = ew_pair[0] if ew_pair is not None else None
         hub, hub_keep = graph.hub_arg("dst", d)
-        rc = _lib.lib.mlgnn_csr_aggregate_fwd(
-            x.data_ptr(), graph.rowptr.data_ptr(), graph.col.data_ptr(), _lib.ptr(ew), None, None, None, None,
-            out.data_ptr(), None, None, None, None, N, d, _DTYPE_IDS[x.dtype], msg, EDGE_NONE, 0, aggr_id, 1.0, 1.0, None, None,
-            0.0, 0, hub, _stream())
-        _lib.check(rc, "mlgnn_csr_aggregate_fwd")
+        _aggregate_fwd(x, graph, out, msg, aggr_id, hub, ew_pair=ew_pair)
         ctx.graph, ctx.ew_pair, ctx.cfg = graph, ew_pair, (msg, aggr_id, N, d)
         return out
 
@@ -898,14 +830,8 @@ class _WeightedAggregate(torch.autograd.Function):
         msg, aggr_id, N, d = ctx.cfg
         go = _dev_act(go, "grad_out")
         gx = torch.empty_like(go)
-        ew_t = ctx.ew_pair[1] if ctx.ew_pair is not None else None
         hub, hub_keep = g.hub_arg("src", d)
-        rc = _lib.lib.mlgnn_csr_aggregate_bwd(
-            go.data_ptr(), None, None, None, None, g.rowptr_t.data_ptr(), g.col_t.data_ptr(), g.pos_t.data_ptr(),
-            g.rowptr.data_ptr(), _lib.ptr(ew_t), None, None, None, None, None, gx.data_ptr(), None, None, None, 0,
-            N, d, _DTYPE_IDS[go.dtype], msg, EDGE_NONE, 0, aggr_id, 0, 1.0, 1.0, None, None, 0.0, 0, 0, hub, None, None,
-            _stream())
-        _lib.check(rc, "mlgnn_csr_aggregate_bwd")
+        _aggregate_bwd(go, g, gx, msg, aggr_id, hub=hub, ew_pair=ctx.ew_pair)
         return gx, None, None, None
 
 

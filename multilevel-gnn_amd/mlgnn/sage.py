@@ -19,7 +19,8 @@ import torch
 
 from . import _lib
 from .dense import WGRAD_MIN_ROWS, _aligned, _wgrad, tall_matmul_nt, tall_matmul_supported
-from .ops import AGGR_MEAN, AGGR_SUM, EDGE_NONE, MSG_IDENTITY, MSG_WEIGHTED, _DTYPE_IDS, _stream, tag_row_max
+from .ops import AGGR_MEAN, AGGR_SUM, MSG_IDENTITY, MSG_WEIGHTED, _aggregate_bwd, _aggregate_fwd, _stream
+from .tags import tag_row_max
 
 STATS = {"fused": 0, "fallback": 0}
 
@@ -50,13 +51,8 @@ class _SageLayer(torch.autograd.Function):
         agg = torch.empty_like(x)
         msg = MSG_WEIGHTED if ew_pair is not None else MSG_IDENTITY
         aggr = AGGR_SUM if folded_mean else AGGR_MEAN
-        ew = ew_pair[0] if ew_pair is not None else None
         hub, hub_keep = graph.hub_arg("dst", cin)
-        rc = _lib.lib.mlgnn_csr_aggregate_fwd(
-            x.data_ptr(), graph.rowptr.data_ptr(), graph.col.data_ptr(), _lib.ptr(ew), None, None, None, None,
-            agg.data_ptr(), None, None, None, None, N, cin, _DTYPE_IDS[x.dtype], msg, EDGE_NONE, 0, aggr, 1.0, 1.0,
-            None, None, 0.0, 0, hub, _stream())
-        _lib.check(rc, "mlgnn_csr_aggregate_fwd")
+        _aggregate_fwd(x, graph, agg, msg, aggr, hub, ew_pair=ew_pair)
         # lin_r folded into the update's weight: [W_x (- W_c) | W_c], W_c = W_a W_r  (one small launch)
         w_nn_c, w_r_c = w_nn.contiguous(), w_r.contiguous()
         f32 = dict(dtype=torch.float32, device=dev)
@@ -99,14 +95,8 @@ class _SageLayer(torch.autograd.Function):
             # d agg = dz W_c, through the transposed aggregation, then dx = dz W_x' + that (the sum in the GEMM's epilogue)
             dagg = tall_matmul_nt(dz, w_c, row_max=dz_max, bt_transposed=True)
             gagg = torch.empty_like(dagg)
-            ew_t = ctx.ew_pair[1] if ctx.ew_pair is not None else None
             hub, hub_keep = g.hub_arg("src", cin)
-            rc = _lib.lib.mlgnn_csr_aggregate_bwd(
-                dagg.data_ptr(), None, None, None, None, g.rowptr_t.data_ptr(), g.col_t.data_ptr(), g.pos_t.data_ptr(),
-                g.rowptr.data_ptr(), _lib.ptr(ew_t), None, None, None, None, None, gagg.data_ptr(), None, None, None, 0,
-                N, cin, _DTYPE_IDS[dagg.dtype], msg, EDGE_NONE, 0, aggr, 0, 1.0, 1.0, None, None, 0.0, 0, 0, hub,
-                None, None, _stream())
-            _lib.check(rc, "mlgnn_csr_aggregate_bwd")
+            _aggregate_bwd(dagg, g, gagg, msg, aggr, hub=hub, ew_pair=ctx.ew_pair)
             gx = tall_matmul_nt(dz, w_x1, residual=gagg, row_max=dz_max, bt_transposed=True)
         # dW of the folded weight: dz^T x and dz^T agg (split-row kernels; a_max bounds both operands' rows)
         gw_x1, gb = _wgrad(dz, x, go_max=dz_max, x_max=a_max)
