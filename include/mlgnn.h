@@ -708,6 +708,7 @@ int mlgnn_diffpool_large_bwd(const void* z, const void* adj, const void* s_logit
  * tensors fp32: z [B,N,C], s_logits / s_out [B,N,K] (s_out = softmax), adj [B,N,N] (adj_batched) or ONE [N,N],
  * x_out [B,K,C], adj_out [B,K,K], scal_out [2] = {link, entropy}, stats float[3] as above.  A batch runs as grouped
  * launches with the reference's batch semantics for the scalars (see above).  Shapes: mlgnn_diffpool_large_supported.
+ * (csrc/diffpool_large_f32.hip)
  * workspace: B consecutive blocks of mlgnn_diffpool_large_f32_workspace_bytes(N, K, C) bytes (256-byte aligned); the first
  * mlgnn_diffpool_large_f32_saved_bytes(N, K, C) bytes of every block must reach the backward unchanged (`saved` = the
  * same pointer: the backward finds block b at saved + b * workspace_bytes(N, K, C)).
@@ -733,6 +734,7 @@ int mlgnn_diffpool_large_f32_bwd(const float* adj, const float* s_logits, const 
  * the fp32 weight image does not fit LDS) -- torch_nn.py:54-75 at BASELINE configs[4]'s sizes in fp32.  Every product
  * as three bf16 terms on the matrix cores (see mlgnn_diffpool_large_f32_fwd), fp32 accumulation; the library's fp32
  * GEMMs for these shapes run at ~40 TFLOP/s.  R, J multiples of 128 (mlgnn_linear_f32x3_supported).
+ * (csrc/linear_f32x3.hip)
  *   fwd:  y [Npad, J] = x [N,R] w[J,R]^T + bias [J] (or NULL); Npad = mlgnn_linear_f32x3_padded_rows(N): the first N
  *         rows are the result (the rest is scratch)
  *   bwd:  grad_x [Npad, R] (or NULL) = grad_out [N,J] w;  grad_w [J,R] = grad_out^T x  (one product over the row index,

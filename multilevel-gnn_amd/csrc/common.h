@@ -74,6 +74,9 @@ __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __builtin_bit_
 __device__ __forceinline__ uint16_t f32_to_bf16(float f) {         // round to nearest even (v_cvt_pk_bf16_f32)
   return __builtin_bit_cast(uint16_t, (__bf16)f);
 }
+__device__ __forceinline__ uint32_t pack2_bf16(float a, float b) {
+  return (uint32_t)f32_to_bf16(a) | ((uint32_t)f32_to_bf16(b) << 16);
+}
 
 template <typename T, int VEC>
 __device__ __forceinline__ void load_t(float (&r)[VEC], const T* __restrict__ p) {
@@ -168,6 +171,17 @@ __device__ __forceinline__ float half_max(float v) {
   v = fmaxf(v, dpp_row_ror<2>(v)); v = fmaxf(v, dpp_row_ror<1>(v));
   return fmaxf(v, __shfl_xor(v, 16));
 }
+// All-reduce over the whole wavefront
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
 
 // relu that carries a NaN through like torch's (fmaxf / v_max_f32 return the non-NaN operand)
 __device__ __forceinline__ float relu_keep_nan(float y) { return (y < 0.f) ? 0.f : y; }
@@ -244,6 +258,9 @@ inline int grid_for_rows(int64_t n_rows) {
   return (int)blocks;
 }
 
+// workspace carving: every buffer starts on a 256-byte boundary
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
 // lanes-per-row (power of two) for d channels at VEC floats per lane, capped at one wave
 inline int lanes_per_row_log2(int64_t d, int vec) {
   int64_t need = (d + vec - 1) / vec;
@@ -252,7 +269,6 @@ inline int lanes_per_row_log2(int64_t d, int vec) {
   return l;
 }
 
-// ws[nblk][cols] -> out[cols] in a fixed summation order (defined in aggregate_bwd.hip)
 // Fixed-point accumulator of a table gradient (csrc/embedding.hip, the max-aggregation backward with a table edge
 // term): a 256-byte header {bits of max |cotangent|, non-finite flag, headroom bits} followed by int64 [T, d].
 // Integer atomic adds commute, so the sums are independent of the order the edges arrive in (bitwise reproducible).
@@ -268,6 +284,7 @@ __device__ __forceinline__ float fix_scale_of(const uint32_t* hdr) {
   return __builtin_bit_cast(float, (uint32_t)fix_scale_exponent(hdr) << 23);
 }
 
+// ws[nblk][cols] -> out[cols] in a fixed summation order (defined in aggregate_bwd.hip)
 // accumulate: out += the sum (a later row slab of one reduction: slab sums are added in slab order, still bitwise reproducible)
 void launch_reduce_partials(const float* ws, float* out, int nblk, int cols, hipStream_t stream, bool accumulate = false);
 

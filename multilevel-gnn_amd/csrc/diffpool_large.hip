@@ -22,14 +22,12 @@
 //         dS = [Z | T | T2 | S~] [dX' | dA' - cI | dA'^T - cI | 2c G]^T,      T2 = A^T S~
 //     then the softmax backward (with the entropy term) as one streaming pass; dZ = S~ dX'.
 // No atomics; every reduction is a fixed-order sum of per-workgroup partials: bitwise reproducible.
+// The split-K reduce is csrc/gemm_chain.hip; the fp32 three-term form of this chain is csrc/diffpool_large_f32.hip.
 #include "common.h"
-#include "gemm_nt.h"
-#include "mlgnn.h"
+#include "gemm_chain.h"
 
 namespace mlgnn {
 
-constexpr float kDplEps = 1e-15f;
-constexpr int kDplPartials = 1024;       // workgroups of the split-K reduce (= partial sums of ||S^T S||^2)
 constexpr int kDplSqBlocks = 256;        // workgroups (= partial sums) of ||A||_F^2
 constexpr int kProRows = 32;             // rows of the logits one softmax workgroup owns
 constexpr int kProCols = 128;            // columns per transposed write-out
@@ -42,19 +40,6 @@ __device__ __forceinline__ float dpl_load(const T* p, size_t i) {
 }
 __device__ __forceinline__ float dpl_load_dt(const void* p, size_t i, int f32) {
   return f32 ? reinterpret_cast<const float*>(p)[i] : bf16_to_f32(reinterpret_cast<const uint16_t*>(p)[i]);
-}
-__device__ __forceinline__ uint32_t dpl_pack2(float a, float b) {
-  return (uint32_t)f32_to_bf16(a) | ((uint32_t)f32_to_bf16(b) << 16);
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // 64 x 64 bf16 tile transpose through LDS: in [.., ld_in] -> out [.., ld_out]; 256 threads; tile = [64][66]
@@ -205,7 +190,7 @@ __global__ __launch_bounds__(kProThreads) void dpl_prologue_kernel(const DplProA
       for (int j = 0; j < kProRowsPerWave; ++j) {
         uint32_t w[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) w[i] = dpl_pack2(v[j][q][2 * i], v[j][q][2 * i + 1]);
+        for (int i = 0; i < 4; ++i) w[i] = pack2_bf16(v[j][q][2 * i], v[j][q][2 * i + 1]);
         const uint4 pk = make_uint4(w[0], w[1], w[2], w[3]);
         *reinterpret_cast<uint4*>(p.S + (size_t)(row0 + j) * K + q * kProWide + lane * 8) = pk;
         *reinterpret_cast<uint4*>(lds_all + (wave * kProRowsPerWave + j) * kProWidePitch + lane * 8) = pk;
@@ -269,7 +254,7 @@ __global__ __launch_bounds__(kProThreads) void dpl_prologue_kernel(const DplProA
       const float s0 = __expf(dpl_load(logits, at) - mx[j]) * inv[j];
       const float s1 = __expf(dpl_load(logits, at + 1) - mx[j]) * inv[j];
       ent -= s0 * __logf(s0 + kDplEps) + s1 * __logf(s1 + kDplEps);
-      const uint32_t w = dpl_pack2(s0, s1);
+      const uint32_t w = pack2_bf16(s0, s1);
       *reinterpret_cast<uint32_t*>(p.S + at) = w;
       *reinterpret_cast<uint32_t*>(img + (wave * kProRowsPerWave + j) * kProPitch + lane * 2) = w;
     }
@@ -358,18 +343,6 @@ __global__ __launch_bounds__(256) void dpl_softmax_bwd_kernel(const T* __restric
   }
 }
 
-// ---- forward scalars: stats = {link, ent, ||A - S S^T||_F} from the partial sums, fixed order ---------------------
-struct DplFinalArgs {
-  const float* a2; int n_a2;          // ||A||_F^2 partials
-  const float* dot; int n_dot;        // <S, A S> partials
-  const float* g2; int n_g2;          // ||S^T S||_F^2 partials
-  const float* ent; int n_ent;        // entropy partials
-  float* stats; void* scal_out; int scal_f32; float inv_numel; float inv_rows;
-  // a batch: the partial sums of graph b sit ws_floats further on (a2: only the first adj_batch graphs have their own);
-  // the reference takes ONE Frobenius norm over the whole batch and the mean entropy over all its nodes
-  int batch, adj_batch; int64_t ws_floats;
-};
-
 __device__ float dpl_block_sum(const float* p, int n, float* sh) {
   float acc = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) acc += p[i];
@@ -408,64 +381,6 @@ __device__ void dpl_final(const DplFinalArgs& p, float* sh) {
 __global__ __launch_bounds__(256) void dpl_final_kernel(const DplFinalArgs p) {
   __shared__ float sh[4];
   dpl_final(p, sh);
-}
-
-// ---- split-K reduce of [A' | G | X'] -------------------------------------------------------------------------------
-// out[i] = sum_z slab[z][i]  in a fixed order; columns [0, n_a) of every row go to `ca` (bf16 or fp32, leading
-// dimension lda), columns [n_a, n_b) to `cb` (bf16, leading dimension ldb) with their squares summed per workgroup
-// into sq_partial (||.||_F^2 of that column range), columns [n_b, N) to `cc`.
-// (Measured and not kept: the forward scalars computed by the workgroup that finishes last, found through a completion
-// counter.  The device-scope release in front of the counter writes back the XCD's whole L2 on this part -- 1024
-// workgroups doing that took the reduce from 6 to 34 us; the separate one-workgroup launch costs 5.)
-struct SlabReduceArgs {
-  const float* slab; int splits; int M, N, n_a, n_b;
-  void* ca; int64_t lda; int ca_f32;
-  uint16_t* cb; int64_t ldb; float* sq_partial;
-  void* cc; int64_t ldc; int cc_f32;
-  int cb_f32;                          // the middle column range is kept in fp32 (the three-term fp32 chain)
-  int64_t s_ca, s_cc, ws_stride;       // grouped launch: element strides of ca / cc, bytes between per-graph workspaces
-};
-
-__global__ __launch_bounds__(256) void slab_reduce_kernel(const SlabReduceArgs p_in) {
-  SlabReduceArgs p = p_in;
-  {
-    const int64_t bz = blockIdx.y;
-    p.slab += bz * (p.ws_stride / 4);
-    p.cb = reinterpret_cast<uint16_t*>(reinterpret_cast<unsigned char*>(p.cb) + bz * p.ws_stride);
-    p.sq_partial += bz * (p.ws_stride / 4);
-    p.ca = p.ca_f32 ? (void*)(static_cast<float*>(p.ca) + bz * p.s_ca) : (void*)(static_cast<uint16_t*>(p.ca) + bz * p.s_ca);
-    p.cc = p.cc_f32 ? (void*)(static_cast<float*>(p.cc) + bz * p.s_cc) : (void*)(static_cast<uint16_t*>(p.cc) + bz * p.s_cc);
-  }
-  __shared__ float wsum[4];
-  const int per_row = p.N / 4;
-  const int64_t total = (int64_t)p.M * per_row;
-  float sq = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int row = (int)(i / per_row), col = (int)(i % per_row) * 4;
-    float4 s = reinterpret_cast<const float4*>(p.slab)[i];
-    for (int z = 1; z < p.splits; ++z) {
-      const float4 v = reinterpret_cast<const float4*>(p.slab + (size_t)z * p.M * p.N)[i];
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    }
-    if (col < p.n_a || col >= p.n_b) {
-      const bool first = col < p.n_a;
-      void* dst = first ? p.ca : p.cc;
-      const size_t at = first ? (size_t)row * p.lda + col : (size_t)row * p.ldc + (col - p.n_b);
-      if (first ? p.ca_f32 : p.cc_f32) {
-        *reinterpret_cast<float4*>(reinterpret_cast<float*>(dst) + at) = s;
-      } else {
-        *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(dst) + at) = make_uint2(dpl_pack2(s.x, s.y), dpl_pack2(s.z, s.w));
-      }
-    } else {
-      sq += s.x * s.x + s.y * s.y + s.z * s.z + s.w * s.w;
-      if (p.cb_f32) *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.cb) + (size_t)row * p.ldb + (col - p.n_a)) = s;
-      else *reinterpret_cast<uint2*>(p.cb + (size_t)row * p.ldb + (col - p.n_a)) = make_uint2(dpl_pack2(s.x, s.y), dpl_pack2(s.z, s.w));
-    }
-  }
-  sq = wave_sum(sq);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = sq;
-  __syncthreads();
-  if (threadIdx.x == 0) p.sq_partial[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
 }
 
 // ---- backward operand preparation: ONE launch, workgroups by role --------------------------------------------------
@@ -573,16 +488,6 @@ __global__ __launch_bounds__(256) void dpl_prep_kernel(const DplPrepArgs p_in) {
                      threadIdx.x);
 }
 
-inline size_t dpl_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// split factor that brings a product with `tiles` output tiles to about one workgroup per CU
-inline int dpl_splits(int tiles, int ktiles) {
-  int s = 256 / tiles;
-  if (s < 1) s = 1;
-  if (s > ktiles) s = ktiles;
-  return s;
-}
-
 struct DplLayout {       // byte offsets into the forward workspace (kept for the backward) and scratch
   size_t stack, T, G, scratch, total;      // stack [2K + C, N]: T^T, S~^T, Z^T;  T [N,K];  G [K,K]
   size_t slab, part_a2, part_dot, part_g2, part_ent;
@@ -592,9 +497,9 @@ struct DplLayout {       // byte offsets into the forward workspace (kept for th
 DplLayout dpl_layout(int64_t N, int64_t K, int64_t C) {
   DplLayout L;
   size_t o = 0;
-  L.stack = o; o += dpl_align((size_t)(2 * K + C) * N * 2);
-  L.T = o; o += dpl_align((size_t)N * K * 2);
-  L.G = o; o += dpl_align((size_t)K * K * 2);
+  L.stack = o; o += align256((size_t)(2 * K + C) * N * 2);
+  L.T = o; o += align256((size_t)N * K * 2);
+  L.G = o; o += align256((size_t)K * K * 2);
   L.scratch = o;
   // [A' | G | X'] = S~^T [T | S~ | Z] is ONE product over the whole stack, split along K into about 1.5 workgroups
   // per CU (measured at 4096 / 1024 / 256, 144 tiles: 2 / 3 / 4 / 6 splits 0.110 / 0.104 / 0.109 / 0.113 ms forward)
@@ -602,29 +507,36 @@ DplLayout dpl_layout(int64_t N, int64_t K, int64_t C) {
   int sp = (384 + tiles_agx / 2) / tiles_agx;
   if (sp > (int)(N / kGemmBK)) sp = (int)(N / kGemmBK);
   L.splits_ag = sp < 1 ? 1 : sp;
-  L.slab = o; o += dpl_align((size_t)L.splits_ag * K * (2 * K + C) * 4);
-  L.part_a2 = o; o += dpl_align(kDplPartials * 4);
-  L.part_dot = o; o += dpl_align((size_t)(N / kGemmTile) * (K / kGemmTile) * 4);
-  L.part_g2 = o; o += dpl_align(kDplPartials * 4);
-  L.part_ent = o; o += dpl_align(kDplPartials * 4);
+  L.slab = o; o += align256((size_t)L.splits_ag * K * (2 * K + C) * 4);
+  L.part_a2 = o; o += align256(kReducePartials * 4);
+  L.part_dot = o; o += align256((size_t)(N / kGemmTile) * (K / kGemmTile) * 4);
+  L.part_g2 = o; o += align256(kReducePartials * 4);
+  L.part_ent = o; o += align256(kReducePartials * 4);
   L.total = o;
   return L;
 }
 
-bool dpl_supported(int64_t N, int64_t K, int64_t C) {
-  return N >= kGemmTile && K >= kGemmTile && C >= kGemmTile && N % kGemmTile == 0 && K % kGemmTile == 0 &&
-         C % kGemmTile == 0 && N <= 32768 && K <= 8192 && C <= 8192;
+void dpl_final_launch(const DplFinalArgs& f, hipStream_t st) {
+  hipLaunchKernelGGL(dpl_final_kernel, dim3(1), dim3(256), 0, st, f);
+}
+
+// four rows (one per wavefront) per workgroup and pass
+template <typename T>
+static void dpl_softmax_bwd_launch(const T* logits, const float* ds, const float* coef, T* dlogits, int N, int K,
+                                   int64_t ds_stride, int batch, hipStream_t st) {
+  const int sm_blocks = (N + 3) / 4 < 1024 ? (N + 3) / 4 : 1024;
+  hipLaunchKernelGGL(dpl_softmax_bwd_kernel<T>, dim3(sm_blocks, batch), dim3(256), 0, st, logits, ds, coef, dlogits, N, K,
+                     ds_stride);
+}
+
+void dpl_softmax_bwd_f32_launch(const float* logits, const float* ds, const float* coef, float* dlogits, int N, int K,
+                                int64_t ds_stride, int batch, hipStream_t st) {
+  dpl_softmax_bwd_launch<float>(logits, ds, coef, dlogits, N, K, ds_stride, batch, st);
 }
 
 }  // namespace mlgnn
 
 using namespace mlgnn;
-
-#define DPL_CHECK(expr)       \
-  do {                        \
-    const int rc_ = (expr);   \
-    if (rc_ != 0) return rc_; \
-  } while (0)
 
 extern "C" int mlgnn_diffpool_large_supported(int64_t N, int64_t K, int64_t C) { return dpl_supported(N, K, C) ? 1 : 0; }
 
@@ -721,25 +633,25 @@ extern "C" int mlgnn_diffpool_large_fwd(const void* z, const void* adj, const vo
     r.cb = G; r.ldb = K; r.sq_partial = p_g2;
     r.cc = x_out; r.ldc = C; r.cc_f32 = out_dtype == MLGNN_DTYPE_F32;
     r.s_ca = K * K; r.s_cc = K * C; r.ws_stride = WS;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(kDplPartials, batch), dim3(256), 0, st, r);
+    slab_reduce_launch(r, batch, st);
   }
   // 4. link / entropy from the partial sums of the whole batch; numel(adj) is the ARGUMENT's element count
-  DplFinalArgs f{p_a2, kDplSqBlocks, p_dot, (int)((N / kGemmTile) * (K / kGemmTile)), p_g2, kDplPartials, p_ent, pro.nb_sm,
+  DplFinalArgs f{p_a2, kDplSqBlocks, p_dot, (int)((N / kGemmTile) * (K / kGemmTile)), p_g2, kReducePartials, p_ent, pro.nb_sm,
                  stats, scal_out, out_dtype == MLGNN_DTYPE_F32, (float)(1.0 / ((double)adj_batch * (double)N * (double)N)),
                  (float)(1.0 / ((double)B * (double)N)), batch, adj_batch, WS / 4};
-  hipLaunchKernelGGL(dpl_final_kernel, dim3(1), dim3(256), 0, st, f);
+  dpl_final_launch(f, st);
   return (int)hipGetLastError();
 }
 
 extern "C" int64_t mlgnn_diffpool_large_bwd_workspace_bytes(int64_t N, int64_t K, int64_t C, int adj_symmetric) {
   if (!dpl_supported(N, K, C)) return MLGNN_E_SHAPE;
   size_t o = 0;
-  o += dpl_align(16);                                           // coef
-  o += 3 * dpl_align((size_t)K * K * 2);                        // b1, b2, b3
-  o += 2 * dpl_align((size_t)K * C * 2);                        // gx bf16, its transpose
-  o += dpl_align((size_t)N * K * 4);                            // dS fp32
-  if (!adj_symmetric) o += dpl_align((size_t)N * N * 2) + dpl_align((size_t)N * K * 2);   // A^T, T2
-  o += dpl_align((size_t)N * K * 2);                            // P = S~ (dA' - cI) of the adjacency gradient
+  o += align256(16);                                           // coef
+  o += 3 * align256((size_t)K * K * 2);                        // b1, b2, b3
+  o += 2 * align256((size_t)K * C * 2);                        // gx bf16, its transpose
+  o += align256((size_t)N * K * 4);                            // dS fp32
+  if (!adj_symmetric) o += align256((size_t)N * N * 2) + align256((size_t)N * K * 2);   // A^T, T2
+  o += align256((size_t)N * K * 2);                            // P = S~ (dA' - cI) of the adjacency gradient
   return (int64_t)o;
 }
 
@@ -778,7 +690,7 @@ extern "C" int mlgnn_diffpool_large_bwd(const void* z, const void* adj, const vo
   const int n = (int)N, k = (int)K, c = (int)C;
   unsigned char* ws = (unsigned char*)workspace;
   size_t o = 0;
-  auto take = [&](size_t bytes) { unsigned char* p = ws + o; o += dpl_align(bytes); return p; };
+  auto take = [&](size_t bytes) { unsigned char* p = ws + o; o += align256(bytes); return p; };
   float* coef = (float*)take(16);                     // (the first graph's block; one pair of coefficients for the batch)
   uint16_t* b1 = (uint16_t*)take((size_t)K * K * 2);
   uint16_t* b2 = (uint16_t*)take((size_t)K * K * 2);
@@ -831,13 +743,10 @@ extern "C" int mlgnn_diffpool_large_bwd(const void* z, const void* adj, const vo
     d.batch = batch; d.s_c = W / 4;
     DPL_CHECK(gemm_nt_launch(d, st));
   }
-  const int sm_blocks = (int)((N + 3) / 4 < 1024 ? (N + 3) / 4 : 1024);
   if (logits_dtype == MLGNN_DTYPE_F32)
-    hipLaunchKernelGGL(dpl_softmax_bwd_kernel<float>, dim3(sm_blocks, batch), dim3(256), 0, st, (const float*)s_logits, dS, coef,
-                       (float*)grad_logits, n, k, W / 4);
+    dpl_softmax_bwd_launch(static_cast<const float*>(s_logits), dS, coef, static_cast<float*>(grad_logits), n, k, W / 4, batch, st);
   else
-    hipLaunchKernelGGL(dpl_softmax_bwd_kernel<bf16_t>, dim3(sm_blocks, batch), dim3(256), 0, st, (const bf16_t*)s_logits, dS,
-                       coef, (bf16_t*)grad_logits, n, k, W / 4);
+    dpl_softmax_bwd_launch(static_cast<const bf16_t*>(s_logits), dS, coef, static_cast<bf16_t*>(grad_logits), n, k, W / 4, batch, st);
   // dZ = S~ gx, written in the dtype of z (= the dtype of the logits).  One workgroup per output tile: at
   // 4096 x 256 x 1024 that is 64 workgroups for 16 K-steps -- a split along K with its slabs and reduce launch
   // (round 2) took longer than the quarter-filled chip does.
@@ -871,703 +780,5 @@ extern "C" int mlgnn_diffpool_large_bwd(const void* z, const void* adj, const vo
     e.batch = batch; e.s_c = N * N; e.s_aux = s_adj;
     DPL_CHECK(gemm_nt_launch(e, st));
   }
-  return (int)hipGetLastError();
-}
-
-// =====================================================================================================================
-// fp32 inputs: the same product chain with every product as THREE bf16 terms on the matrix cores
-//     x y^T ~= x_hi y_hi^T + x_hi y_lo^T + x_lo y_hi^T,     x = x_hi + x_lo up to 2^-17 |x|  (the dropped lo x lo term is
-// 2^-18 relative), fp32 accumulation -- fp32-level accuracy (tests: 1e-4 of the fp64 oracle) at 3x the matrix work of
-// the bf16 chain, still far ahead of fp32 matrix instructions (1/16 of the bf16 rate).  One entry point each way
-// (mlgnn_diffpool_large_f32_fwd / _bwd), a batch as grouped launches; the three terms are three segments of ONE
-// gemm_nt launch (the contraction range concatenated).  Around the products: a softmax pass (fp32 S + entropy), a
-// multi-job "split" launch (fp32 matrix -> hi / lo bf16, row-major and / or transposed through LDS, optionally with the
-// partial sums of <src, other>), the split-K reduce and the scalar kernel of the bf16 chain.
-// Reference: the same call, models/diff_pooling.py:59-65 on fp32 tensors.
-namespace mlgnn {
-
-// S = softmax(logits) in fp32 (the expression the backward recomputes: __expf(v - max) / sum), entropy partials.
-// One wavefront per row, rows grid-strided; ent_partial[block] = sum over the block's rows of -sum_k S log(S + eps).
-__global__ __launch_bounds__(256) void dpl32_softmax_kernel(const float* __restrict__ logits, float* __restrict__ S,
-                                                            float* __restrict__ ent_partial, int N, int K, int64_t ws_floats) {
-  __shared__ float wsum[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  logits += (size_t)blockIdx.y * N * K;
-  S += (size_t)blockIdx.y * N * K;
-  ent_partial += (size_t)blockIdx.y * ws_floats;
-  float ent = 0.f;
-  for (int row = blockIdx.x * 4 + wave; row < N; row += gridDim.x * 4) {
-    const float* lr = logits + (size_t)row * K;
-    float mx = -3.0e38f;
-    for (int k = lane * 4; k < K; k += 256) {
-      float v[4];
-      load_vec<4>(v, lr + k);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) mx = fmaxf(mx, v[i]);
-    }
-    mx = wave_max(mx);
-    float sum = 0.f;
-    for (int k = lane * 4; k < K; k += 256) {
-      float v[4];
-      load_vec<4>(v, lr + k);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) sum += __expf(v[i] - mx);
-    }
-    sum = wave_sum(sum);
-    const float inv = 1.0f / sum;
-    for (int k = lane * 4; k < K; k += 256) {
-      float v[4], o[4];
-      load_vec<4>(v, lr + k);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        o[i] = __expf(v[i] - mx) * inv;
-        ent -= o[i] * __logf(o[i] + kDplEps);
-      }
-      store_vec<4>(S + (size_t)row * K + k, o);
-    }
-  }
-  ent = wave_sum(ent);
-  if (lane == 0) wsum[wave] = ent;
-  __syncthreads();
-  if (threadIdx.x == 0) ent_partial[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-}
-
-// One job of a split launch: src [R, Cc] fp32 (leading dimension ld; R, Cc multiples of 64) ->
-//   hi / lo   [R, Cc] bf16 (leading dimension ldo), when hi != NULL
-//   hit / lot [Cc, R] bf16 (leading dimension ldt), when hit != NULL  (64 x 64 tiles through LDS)
-//   partial[tile] = sum over the tile of src * dot (dot == src: the sum of squares), when dot != NULL
-// Batch: graph blockIdx.y < nb runs the job on pointers advanced by the s_* strides (elements of each pointer's type).
-struct SplitJob {
-  const float* src; int64_t ld; int R, Cc;
-  uint16_t *hi, *lo; int64_t ldo;
-  uint16_t *hit, *lot; int64_t ldt;
-  const float* dot; int64_t lddot; float* partial;
-  int64_t s_src, s_out, s_outt, s_dot, s_part;
-  int nb, tiles;
-  int rows_valid;            // rows >= rows_valid of src do not exist: they split to zeros (a tall operand padded to R rows)
-  float* colsum;             // non-NULL: colsum[tile row][Cc] = column sums of src over the 64 rows of each tile row
-};
-constexpr int kSplitMaxJobs = 4;
-struct SplitArgs { SplitJob job[kSplitMaxJobs]; int njobs; };
-
-__device__ __forceinline__ void split2(float v, uint16_t& h, uint16_t& l) {
-  h = f32_to_bf16(v);
-  l = f32_to_bf16(v - bf16_to_f32(h));
-}
-
-__global__ __launch_bounds__(256) void dpl32_split_kernel(const SplitArgs a) {
-  __shared__ __attribute__((aligned(16))) uint16_t th[64][66];
-  __shared__ __attribute__((aligned(16))) uint16_t tl[64][66];
-  __shared__ float wsum[4];
-  __shared__ float cs_lds[16][64];
-  int t = blockIdx.x, j = 0;
-#pragma unroll
-  for (int i = 0; i + 1 < kSplitMaxJobs; ++i)
-    if (j == i && i + 1 < a.njobs && t >= a.job[i].tiles) { t -= a.job[i].tiles; j = i + 1; }
-  SplitJob q;
-  // (a uniform select over the by-value argument: no dynamic indexing of the kernel argument segment)
-  q = a.job[0];
-  if (j == 1) q = a.job[1];
-  if (j == 2) q = a.job[2];
-  if (j == 3) q = a.job[3];
-  const int64_t bz = blockIdx.y;
-  if (bz >= q.nb) return;
-  const int tiles_c = q.Cc / 64, r0 = (t / tiles_c) * 64, c0 = (t % tiles_c) * 64;
-  const float* src = q.src + bz * q.s_src;
-  const float* dot = q.dot ? q.dot + bz * q.s_dot : nullptr;
-  const int tid = threadIdx.x;
-  float part = 0.f;
-  float cs[4] = {0.f, 0.f, 0.f, 0.f};
-  // 64 rows x 256 B: 16 lanes per row, 16 bytes each; 256 threads = 16 rows per pass
-#pragma unroll
-  for (int pass = 0; pass < 4; ++pass) {
-    const int r = pass * 16 + (tid >> 4), ch = tid & 15;
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (r0 + r < q.rows_valid) load_vec<4>(v, src + (size_t)(r0 + r) * q.ld + c0 + ch * 4);
-    if (dot) {
-      float d[4];
-      load_vec<4>(d, dot + (size_t)(r0 + r) * q.lddot + c0 + ch * 4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) part += v[i] * d[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) cs[i] += v[i];
-    uint16_t h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) split2(v[i], h[i], l[i]);
-    if (q.hi) {
-      const size_t at = (size_t)(bz * q.s_out) + (size_t)(r0 + r) * q.ldo + c0 + ch * 4;
-      *reinterpret_cast<uint2*>(q.hi + at) = make_uint2((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16));
-      *reinterpret_cast<uint2*>(q.lo + at) = make_uint2((uint32_t)l[0] | ((uint32_t)l[1] << 16), (uint32_t)l[2] | ((uint32_t)l[3] << 16));
-    }
-    if (q.hit) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        th[r][ch * 4 + i] = h[i];
-        tl[r][ch * 4 + i] = l[i];
-      }
-    }
-  }
-  if (q.hit) {
-    __syncthreads();
-    uint16_t* oh = q.hit + bz * q.s_outt;
-    uint16_t* ol = q.lot + bz * q.s_outt;
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-      const int c = pass * 32 + (tid >> 3), ch = tid & 7;                  // column of the tile = row of the transpose
-      uint32_t wh[4], wl[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        wh[i] = (uint32_t)th[ch * 8 + 2 * i][c] | ((uint32_t)th[ch * 8 + 2 * i + 1][c] << 16);
-        wl[i] = (uint32_t)tl[ch * 8 + 2 * i][c] | ((uint32_t)tl[ch * 8 + 2 * i + 1][c] << 16);
-      }
-      const size_t at = (size_t)(c0 + c) * q.ldt + r0 + ch * 8;
-      *reinterpret_cast<uint4*>(oh + at) = make_uint4(wh[0], wh[1], wh[2], wh[3]);
-      *reinterpret_cast<uint4*>(ol + at) = make_uint4(wl[0], wl[1], wl[2], wl[3]);
-    }
-  }
-  if (q.colsum) {                                     // fixed order: a thread's four rows, then the 16 row lanes in order
-#pragma unroll
-    for (int i = 0; i < 4; ++i) cs_lds[tid >> 4][(tid & 15) * 4 + i] = cs[i];
-    __syncthreads();
-    if (tid < 64) {
-      float acc = cs_lds[0][tid];
-#pragma unroll
-      for (int k = 1; k < 16; ++k) acc += cs_lds[k][tid];
-      q.colsum[(size_t)(t / tiles_c) * q.Cc + c0 + tid] = acc;
-    }
-  }
-  if (dot) {
-    part = wave_sum(part);
-    if ((tid & 63) == 0) wsum[tid >> 6] = part;
-    __syncthreads();
-    if (tid == 0) q.partial[bz * q.s_part + t] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-  }
-}
-
-inline SplitJob split_job(const float* src, int64_t ld, int R, int Cc, int nb, int64_t s_src) {
-  SplitJob q{};
-  q.src = src; q.ld = ld; q.R = R; q.Cc = Cc; q.nb = nb; q.s_src = s_src;
-  q.tiles = (R / 64) * (Cc / 64);
-  q.rows_valid = R;
-  return q;
-}
-
-inline int split_launch(const SplitArgs& a, int batch, hipStream_t st) {
-  int tiles = 0;
-  for (int i = 0; i < a.njobs; ++i) tiles += a.job[i].tiles;
-  hipLaunchKernelGGL(dpl32_split_kernel, dim3(tiles, batch), dim3(256), 0, st, a);
-  return (int)hipGetLastError();
-}
-
-// backward operands from the cotangents: coef = {c, grad_ent / rows} (as in the bf16 chain),
-// b1 = ga - cI and b3 = 2c G as fp32 [K,K] (b2 = ga^T - cI is b1's transpose: the split launch writes it)
-struct Dpl32PrepArgs {
-  const float* g_link; const float* g_ent; const float* stats; float* coef; float inv_numel, inv_rows;
-  const float* ga; const float* G; float* b1; float* b3; int K;
-  int64_t fws_floats, bws_floats;
-};
-
-__global__ __launch_bounds__(256) void dpl32_prep_kernel(const Dpl32PrepArgs p) {
-  const float c = p.g_link[0] * p.inv_numel / p.stats[2];
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-    p.coef[0] = c;
-    p.coef[1] = p.g_ent[0] * p.inv_rows;
-  }
-  const int64_t bz = blockIdx.y;
-  const float* ga = p.ga + bz * (int64_t)p.K * p.K;
-  const float* G = p.G + bz * p.fws_floats;
-  float* b1 = p.b1 + bz * p.bws_floats;
-  float* b3 = p.b3 + bz * p.bws_floats;
-  const int per_row = p.K / 4;
-  const int64_t total = (int64_t)p.K * per_row;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int row = (int)(i / per_row), col = (int)(i % per_row) * 4;
-    float v[4], g[4], o1[4], o3[4];
-    load_vec<4>(v, ga + (size_t)row * p.K + col);
-    load_vec<4>(g, G + (size_t)row * p.K + col);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      o1[k] = v[k] - (row == col + k ? c : 0.f);
-      o3[k] = 2.f * c * g[k];
-    }
-    store_vec<4>(b1 + (size_t)row * p.K + col, o1);
-    store_vec<4>(b3 + (size_t)row * p.K + col, o3);
-  }
-}
-
-struct Dpl32Layout {     // byte offsets into the per-graph forward workspace; [0, scratch) reaches the backward
-  size_t Sh, Sl, stack_h, stack_l, Th, Tl, Zh, Zl, Ah, Al, G, scratch, T, slab, part_a2, part_dot, part_g2, part_ent, total;
-  int splits, n_a2, n_dot, n_ent;
-};
-
-Dpl32Layout dpl32_layout(int64_t N, int64_t K, int64_t C) {
-  Dpl32Layout L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += dpl_align(bytes); return at; };
-  L.Sh = take((size_t)N * K * 2); L.Sl = take((size_t)N * K * 2);
-  L.stack_h = take((size_t)(2 * K + C) * N * 2); L.stack_l = take((size_t)(2 * K + C) * N * 2);
-  L.Th = take((size_t)N * K * 2); L.Tl = take((size_t)N * K * 2);
-  L.Zh = take((size_t)N * C * 2); L.Zl = take((size_t)N * C * 2);
-  L.Ah = take((size_t)N * N * 2); L.Al = take((size_t)N * N * 2);
-  L.G = take((size_t)K * K * 4);
-  L.scratch = o;
-  L.T = take((size_t)N * K * 4);
-  const int tiles_agx = (int)((K / kGemmTile) * ((2 * K + C) / kGemmTile));
-  int sp = (384 + tiles_agx / 2) / tiles_agx;
-  const int ktiles = (int)(3 * N / kGemmBK);
-  if (sp > ktiles) sp = ktiles;
-  L.splits = sp < 1 ? 1 : sp;
-  L.slab = take((size_t)L.splits * K * (2 * K + C) * 4);
-  L.n_a2 = (int)((N / 64) * (N / 64));
-  L.n_dot = (int)((N / 64) * (K / 64));
-  L.n_ent = (int)((N + 3) / 4 < 1024 ? (N + 3) / 4 : 1024);
-  L.part_a2 = take((size_t)L.n_a2 * 4);
-  L.part_dot = take((size_t)L.n_dot * 4);
-  L.part_g2 = take(kDplPartials * 4);
-  L.part_ent = take((size_t)L.n_ent * 4);
-  L.total = o;
-  return L;
-}
-
-// three-term product: (a_hi, b_hi), (a_hi, b_lo), (a_lo, b_hi) as segments i0 .. i0 + 2 of a descriptor
-inline void seg3(GemmDesc& d, int i0, const uint16_t* ah, const uint16_t* al, const uint16_t* bh, const uint16_t* bl,
-                 int64_t lda, int64_t ldb, int K, int64_t sa, int64_t sb) {
-  d.seg[i0] = GemmSeg{ah, bh, lda, ldb, K, sa, sb};
-  d.seg[i0 + 1] = GemmSeg{ah, bl, lda, ldb, K, sa, sb};
-  d.seg[i0 + 2] = GemmSeg{al, bh, lda, ldb, K, sa, sb};
-}
-
-struct Dpl32Bwd {        // byte offsets into the per-graph backward workspace
-  size_t coef, b1f, b3f, b1h, b1l, b2h, b2l, b3h, b3l, gxh, gxl, gxth, gxtl, dS, Ath, Atl, T2, T2h, T2l, P, Ph, Pl, total;
-};
-
-Dpl32Bwd dpl32_bwd_layout(int64_t N, int64_t K, int64_t C, int sym) {
-  Dpl32Bwd W{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += dpl_align(bytes); return at; };
-  W.coef = take(16);
-  W.b1f = take((size_t)K * K * 4); W.b3f = take((size_t)K * K * 4);
-  W.b1h = take((size_t)K * K * 2); W.b1l = take((size_t)K * K * 2);
-  W.b2h = take((size_t)K * K * 2); W.b2l = take((size_t)K * K * 2);
-  W.b3h = take((size_t)K * K * 2); W.b3l = take((size_t)K * K * 2);
-  W.gxh = take((size_t)K * C * 2); W.gxl = take((size_t)K * C * 2);
-  W.gxth = take((size_t)K * C * 2); W.gxtl = take((size_t)K * C * 2);
-  W.dS = take((size_t)N * K * 4);
-  if (!sym) {
-    W.Ath = take((size_t)N * N * 2); W.Atl = take((size_t)N * N * 2);
-    W.T2 = take((size_t)N * K * 4);
-    W.T2h = take((size_t)N * K * 2); W.T2l = take((size_t)N * K * 2);
-  }
-  W.P = take((size_t)N * K * 4);
-  W.Ph = take((size_t)N * K * 2); W.Pl = take((size_t)N * K * 2);
-  W.total = o;
-  return W;
-}
-
-}  // namespace mlgnn
-
-extern "C" int64_t mlgnn_diffpool_large_f32_workspace_bytes(int64_t N, int64_t K, int64_t C) {
-  if (!dpl_supported(N, K, C)) return MLGNN_E_SHAPE;
-  return (int64_t)dpl32_layout(N, K, C).total;
-}
-
-extern "C" int64_t mlgnn_diffpool_large_f32_saved_bytes(int64_t N, int64_t K, int64_t C) {
-  if (!dpl_supported(N, K, C)) return MLGNN_E_SHAPE;
-  return (int64_t)dpl32_layout(N, K, C).scratch;
-}
-
-// Forward, SEVEN launches for the whole batch: softmax, split {S, Z, A}, T = A S, split {T} (+ <S, T>),
-// [A' | G | X'] = S^T [T | S | Z] split along K, its reduce, the scalars.  All tensors fp32; s_out [B,N,K] = softmax.
-extern "C" int mlgnn_diffpool_large_f32_fwd(const float* z, const float* adj, const float* s_logits, float* s_out,
-                                            float* x_out, float* adj_out, float* scal_out, float* stats, void* workspace,
-                                            int64_t workspace_bytes, int64_t N, int64_t K, int64_t C, int64_t B,
-                                            int adj_batched, void* stream) {
-  if (!dpl_supported(N, K, C) || B < 1 || B > 65535) return MLGNN_E_SHAPE;
-  if (!z || !adj || !s_logits || !s_out || !x_out || !adj_out || !scal_out || !stats || !workspace) return MLGNN_E_NULL;
-  const Dpl32Layout L = dpl32_layout(N, K, C);
-  if (workspace_bytes < (int64_t)L.total * B) return MLGNN_E_WORKSPACE;
-  if (((uintptr_t)z | (uintptr_t)adj | (uintptr_t)s_out | (uintptr_t)workspace | (uintptr_t)s_logits | (uintptr_t)x_out |
-       (uintptr_t)adj_out) & 15) return MLGNN_E_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  unsigned char* ws = (unsigned char*)workspace;
-  const int64_t WS = (int64_t)L.total, W2 = WS / 2, W4 = WS / 4;
-  const int batch = (int)B, adj_batch = adj_batched ? batch : 1;
-  const int n = (int)N, k = (int)K, c = (int)C;
-  uint16_t *Sh = (uint16_t*)(ws + L.Sh), *Sl = (uint16_t*)(ws + L.Sl);
-  uint16_t *stack_h = (uint16_t*)(ws + L.stack_h), *stack_l = (uint16_t*)(ws + L.stack_l);
-  uint16_t *Sth = stack_h + (size_t)K * N, *Stl = stack_l + (size_t)K * N;
-  uint16_t *Th = (uint16_t*)(ws + L.Th), *Tl = (uint16_t*)(ws + L.Tl);
-  uint16_t *Zh = (uint16_t*)(ws + L.Zh), *Zl = (uint16_t*)(ws + L.Zl);
-  uint16_t *Ah = (uint16_t*)(ws + L.Ah), *Al = (uint16_t*)(ws + L.Al);
-  float* G = (float*)(ws + L.G);
-  float* T = (float*)(ws + L.T);
-  float* slab = (float*)(ws + L.slab);
-  float *p_a2 = (float*)(ws + L.part_a2), *p_dot = (float*)(ws + L.part_dot), *p_g2 = (float*)(ws + L.part_g2),
-        *p_ent = (float*)(ws + L.part_ent);
-  // 1. S = softmax(logits), entropy partials
-  hipLaunchKernelGGL(dpl32_softmax_kernel, dim3(L.n_ent, batch), dim3(256), 0, st, s_logits, s_out, p_ent, n, k, W4);
-  // 2. hi / lo terms of S (and S^T), Z (and Z^T), A (with ||A||_F^2)
-  {
-    SplitArgs a{};
-    a.njobs = 3;
-    SplitJob& s = a.job[0];
-    s = split_job(s_out, K, n, k, batch, N * K);
-    s.hi = Sh; s.lo = Sl; s.ldo = K; s.s_out = W2;
-    s.hit = Sth; s.lot = Stl; s.ldt = N; s.s_outt = W2;
-    SplitJob& zj = a.job[1];
-    zj = split_job(z, C, n, c, batch, N * C);
-    zj.hi = Zh; zj.lo = Zl; zj.ldo = C; zj.s_out = W2;
-    zj.hit = stack_h + (size_t)2 * K * N; zj.lot = stack_l + (size_t)2 * K * N; zj.ldt = N; zj.s_outt = W2;
-    SplitJob& aj = a.job[2];
-    aj = split_job(adj, N, n, n, adj_batch, N * N);
-    aj.hi = Ah; aj.lo = Al; aj.ldo = N; aj.s_out = W2;
-    aj.dot = adj; aj.lddot = N; aj.s_dot = N * N; aj.partial = p_a2; aj.s_part = W4;
-    DPL_CHECK(split_launch(a, batch, st));
-  }
-  // 3. T = A S
-  {
-    GemmDesc d{};
-    d.nseg = 3;
-    seg3(d, 0, Ah, Al, Sth, Stl, N, N, n, adj_batched ? W2 : 0, W2);
-    d.M = n; d.N = k; d.splits = 1;
-    d.c = T; d.ldc = K; d.c_f32 = 1;
-    d.batch = batch; d.s_c = W4;
-    DPL_CHECK(gemm_nt_launch(d, st));
-  }
-  // 4. hi / lo terms of T and T^T, <S, T> partials
-  {
-    SplitArgs a{};
-    a.njobs = 1;
-    SplitJob& t = a.job[0];
-    t = split_job(T, K, n, k, batch, W4);
-    t.hi = Th; t.lo = Tl; t.ldo = K; t.s_out = W2;
-    t.hit = stack_h; t.lot = stack_l; t.ldt = N; t.s_outt = W2;
-    t.dot = s_out; t.lddot = K; t.s_dot = N * K; t.partial = p_dot; t.s_part = W4;
-    DPL_CHECK(split_launch(a, batch, st));
-  }
-  // 5. [A' | G | X'] = S^T [T | S | Z]: one three-term product over the stack, split along K, one reduce
-  {
-    GemmDesc d{};
-    d.nseg = 3;
-    seg3(d, 0, Sth, Stl, stack_h, stack_l, N, N, n, W2, W2);
-    d.M = k; d.N = 2 * k + c; d.splits = L.splits; d.slab = slab;
-    d.batch = batch; d.s_slab = W4;
-    DPL_CHECK(gemm_nt_launch(d, st));
-    SlabReduceArgs r{};
-    r.slab = slab; r.splits = L.splits; r.M = k; r.N = 2 * k + c; r.n_a = k; r.n_b = 2 * k;
-    r.ca = adj_out; r.lda = K; r.ca_f32 = 1;
-    r.cb = (uint16_t*)G; r.ldb = K; r.cb_f32 = 1; r.sq_partial = p_g2;
-    r.cc = x_out; r.ldc = C; r.cc_f32 = 1;
-    r.s_ca = K * K; r.s_cc = K * C; r.ws_stride = WS;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(kDplPartials, batch), dim3(256), 0, st, r);
-  }
-  // 6. scalars of the batch
-  DplFinalArgs f{p_a2, L.n_a2, p_dot, L.n_dot, p_g2, kDplPartials, p_ent, L.n_ent,
-                 stats, scal_out, 1, (float)(1.0 / ((double)adj_batch * (double)N * (double)N)),
-                 (float)(1.0 / ((double)B * (double)N)), batch, adj_batch, W4};
-  hipLaunchKernelGGL(dpl_final_kernel, dim3(1), dim3(256), 0, st, f);
-  return (int)hipGetLastError();
-}
-
-extern "C" int64_t mlgnn_diffpool_large_f32_bwd_workspace_bytes(int64_t N, int64_t K, int64_t C, int adj_symmetric) {
-  if (!dpl_supported(N, K, C)) return MLGNN_E_SHAPE;
-  return (int64_t)dpl32_bwd_layout(N, K, C, adj_symmetric).total;
-}
-
-// Backward: operand preparation, split {b1 (-> b2), b3, gx (, A^T)}, [T2 = A^T S, split {T2}], dS as three launches of
-// four segments (twelve terms), softmax backward, dZ, [P = S (dA' - cI), split {P}, dA = P S^T + c A].
-extern "C" int mlgnn_diffpool_large_f32_bwd(const float* adj, const float* s_logits, const void* saved,
-                                            const float* grad_x, const float* grad_adj_out, const float* grad_link,
-                                            const float* grad_ent, const float* stats, float* grad_z, float* grad_logits,
-                                            float* grad_adj, int adj_symmetric, void* workspace, int64_t workspace_bytes,
-                                            int64_t N, int64_t K, int64_t C, int64_t B, int adj_batched, void* stream) {
-  if (!dpl_supported(N, K, C) || B < 1 || B > 65535) return MLGNN_E_SHAPE;
-  if (!adj || !s_logits || !saved || !grad_x || !grad_adj_out || !grad_link || !grad_ent || !stats || !grad_z ||
-      !grad_logits || !workspace) return MLGNN_E_NULL;
-  const Dpl32Bwd Wl = dpl32_bwd_layout(N, K, C, adj_symmetric);
-  const int64_t W = (int64_t)Wl.total, Wh = W / 2, Wf = W / 4;
-  if (workspace_bytes < W * B) return MLGNN_E_WORKSPACE;
-  if (((uintptr_t)s_logits | (uintptr_t)grad_logits | (uintptr_t)workspace | (uintptr_t)adj | (uintptr_t)grad_x |
-       (uintptr_t)grad_adj_out | (uintptr_t)grad_z | (uintptr_t)saved | (uintptr_t)grad_adj) & 15) return MLGNN_E_ALIGN;
-  const Dpl32Layout L = dpl32_layout(N, K, C);
-  const int64_t WS = (int64_t)L.total, W2 = WS / 2, W4 = WS / 4;
-  const int batch = (int)B, adj_batch = adj_batched ? batch : 1;
-  const int64_t s_adj = adj_batched ? N * N : 0;
-  const int n = (int)N, k = (int)K, c = (int)C;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned char* sv = (const unsigned char*)saved;
-  const uint16_t *Sh = (const uint16_t*)(sv + L.Sh), *Sl = (const uint16_t*)(sv + L.Sl);
-  const uint16_t *Sth = (const uint16_t*)(sv + L.stack_h) + (size_t)K * N, *Stl = (const uint16_t*)(sv + L.stack_l) + (size_t)K * N;
-  const uint16_t *Th = (const uint16_t*)(sv + L.Th), *Tl = (const uint16_t*)(sv + L.Tl);
-  const uint16_t *Zh = (const uint16_t*)(sv + L.Zh), *Zl = (const uint16_t*)(sv + L.Zl);
-  const float* G = (const float*)(sv + L.G);
-  unsigned char* ws = (unsigned char*)workspace;
-  float* coef = (float*)(ws + Wl.coef);
-  float *b1f = (float*)(ws + Wl.b1f), *b3f = (float*)(ws + Wl.b3f);
-  uint16_t *b1h = (uint16_t*)(ws + Wl.b1h), *b1l = (uint16_t*)(ws + Wl.b1l), *b2h = (uint16_t*)(ws + Wl.b2h),
-           *b2l = (uint16_t*)(ws + Wl.b2l), *b3h = (uint16_t*)(ws + Wl.b3h), *b3l = (uint16_t*)(ws + Wl.b3l);
-  uint16_t *gxh = (uint16_t*)(ws + Wl.gxh), *gxl = (uint16_t*)(ws + Wl.gxl), *gxth = (uint16_t*)(ws + Wl.gxth),
-           *gxtl = (uint16_t*)(ws + Wl.gxtl);
-  float* dS = (float*)(ws + Wl.dS);
-  // 1. coef, b1 = ga - cI, b3 = 2c G (fp32)
-  {
-    Dpl32PrepArgs q{grad_link, grad_ent, stats, coef, (float)(1.0 / ((double)adj_batch * (double)N * (double)N)),
-                    (float)(1.0 / ((double)B * (double)N)), grad_adj_out, G, b1f, b3f, k, W4, Wf};
-    const int blocks = (int)(((int64_t)K * K / 4 + 255) / 256);
-    hipLaunchKernelGGL(dpl32_prep_kernel, dim3(blocks < 1024 ? blocks : 1024, batch), dim3(256), 0, st, q);
-  }
-  // 2. their hi / lo terms (b2 = b1^T), gx and gx^T, A^T when adj is not promised symmetric
-  {
-    SplitArgs a{};
-    a.njobs = adj_symmetric ? 3 : 4;
-    SplitJob& j1 = a.job[0];
-    j1 = split_job(b1f, K, k, k, batch, Wf);
-    j1.hi = b1h; j1.lo = b1l; j1.ldo = K; j1.s_out = Wh;
-    j1.hit = b2h; j1.lot = b2l; j1.ldt = K; j1.s_outt = Wh;
-    SplitJob& j3 = a.job[1];
-    j3 = split_job(b3f, K, k, k, batch, Wf);
-    j3.hi = b3h; j3.lo = b3l; j3.ldo = K; j3.s_out = Wh;
-    SplitJob& jx = a.job[2];
-    jx = split_job(grad_x, C, k, c, batch, K * C);
-    jx.hi = gxh; jx.lo = gxl; jx.ldo = C; jx.s_out = Wh;
-    jx.hit = gxth; jx.lot = gxtl; jx.ldt = K; jx.s_outt = Wh;
-    if (!adj_symmetric) {
-      SplitJob& ja = a.job[3];
-      ja = split_job(adj, N, n, n, adj_batch, N * N);
-      ja.hit = (uint16_t*)(ws + Wl.Ath); ja.lot = (uint16_t*)(ws + Wl.Atl); ja.ldt = N; ja.s_outt = Wh;
-    }
-    DPL_CHECK(split_launch(a, batch, st));
-  }
-  const uint16_t *T2h = Th, *T2l = Tl;
-  int64_t s_T2 = W2;
-  if (!adj_symmetric) {
-    uint16_t *Ath = (uint16_t*)(ws + Wl.Ath), *Atl = (uint16_t*)(ws + Wl.Atl);
-    float* T2 = (float*)(ws + Wl.T2);
-    GemmDesc d{};
-    d.nseg = 3;
-    seg3(d, 0, Ath, Atl, Sth, Stl, N, N, n, adj_batched ? Wh : 0, W2);
-    d.M = n; d.N = k; d.splits = 1;
-    d.c = T2; d.ldc = K; d.c_f32 = 1;
-    d.batch = batch; d.s_c = Wf;
-    DPL_CHECK(gemm_nt_launch(d, st));
-    SplitArgs a{};
-    a.njobs = 1;
-    SplitJob& t = a.job[0];
-    t = split_job(T2, K, n, k, batch, Wf);
-    t.hi = (uint16_t*)(ws + Wl.T2h); t.lo = (uint16_t*)(ws + Wl.T2l); t.ldo = K; t.s_out = Wh;
-    DPL_CHECK(split_launch(a, batch, st));
-    T2h = t.hi; T2l = t.lo; s_T2 = Wh;
-  }
-  // 3. dS = Z gx^T + T b1^T + T2 b2^T + S b3^T: twelve bf16 terms as three launches of four segments, the second and
-  //    third adding to the first's result (the epilogue's `+ 1 * aux` with aux = the output itself: every element is
-  //    read and written by the same lane)
-  {
-    GemmSeg all[12];
-    GemmDesc tmp{};
-    seg3(tmp, 0, Zh, Zl, gxh, gxl, C, C, c, W2, Wh);
-    for (int i = 0; i < 3; ++i) all[i] = tmp.seg[i];
-    seg3(tmp, 0, Th, Tl, b1h, b1l, K, K, k, W2, Wh);
-    for (int i = 0; i < 3; ++i) all[3 + i] = tmp.seg[i];
-    seg3(tmp, 0, T2h, T2l, b2h, b2l, K, K, k, s_T2, Wh);
-    for (int i = 0; i < 3; ++i) all[6 + i] = tmp.seg[i];
-    seg3(tmp, 0, Sh, Sl, b3h, b3l, K, K, k, W2, Wh);
-    for (int i = 0; i < 3; ++i) all[9 + i] = tmp.seg[i];
-    for (int part = 0; part < 3; ++part) {
-      GemmDesc d{};
-      d.nseg = 4;
-      for (int i = 0; i < 4; ++i) d.seg[i] = all[4 * part + i];
-      d.M = n; d.N = k; d.splits = 1;
-      d.c = dS; d.ldc = K; d.c_f32 = 1;
-      if (part > 0) { d.aux = dS; d.ldaux = K; d.aux_f32 = 1; d.alpha = 1.f; d.s_aux = Wf; }
-      d.batch = batch; d.s_c = Wf;
-      DPL_CHECK(gemm_nt_launch(d, st));
-    }
-  }
-  // 4. softmax backward with the entropy term
-  const int sm_blocks = (int)((N + 3) / 4 < 1024 ? (N + 3) / 4 : 1024);
-  hipLaunchKernelGGL(dpl_softmax_bwd_kernel<float>, dim3(sm_blocks, batch), dim3(256), 0, st, s_logits, dS, coef, grad_logits,
-                     n, k, Wf);
-  // 5. dZ = S gx
-  {
-    GemmDesc d{};
-    d.nseg = 3;
-    seg3(d, 0, Sh, Sl, gxth, gxtl, K, K, k, W2, Wh);
-    d.M = n; d.N = c; d.splits = 1;
-    d.c = grad_z; d.ldc = C; d.c_f32 = 1;
-    d.batch = batch; d.s_c = N * C;
-    DPL_CHECK(gemm_nt_launch(d, st));
-  }
-  // 6. dA = P S^T + c A,  P = S (dA' - cI)
-  if (grad_adj) {
-    float* P = (float*)(ws + Wl.P);
-    uint16_t *Ph = (uint16_t*)(ws + Wl.Ph), *Pl = (uint16_t*)(ws + Wl.Pl);
-    GemmDesc d{};
-    d.nseg = 3;
-    seg3(d, 0, Sh, Sl, b2h, b2l, K, K, k, W2, Wh);
-    d.M = n; d.N = k; d.splits = 1;
-    d.c = P; d.ldc = K; d.c_f32 = 1;
-    d.batch = batch; d.s_c = Wf;
-    DPL_CHECK(gemm_nt_launch(d, st));
-    SplitArgs a{};
-    a.njobs = 1;
-    SplitJob& t = a.job[0];
-    t = split_job(P, K, n, k, batch, Wf);
-    t.hi = Ph; t.lo = Pl; t.ldo = K; t.s_out = Wh;
-    DPL_CHECK(split_launch(a, batch, st));
-    GemmDesc e{};
-    e.nseg = 3;
-    seg3(e, 0, Ph, Pl, Sh, Sl, K, K, k, Wh, W2);
-    e.M = n; e.N = n; e.splits = 1;
-    e.c = grad_adj; e.ldc = N; e.c_f32 = 1;
-    e.aux = adj; e.ldaux = N; e.aux_f32 = 1; e.alpha = 0.f; e.alpha_dev = coef;
-    e.batch = batch; e.s_c = N * N; e.s_aux = s_adj;
-    DPL_CHECK(gemm_nt_launch(e, st));
-  }
-  (void)Sth; (void)Stl;
-  return (int)hipGetLastError();
-}
-
-
-// =====================================================================================================================
-// fp32 nn.Linear on tall inputs whose widths are past the fp32 tall kernels (csrc/tallgemm.hip: weight image <= 128 KB,
-// i.e. hidden width 512 at BASELINE configs[4]'s d = 256): the same three-term bf16 products as above -- the library's
-// fp32 GEMMs for these shapes (200 000 x 256 x 512) run at ~40 TFLOP/s, 1.35 ms each.
-//     forward   y  = x W^T + b          x [N,R], W [J,R]:  split {x, W}, one three-segment product (bias through aux, ld 0)
-//     backward  dx = go W               split {go (+ go^T), x^T, W^T}, one product
-//               dW = go^T x             one product over the row index, split along it, one reduce
-// Reference: torch_nn.py:54-75 (the Linears of MLP).  R, J multiples of 128; the rows are padded to a multiple of 128
-// inside the workspace (zero rows), y / dx are [Npad, .] buffers whose first N rows are the result.
-namespace mlgnn {
-
-inline int64_t lin3_pad(int64_t N) { return (N + 127) / 128 * 128; }
-inline bool lin3_ok(int64_t N, int64_t R, int64_t J) {
-  return N > 0 && N <= (int64_t)1 << 26 && R >= 128 && J >= 128 && R % 128 == 0 && J % 128 == 0 && R <= 8192 && J <= 8192;
-}
-inline int lin3_splits(int64_t Np, int64_t R, int64_t J) {
-  const int tiles = (int)((J / kGemmTile) * (R / kGemmTile));
-  int sp = 512 / tiles;
-  const int64_t ktiles = 3 * Np / kGemmBK;
-  if (sp > ktiles / 8) sp = (int)(ktiles / 8);
-  return sp < 1 ? 1 : sp;
-}
-
-}  // namespace mlgnn
-
-extern "C" int mlgnn_linear_f32x3_supported(int64_t N, int64_t R, int64_t J) { return lin3_ok(N, R, J) ? 1 : 0; }
-
-extern "C" int64_t mlgnn_linear_f32x3_padded_rows(int64_t N) { return N > 0 ? lin3_pad(N) : 0; }
-
-extern "C" int64_t mlgnn_linear_f32x3_fwd_workspace_bytes(int64_t N, int64_t R, int64_t J) {
-  if (!lin3_ok(N, R, J)) return MLGNN_E_SHAPE;
-  const int64_t Np = lin3_pad(N);
-  return (int64_t)(2 * dpl_align((size_t)Np * R * 2) + 2 * dpl_align((size_t)J * R * 2));
-}
-
-extern "C" int mlgnn_linear_f32x3_fwd(const float* x, const float* w, const float* bias, float* y, void* workspace,
-                                      int64_t workspace_bytes, int64_t N, int64_t R, int64_t J, void* stream) {
-  if (!lin3_ok(N, R, J)) return MLGNN_E_SHAPE;
-  if (!x || !w || !y || !workspace) return MLGNN_E_NULL;
-  if (workspace_bytes < mlgnn_linear_f32x3_fwd_workspace_bytes(N, R, J)) return MLGNN_E_WORKSPACE;
-  if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)y | (uintptr_t)workspace | (uintptr_t)bias) & 15) return MLGNN_E_ALIGN;
-  const int64_t Np = lin3_pad(N);
-  hipStream_t st = (hipStream_t)stream;
-  unsigned char* ws = (unsigned char*)workspace;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { unsigned char* p = ws + o; o += dpl_align(bytes); return (uint16_t*)p; };
-  uint16_t *xh = take((size_t)Np * R * 2), *xl = take((size_t)Np * R * 2);
-  uint16_t *wh = take((size_t)J * R * 2), *wl = take((size_t)J * R * 2);
-  SplitArgs a{};
-  a.njobs = 2;
-  a.job[0] = split_job(x, R, (int)Np, (int)R, 1, 0);
-  a.job[0].rows_valid = (int)N; a.job[0].hi = xh; a.job[0].lo = xl; a.job[0].ldo = R;
-  a.job[1] = split_job(w, R, (int)J, (int)R, 1, 0);
-  a.job[1].hi = wh; a.job[1].lo = wl; a.job[1].ldo = R;
-  DPL_CHECK(split_launch(a, 1, st));
-  GemmDesc d{};
-  d.nseg = 3;
-  seg3(d, 0, xh, xl, wh, wl, R, R, (int)R, 0, 0);
-  d.M = (int)Np; d.N = (int)J; d.splits = 1;
-  d.c = y; d.ldc = J; d.c_f32 = 1;
-  if (bias) { d.aux = bias; d.ldaux = 0; d.aux_f32 = 1; d.alpha = 1.f; }      // leading dimension 0: one row for all
-  d.batch = 1;
-  return gemm_nt_launch(d, st);
-}
-
-extern "C" int64_t mlgnn_linear_f32x3_bwd_workspace_bytes(int64_t N, int64_t R, int64_t J) {
-  if (!lin3_ok(N, R, J)) return MLGNN_E_SHAPE;
-  const int64_t Np = lin3_pad(N);
-  size_t o = 0;
-  o += 4 * dpl_align((size_t)Np * J * 2);             // go hi / lo, go^T hi / lo
-  o += 2 * dpl_align((size_t)Np * R * 2);             // x^T hi / lo
-  o += 2 * dpl_align((size_t)J * R * 2);              // W^T hi / lo
-  o += dpl_align((size_t)lin3_splits(Np, R, J) * J * R * 4);
-  o += dpl_align(kDplPartials * 4);
-  o += dpl_align((size_t)(Np / 64) * J * 4);          // column sums of grad_out per tile row (the bias gradient's partials)
-  return (int64_t)o;
-}
-
-// grad_x [Npad, R] (first N rows = the gradient; NULL: not wanted), grad_w [J, R], grad_bias [J] or NULL (the column
-// sums of grad_out: partial sums per 64 rows from the split launch that reads grad_out anyway, fixed-order reduce).
-extern "C" int mlgnn_linear_f32x3_bwd(const float* grad_out, const float* x, const float* w, float* grad_x, float* grad_w,
-                                      float* grad_bias, void* workspace, int64_t workspace_bytes, int64_t N, int64_t R,
-                                      int64_t J, void* stream) {
-  if (!lin3_ok(N, R, J)) return MLGNN_E_SHAPE;
-  if (!grad_out || !x || !w || !grad_w || !workspace) return MLGNN_E_NULL;
-  if (workspace_bytes < mlgnn_linear_f32x3_bwd_workspace_bytes(N, R, J)) return MLGNN_E_WORKSPACE;
-  if (((uintptr_t)grad_out | (uintptr_t)x | (uintptr_t)w | (uintptr_t)grad_x | (uintptr_t)grad_w | (uintptr_t)workspace) & 15)
-    return MLGNN_E_ALIGN;
-  const int64_t Np = lin3_pad(N);
-  const int splits = lin3_splits(Np, R, J);
-  hipStream_t st = (hipStream_t)stream;
-  unsigned char* ws = (unsigned char*)workspace;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { unsigned char* p = ws + o; o += dpl_align(bytes); return p; };
-  uint16_t *gh = (uint16_t*)take((size_t)Np * J * 2), *gl = (uint16_t*)take((size_t)Np * J * 2);
-  uint16_t *gth = (uint16_t*)take((size_t)Np * J * 2), *gtl = (uint16_t*)take((size_t)Np * J * 2);
-  uint16_t *xth = (uint16_t*)take((size_t)Np * R * 2), *xtl = (uint16_t*)take((size_t)Np * R * 2);
-  uint16_t *wth = (uint16_t*)take((size_t)J * R * 2), *wtl = (uint16_t*)take((size_t)J * R * 2);
-  float* slab = (float*)take((size_t)splits * J * R * 4);
-  float* scratch = (float*)take(kDplPartials * 4);
-  float* colsum = (float*)take((size_t)(Np / 64) * J * 4);
-  {
-    SplitArgs a{};
-    a.njobs = 3;
-    SplitJob& g = a.job[0];
-    g = split_job(grad_out, J, (int)Np, (int)J, 1, 0);
-    g.rows_valid = (int)N; g.hi = gh; g.lo = gl; g.ldo = J; g.hit = gth; g.lot = gtl; g.ldt = Np;
-    g.colsum = grad_bias ? colsum : nullptr;
-    SplitJob& xj = a.job[1];
-    xj = split_job(x, R, (int)Np, (int)R, 1, 0);
-    xj.rows_valid = (int)N; xj.hit = xth; xj.lot = xtl; xj.ldt = Np;
-    SplitJob& wj = a.job[2];
-    wj = split_job(w, R, (int)J, (int)R, 1, 0);
-    wj.hit = wth; wj.lot = wtl; wj.ldt = J;
-    DPL_CHECK(split_launch(a, 1, st));
-  }
-  if (grad_x) {                                        // dx = go W:  go [Np, J] x (W^T [R, J])^T
-    GemmDesc d{};
-    d.nseg = 3;
-    seg3(d, 0, gh, gl, wth, wtl, J, J, (int)J, 0, 0);
-    d.M = (int)Np; d.N = (int)R; d.splits = 1;
-    d.c = grad_x; d.ldc = R; d.c_f32 = 1;
-    d.batch = 1;
-    DPL_CHECK(gemm_nt_launch(d, st));
-  }
-  {                                                    // dW = go^T x:  go^T [J, Np] x (x^T [R, Np])^T, split along the rows
-    GemmDesc d{};
-    d.nseg = 3;
-    seg3(d, 0, gth, gtl, xth, xtl, Np, Np, (int)Np, 0, 0);
-    d.M = (int)J; d.N = (int)R; d.splits = splits; d.slab = slab;
-    d.batch = 1;
-    DPL_CHECK(gemm_nt_launch(d, st));
-    SlabReduceArgs r{};
-    r.slab = slab; r.splits = splits; r.M = (int)J; r.N = (int)R; r.n_a = (int)R; r.n_b = (int)R;
-    r.ca = grad_w; r.lda = R; r.ca_f32 = 1;
-    r.cb = (uint16_t*)scratch; r.ldb = R; r.sq_partial = scratch;
-    r.cc = grad_w; r.ldc = R; r.cc_f32 = 1;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(kDplPartials, 1), dim3(256), 0, st, r);
-  }
-  if (grad_bias) launch_reduce_partials(colsum, grad_bias, (int)(Np / 64), (int)J, st);
   return (int)hipGetLastError();
 }

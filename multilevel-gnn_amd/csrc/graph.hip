@@ -325,8 +325,6 @@ __global__ __launch_bounds__(256) void edge_table_w1_kernel(const float* __restr
   by_src[i] = b;
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static size_t scan_temp_bytes(int64_t n) {
   size_t bytes = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, (const int*)nullptr, (int*)nullptr, (int)n, (hipStream_t)0);

@@ -16,6 +16,7 @@
 // contiguous bytes of a row (2-byte stores of the natural layout would touch 64-byte pieces).  The permutation is
 // free: it only changes which weight row goes where in the LDS image.
 #include "common.h"
+#include "dense_bf16.h"
 #include "mlgnn.h"
 
 namespace mlgnn {

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "dense_bf16.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
@@ -384,11 +385,6 @@ __global__ __launch_bounds__(NW * kWave) void linear_wgrad_kernel(const WgradArg
     out[(size_t)p.M * p.K + m] = s;
   }
 }
-
-// bf16 storage: csrc/wgrad_bf16.hip
-int wb_slabs(int64_t N, int64_t M, int64_t K);
-int linear_wgrad_bf16(const void* grad_out, const void* x, float* grad_w_b, float* workspace, int64_t N, int64_t M,
-                      int64_t K, hipStream_t s);
 
 struct WgradPlan { int nw, wm, wk, tm, tk; };
 

@@ -17,6 +17,7 @@
 // Traffic: every M block streams x once and every K block streams grad_out once -- 2 passes over one of them at
 // 512 x 256 -- against 2 N M K FLOP that take a fifth of that time on the bf16 matrix cores: HBM-bound.
 #include "common.h"
+#include "dense_bf16.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
@@ -178,7 +179,7 @@ __global__ __launch_bounds__(kWbBlock) void linear_wgrad_bf16_kernel(const WbArg
 }
 
 // tiles per wave along M (64 TM | M) and K (128 TK | K); 0 = shape not covered
-void wb_plan(int64_t M, int64_t K, int* tm, int* tk) {
+static void wb_plan(int64_t M, int64_t K, int* tm, int* tk) {
   *tm = *tk = 0;
   if (M <= 0 || K <= 0 || M % 64 != 0 || K % 128 != 0 || M > 4096 || K > 4096) return;
   *tm = M % 256 == 0 ? 4 : (M % 128 == 0 ? 2 : 1);

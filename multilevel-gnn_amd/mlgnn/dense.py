@@ -449,7 +449,7 @@ def fused_mlp2_post_supported(x, w1, w2, post_weight):
 class _WideLinearF32(torch.autograd.Function):
     """``y = x W^T + b`` for a tall fp32 ``x`` whose widths are past the fp32 tall kernels (hidden width 512): forward,
     ``dX`` and ``dW`` as three-term bf16 products on the matrix cores (``mlgnn_linear_f32x3_fwd`` / ``_bwd``,
-    csrc/diffpool_large.hip) instead of the library's fp32 GEMMs."""
+    csrc/linear_f32x3.hip) instead of the library's fp32 GEMMs."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -806,7 +806,7 @@ class _DiffPoolLarge(torch.autograd.Function):
 class _DiffPoolLargeFP32(torch.autograd.Function):
     """fp32 inputs at sizes past the fused small-graph kernel (multiples of 128): the product chain of
     :class:`_DiffPoolLarge` with every product as three bf16 terms on the matrix cores (fp32-level accuracy: within 1e-4
-    of fp64), one C entry point each way (``mlgnn_diffpool_large_f32_fwd`` / ``_bwd``, csrc/diffpool_large.hip); a batch
+    of fp64), one C entry point each way (``mlgnn_diffpool_large_f32_fwd`` / ``_bwd``, csrc/diffpool_large_f32.hip); a batch
     ``z [B,N,C]``, ``s [B,N,K]``, ``adj [B,N,N]`` or ``[1,N,N]`` (shared) runs as grouped launches."""
 
     @staticmethod
@@ -884,7 +884,7 @@ def dense_diff_pool(z, adj, s, adj_symmetric=False):
     Pooled graphs of up to 160 nodes / 48 clusters / 64 channels (the reference's 146 -> 37 -> 10)
     run as one fused fp32-MFMA launch; graphs whose sizes are multiples of 128 (BASELINE configs[4]:
     4096 nodes, 1024 clusters) as the matrix-core product chain of csrc/diffpool_large.hip (bf16) or its three-term
-    fp32-accurate form; anything else as batched library GEMMs.  ``adj_symmetric`` promises ``adj == adj^T`` (saves a third of the large backward)."""
+    fp32-accurate form (csrc/diffpool_large_f32.hip); anything else as batched library GEMMs.  ``adj_symmetric`` promises ``adj == adj^T`` (saves a third of the large backward)."""
     z = z.unsqueeze(0) if z.dim() == 2 else z
     adj = adj.unsqueeze(0) if adj.dim() == 2 else adj
     s = s.unsqueeze(0) if s.dim() == 2 else s

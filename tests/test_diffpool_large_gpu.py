@@ -1,5 +1,5 @@
 """DiffPool contraction for large pooled graphs (csrc/diffpool_large.hip, csrc/gemm_nt.hip; BASELINE configs[4]:
-4096 nodes, 1024 clusters, 256 channels, bf16) against the fp64 oracle ``oracle.primitives.dense_diff_pool``
+4096 nodes, 1024 clusters, 256 channels, bf16; the fp32 three-term form: csrc/diffpool_large_f32.hip) against the fp64 oracle ``oracle.primitives.dense_diff_pool``
 (reference: torch_geometric dense_diff_pool as called from models/diff_pooling.py:59-65).
 
 Two levels.  (i) Kernel arithmetic: given the bf16-rounded softmax S~ the kernel itself produced, every product must

@@ -1,5 +1,5 @@
 """fp32 nn.Linear at widths past the fp32 tall kernels (hidden 512 at BASELINE configs[4]'s d = 256):
-``mlgnn_linear_f32x3_fwd`` / ``_bwd`` -- three-term bf16 products -- against fp64 (torch_nn.py:54-75)."""
+``mlgnn_linear_f32x3_fwd`` / ``_bwd`` (csrc/linear_f32x3.hip) -- three-term bf16 products -- against fp64 (torch_nn.py:54-75)."""
 import pytest
 import torch
 

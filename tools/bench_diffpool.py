@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """dense_diff_pool at BASELINE configs[4] size (pooled graph of 4096 nodes, 1024 clusters, 256 channels, bf16):
-the matrix-core product chain of csrc/diffpool_large.hip next to the library-GEMM formulation it replaces.
+the matrix-core product chain of csrc/diffpool_large.hip (--dtype fp32: its three-term form, csrc/diffpool_large_f32.hip)
+next to the library-GEMM formulation it replaces.
 
   python tools/bench_diffpool.py [--iters 20] [--json profiles/r02_diffpool_configs4.json]
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Development tool: random shapes through the fp32 three-term paths -- ``mlgnn_linear_f32x3_*`` (ragged row counts,
-widths that are multiples of 128) and ``mlgnn_diffpool_large_f32_*`` (batches, own / shared adjacency, the symmetric
+"""Development tool: random shapes through the fp32 three-term paths -- ``mlgnn_linear_f32x3_*`` (csrc/linear_f32x3.hip; ragged
+row counts, widths that are multiples of 128) and ``mlgnn_diffpool_large_f32_*`` (csrc/diffpool_large_f32.hip; batches, own / shared adjacency, the symmetric
 shortcut, adjacency gradient) -- against fp64 on the device.  `python tools/fuzz_dense_f32.py [cases] [seed]`."""
 import os
 import random

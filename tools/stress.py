@@ -94,6 +94,7 @@ def main():
 
     # DiffPool at the stress size (pooled graph of 4096 nodes, 1024 clusters): bf16 -> the matrix-core product chain of
     # csrc/diffpool_large.hip (tools/bench_diffpool.py has the full report); fp32 -> the same chain with three-term products
+    # (csrc/diffpool_large_f32.hip)
     P, K, C = 4096, 1024, a.hidden
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
     peak = 2500.0 if a.dtype == "bf16" else 157.3                 # TFLOP/s dense: bf16 MFMA / fp32 matrix (MI355X_MICROARCH.md)
@@ -128,7 +129,7 @@ def main():
                                  "approx_TFLOPs_fwd_bwd": 3 * flop_fwd / dtp / 1e12,
                                  "dense_peak_TFLOPs": peak,
                                  "path": "csrc/diffpool_large.hip + gemm_nt.hip (bf16 MFMA)" if a.dtype == "bf16"
-                                 else ("gemm_nt.hip, every product as three bf16 terms (mlgnn_diffpool_large_f32_fwd / _bwd)"
+                                 else ("csrc/diffpool_large_f32.hip + gemm_nt.hip, every product as three bf16 terms"
                                        if large_fp32 else "library GEMMs (fp32)"),
                                  "note": "FLOP counted in the reference's formulation (incl. S S^T); see tools/bench_diffpool.py"}
     print(json.dumps(res, indent=1))
