@@ -884,6 +884,38 @@ int mlgnn_skinny_linear_bwd(const float* grad_out, const float* x, const float* 
                             float* grad_b, int64_t M, int64_t J, int64_t K, void* stream);
 
 /*
+ * Graph attention convolution (csrc/gat.hip), fp32: PyG GATConv (concat, self loops added by the caller's graph, no edge
+ * features, no dropout) as wrapped by models/gcn_lib/sparse/torch_vertex.py:207-223.  z [N,H,C] = lin_src(x) is the
+ * caller's GEMM.  H in 1..16, d = H * C <= 256, tensors below 4 GiB; C % 4 == 0 takes 16-byte loads (16-byte aligned
+ * operands: MLGNN_E_ALIGN otherwise), any other C one float per lane.  No atomics: bitwise reproducible.
+ *
+ *   mlgnn_gat_scores         a_src[n,h] = <z[n,h,:], att_src[h,:]>, a_dst likewise with att_dst ([N,H] each)
+ *   mlgnn_gat_aggregate_fwd  y[i,h,:] = act(sum_{j->i} alpha z[j,h,:] + bias),  alpha = softmax over the incoming edges of i
+ *                            of leaky_relu(a_src[j,h] + a_dst[i,h], negative_slope), the row maximum subtracted;
+ *                            act = leaky_relu(., act_slope) (1: none, 0: relu); bias [d] or NULL; a row without edges
+ *                            yields act(bias).  rowptr [N+1], col [E]: CSR by destination.  lse [N,H]: max + ln(sum),
+ *                            for the backward; row_max [N] (NULL: skipped): max_c |y[i][c]|.
+ *   mlgnn_gat_aggregate_bwd  grad_z [N,d], grad_att_src / grad_att_dst [d] (both or neither), grad_bias [d]; each may be
+ *                            NULL (skipped).  rowptr_t / col_t / pos_t: CSR by source.  workspace:
+ *                            mlgnn_gat_bwd_workspace_floats(N, E, H, C) floats, 16-byte aligned.
+ */
+int mlgnn_gat_supported(int64_t N, int64_t H, int64_t C);
+int mlgnn_gat_scores(const float* z, const float* att_src, const float* att_dst, float* a_src, float* a_dst,
+                     int64_t N, int64_t H, int64_t C, void* stream);
+int mlgnn_gat_aggregate_fwd(const float* z, const float* a_src, const float* a_dst, const float* bias,
+                            const int32_t* rowptr, const int32_t* col, float* y, float* lse, float* row_max,
+                            int64_t N, int64_t E, int64_t H, int64_t C, float negative_slope, float act_slope,
+                            void* stream);
+int64_t mlgnn_gat_bwd_workspace_floats(int64_t N, int64_t E, int64_t H, int64_t C);
+int mlgnn_gat_aggregate_bwd(const float* grad_y, const float* y, const float* z, const float* a_src,
+                            const float* a_dst, const float* lse, const float* att_src, const float* att_dst,
+                            const float* bias, const int32_t* rowptr, const int32_t* rowptr_t,
+                            const int32_t* col_t, const int32_t* pos_t, float* grad_z, float* grad_att_src,
+                            float* grad_att_dst, float* grad_bias, float* workspace, int64_t workspace_floats,
+                            int64_t N, int64_t E, int64_t H, int64_t C, float negative_slope, float act_slope,
+                            void* stream);
+
+/*
  * Measurement aid (bench.py: the box's streaming ceiling next to the 8 TB/s spec peak): dst = src, 16 bytes per lane,
  * non_temporal != 0: non-temporal loads and stores.  bytes a multiple of 16, 16-byte aligned pointers.
  */

@@ -4,6 +4,7 @@ There is no CPU fallback.  Every op in this package launches a HIP kernel throug
 declared in ``include/mlgnn.h``; importing :mod:`mlgnn._lib` raises if the shared library has not
 been built (``python __graft_entry__.py`` or ``python multilevel-gnn_amd/build_native.py``).
 """
+from .gat import gat_aggregate  # noqa: F401
 from .graph import CSRGraph, as_graph  # noqa: F401
 from .ops import (LowRankEdge, RankOneEdge, TableEdge, edge_type_embedding, gen_aggregate, share_edge_gradient,  # noqa: F401
                   weighted_mean_aggregate)

@@ -101,6 +101,11 @@ SIGNATURES = {
     "mlgnn_skinny_linear_fwd_workspace_floats": (_I64, [_I64, _I64, _I64]),
     "mlgnn_skinny_linear_fwd": (_INT, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P]),
     "mlgnn_skinny_linear_bwd": (_INT, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P]),
+    "mlgnn_gat_supported": (_INT, [_I64, _I64, _I64]),
+    "mlgnn_gat_scores": (_INT, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P]),
+    "mlgnn_gat_aggregate_fwd": (_INT, [_P] * 9 + [_I64, _I64, _I64, _I64, _F, _F, _P]),
+    "mlgnn_gat_bwd_workspace_floats": (_I64, [_I64, _I64, _I64, _I64]),
+    "mlgnn_gat_aggregate_bwd": (_INT, [_P] * 18 + [_I64, _I64, _I64, _I64, _I64, _F, _F, _P]),
     "mlgnn_stream_copy": (_INT, [_P, _P, _I64, _INT, _P]),
     "mlgnn_gemm_bf16_nt_workgroups": (_INT, [_I64, _I64, _INT]),
     "mlgnn_gemm_bf16_nt": (_INT, [_c.POINTER(_P), _c.POINTER(_P), _c.POINTER(_I64), _c.POINTER(_I64), _c.POINTER(_I64),

@@ -1,9 +1,10 @@
 """Sparse graph convolutions on the HIP CSR kernels (interface of the reference's
 ``models/gcn_lib/sparse/torch_vertex.py``: ``GENConv`` :12-104, ``SAGEConv`` :226-294,
-``RSAGEConv`` :297-304, ``GraphConv`` :338-363).
+``RSAGEConv`` :297-304, ``GATConv`` :207-223, ``GraphConv`` :338-363).
 
-Only the conv types reachable from the shipped configs are provided (``gen``, ``sage``, ``rsage``);
-the PyG-wrapper types (edge/mr/gat/gcn/gin) raise ``NotImplementedError``.
+Provided: ``gen``, ``sage``, ``rsage`` (the shipped configs) and ``gat`` (the reference's default ``gnn_name``); the other
+PyG-wrapper types (edge/mr/gcn/gin) raise ``NotImplementedError`` -- the reference's ``GraphConv.forward`` cannot call
+them either.
 """
 import math
 import os
@@ -13,11 +14,12 @@ import torch.nn.functional as F
 from torch import nn
 
 from mlgnn import LowRankEdge, TableEdge, as_graph, weighted_mean_aggregate
+from mlgnn import gat as mlgnn_gat
 from mlgnn.dense import linear
 from mlgnn.graph import sage_graph
 from mlgnn.norm import msg_norm_add
 from .torch_message import GenMessagePassing, MsgNorm
-from .torch_nn import MLP
+from .torch_nn import MLP, act_layer, norm_layer
 
 _SAGE_FUSED = os.environ.get("MLGNN_SAGE_FUSED", "1") == "1"      # (0: the separate aggregate / lin_r / cat / Linear / act ops, for A/B runs)
 
@@ -169,6 +171,64 @@ class RSAGEConv(SAGEConv):
         super().__init__(in_channels, out_channels, nn_, norm, False, relative)
 
 
+class _PygGAT(nn.Module):
+    """Parameters of PyG 2.2 ``GATConv(in, C, heads=H, bias=bias)`` under its attribute names: ``lin_src`` (bias-free, not
+    an ``nn.Linear``: the models' xavier sweeps skip it) and ``lin_dst``, the SAME module (``state_dict`` lists both
+    weights, ``parameters()`` yields one), ``att_src`` / ``att_dst`` [1, H, C], ``bias`` [H * C]; glorot / zeros."""
+
+    def __init__(self, in_channels, out_channels, heads=1, bias=True, negative_slope=0.2):
+        super().__init__()
+        self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
+        self.negative_slope = negative_slope
+        self.lin_src = Linear(in_channels, heads * out_channels, bias=False)
+        self.lin_dst = self.lin_src
+        self.att_src = nn.Parameter(torch.empty(1, heads, out_channels))
+        self.att_dst = nn.Parameter(torch.empty(1, heads, out_channels))
+        self.bias = nn.Parameter(torch.zeros(heads * out_channels)) if bias else None
+        for t in (self.lin_src.weight, self.att_src, self.att_dst):
+            a = math.sqrt(6.0 / (t.size(-2) + t.size(-1)))          # PyG's glorot
+            nn.init.uniform_(t, -a, a)
+
+
+class GATConv(nn.Module):
+    """Graph attention: ``unlinear(softmax-weighted sum_j z_j + bias)``, ``z = lin_src(x)``, over the edges with the
+    input's self loops replaced by one per node (the rewrite SAGEConv uses).  The projection is :func:`mlgnn.dense.linear`,
+    everything per edge is :func:`mlgnn.gat.gat_aggregate`; a leading ReLU / LeakyReLU of ``unlinear`` runs in its
+    epilogue.  ``out_channels`` is per head: the output is ``heads * out_channels`` wide; the norm of ``unlinear`` is built
+    ``out_channels`` wide as the reference writes it (meaningful for one head only)."""
+
+    def __init__(self, in_channels, out_channels, act='relu', norm=None, bias=True, heads=8):
+        super().__init__()
+        self.gconv = _PygGAT(in_channels, out_channels, heads, bias=bias)
+        m = []
+        if act:
+            m.append(act_layer(act))
+        if norm:
+            m.append(norm_layer(norm, out_channels))
+        self.unlinear = nn.Sequential(*m)
+
+    def _epilogue(self):
+        """``(slope of the activation the kernel applies, the modules of unlinear left to run)``"""
+        mods = list(self.unlinear)
+        if mods and type(mods[0]) is nn.ReLU:
+            return 0.0, mods[1:]
+        if mods and type(mods[0]) is nn.LeakyReLU and mods[0].negative_slope > 0:
+            return float(mods[0].negative_slope), mods[1:]
+        return 1.0, mods
+
+    def forward(self, x, edge_index, edge_attr=None, row_scale=None, shared=None):
+        """``edge_attr`` is ignored (the reference's wrapper drops it); ``row_scale`` / ``shared``: see SAGEConv."""
+        x = x.unsqueeze(-1) if x.dim() == 1 else x
+        graph, _ = sage_graph(edge_index, None, x.shape[0], shared)
+        g = self.gconv
+        z = linear(x, g.lin_src.weight)
+        slope, rest = self._epilogue()
+        out = mlgnn_gat.gat_aggregate(z, g.att_src, g.att_dst, g.bias, graph, g.heads, g.negative_slope, slope)
+        for m in rest:
+            out = m(out)
+        return out if row_scale is None else out * row_scale.reshape(-1, 1)
+
+
 class GraphConv(nn.Module):
     """Static graph convolution dispatcher (torch_vertex.py:338-363)."""
 
@@ -180,7 +240,9 @@ class GraphConv(nn.Module):
             self.gconv = RSAGEConv(in_channels, out_channels, act, norm, mlp_norm, bias, False, drop)
         elif kind == 'rsage':
             self.gconv = RSAGEConv(in_channels, out_channels, act, norm, mlp_norm, bias, True, drop)
-        elif kind in ('edge', 'mr', 'gat', 'gcn', 'gin'):
+        elif kind == 'gat':
+            self.gconv = GATConv(in_channels, out_channels // heads, act, norm, bias, heads)
+        elif kind in ('edge', 'mr', 'gcn', 'gin'):
             raise NotImplementedError('conv {} needs PyG layers outside the accelerated path'.format(conv))
         else:
             raise NotImplementedError('conv {} is not implemented'.format(conv))

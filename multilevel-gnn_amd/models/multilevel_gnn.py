@@ -2,7 +2,7 @@
 class ``MultilevelGNN`` :14, ``forward`` :132-292, ``get_feature_loss`` :329, setters :301-311,
 :350-351, :383-384, ``generate_mutual_mask`` :353).
 
-Level 0: per-node embedding scale -> GraphConv('sage'|'rsage') stack on the CSR kernels -> value
+Level 0: per-node embedding scale -> GraphConv('sage'|'rsage'|'gat') stack on the CSR kernels -> value
 mask; level 1: gene -> pathway learnable-projection pooling; level 2: 1x1 conv head.  Same
 constructor, ``forward(batch) -> (pred [B,2], pca_feature [B,C,146,3k])`` and ``state_dict`` keys.
 The reference's ``except: pdb.set_trace()`` traps around the layer calls are NOT reproduced:
