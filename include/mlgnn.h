@@ -916,6 +916,30 @@ int mlgnn_gat_aggregate_bwd(const float* grad_y, const float* y, const float* z,
                             void* stream);
 
 /*
+ * Dense multi-head self-attention over a short sequence (csrc/mha.hip), fp32: the attention of the pathway readout
+ * 'MSA' (nn.TransformerEncoderLayer over the pathway tokens, models/deepergcn.py:126-128,296-305).
+ *   qkv [B*P, 3*H*D] row-major = linear(x, in_proj_weight, in_proj_bias): columns [0,HD) q, [HD,2HD) k, [2HD,3HD) v,
+ *   head h at h*D .. (h+1)*D of each third, sample b at rows b*P .. (b+1)*P.  Per (b, h), query row i, key row j:
+ *     s_ij = <q_i, k_j> / sqrt(D),  a_ij = softmax_j(s_ij) (row maximum subtracted),  lse_i = max_j s_ij + log sum_j exp(s_ij - max)
+ *     out_i = sum_j (keep_ij * keep_scale * a_ij) v_j          out [B*P, H*D], lse [B, H, P]
+ *   keep [B, H, P, P] bytes or NULL: the dropout on the attention probabilities, drawn by the caller; it multiplies.
+ *   mlgnn_mha_bwd: grad_qkv in the layout of qkv, every element written; a is recomputed from lse, and
+ *     Dl_i = <grad_out_i, out_i> is formed as sum_j a_ij dA_ij from the same registers (out is part of the contract and
+ *     must be passed, this build does not read it);
+ *     workspace: mlgnn_mha_bwd_workspace_floats(B, P, H, D) floats (0 in this build: NULL is accepted).
+ * One workgroup per (b, h), q / k / v (and grad_out) in LDS, no atomics: bitwise reproducible.  Shapes
+ * (mlgnn_mha_supported): H in 1..16, P <= 256, D <= 64 as far as the backward's LDS image fits 160 KiB (every P for
+ * D <= 32; P <= 147 at D = 64), qkv below 4 GiB.  MLGNN_E_SHAPE for anything else; B = 0 or P = 0 is a no-op.
+ */
+int mlgnn_mha_supported(int64_t B, int64_t P, int64_t H, int64_t D);
+int mlgnn_mha_fwd(const float* qkv, const uint8_t* keep, float keep_scale, float* out, float* lse,
+                  int64_t B, int64_t P, int64_t H, int64_t D, void* stream);
+int64_t mlgnn_mha_bwd_workspace_floats(int64_t B, int64_t P, int64_t H, int64_t D);
+int mlgnn_mha_bwd(const float* grad_out, const float* qkv, const float* out, const float* lse,
+                  const uint8_t* keep, float keep_scale, float* grad_qkv, float* workspace, int64_t workspace_floats,
+                  int64_t B, int64_t P, int64_t H, int64_t D, void* stream);
+
+/*
  * Measurement aid (bench.py: the box's streaming ceiling next to the 8 TB/s spec peak): dst = src, 16 bytes per lane,
  * non_temporal != 0: non-temporal loads and stores.  bytes a multiple of 16, 16-byte aligned pointers.
  */

@@ -106,6 +106,10 @@ SIGNATURES = {
     "mlgnn_gat_aggregate_fwd": (_INT, [_P] * 9 + [_I64, _I64, _I64, _I64, _F, _F, _P]),
     "mlgnn_gat_bwd_workspace_floats": (_I64, [_I64, _I64, _I64, _I64]),
     "mlgnn_gat_aggregate_bwd": (_INT, [_P] * 18 + [_I64, _I64, _I64, _I64, _I64, _F, _F, _P]),
+    "mlgnn_mha_supported": (_INT, [_I64, _I64, _I64, _I64]),
+    "mlgnn_mha_fwd": (_INT, [_P, _P, _F, _P, _P, _I64, _I64, _I64, _I64, _P]),
+    "mlgnn_mha_bwd_workspace_floats": (_I64, [_I64, _I64, _I64, _I64]),
+    "mlgnn_mha_bwd": (_INT, [_P, _P, _P, _P, _P, _F, _P, _P, _I64, _I64, _I64, _I64, _I64, _P]),
     "mlgnn_stream_copy": (_INT, [_P, _P, _I64, _INT, _P]),
     "mlgnn_gemm_bf16_nt_workgroups": (_INT, [_I64, _I64, _INT]),
     "mlgnn_gemm_bf16_nt": (_INT, [_c.POINTER(_P), _c.POINTER(_P), _c.POINTER(_I64), _c.POINTER(_I64), _c.POINTER(_I64),

@@ -6,8 +6,18 @@ Same constructor ``(args)``, same ``forward(batch) -> softmax probabilities [B, 
 all layers; a scalar raw edge attribute is carried as a rank-one term through both Linear edge
 encoders (no ``[E, d]`` embedding, no per-layer edge GEMM); the per-graph Python loops with
 device->host syncs of the pathway-global-node branch (:221,:290) are index arithmetic on device.
+
+``pathway_readout='MSA'`` (:126-128, :296-305): ``BatchNorm1d(pathway_num)`` over the stacked pathway rows, one
+``nn.TransformerEncoderLayer(hidden_channels, 8, batch_first=True)`` and the graph pooling over its tokens.  The layer
+is :class:`MSAReadout`, a subclass of the stock module (same parameters, ``state_dict`` keys and initial values) whose
+forward runs ``softmax(Q K^T / sqrt(D)) V`` as one HIP launch per direction (:func:`mlgnn.mha_attention`, csrc/mha.hip)
+on the in-projection's output as it lies in memory, the Linears through :func:`mlgnn.dense.linear` (residual adds in
+their epilogues) and the LayerNorms through :func:`mlgnn.norm.layer_norm_act`.  ``MLGNN_MSA_FUSED=0`` runs the attention
+as torch ops on the device instead (A/B runs).
 """
 import logging
+import math
+import os
 
 import torch
 import torch.nn as nn
@@ -16,10 +26,69 @@ import torch.nn.functional as F
 from mlgnn import CSRGraph, LowRankEdge
 from mlgnn import TableEdge, share_edge_gradient
 from mlgnn.dense import linear
+from mlgnn.mha import mha_attention, mha_supported
 from mlgnn.norm import layer_norm_act, layer_norm_act_fork
 from mlgnn.pool import global_pool
 from .gcn_lib.sparse.torch_vertex import GENConv
 from .gcn_lib.sparse.torch_nn import norm_layer
+
+MSA_FUSED = os.environ.get("MLGNN_MSA_FUSED", "1") == "1"      # (0: the attention of MSAReadout as torch ops, for A/B runs)
+
+
+def torch_attention(qkv, batch, heads, keep=None, keep_scale=1.0):
+    """What :func:`mlgnn.mha_attention` computes, in torch ops on the device of ``qkv`` (shapes the kernels refuse,
+    ``MLGNN_MSA_FUSED=0``)."""
+    B, H = int(batch), int(heads)
+    P, D = qkv.shape[0] // B, qkv.shape[1] // (3 * H)
+    q, k, v = qkv.reshape(B, P, 3, H, D).permute(2, 0, 3, 1, 4)              # [B, H, P, D] each
+    a = torch.softmax(torch.matmul(q, k.transpose(-1, -2)) / math.sqrt(D), dim=-1)
+    if keep is not None:
+        a = a * (keep.to(a.dtype) * keep_scale)
+    return torch.matmul(a, v).transpose(1, 2).reshape(B * P, H * D)
+
+
+class MSAReadout(nn.TransformerEncoderLayer):
+    """``nn.TransformerEncoderLayer`` (post-norm, ReLU, batch first) with the forward on the HIP path; parameters,
+    ``state_dict`` keys and initial values are the stock module's by construction.  The dropout masks are drawn by
+    torch's generator (the attention's as a byte mask the kernel multiplies in)."""
+
+    def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0.1, batch_first=True):
+        if not batch_first:
+            raise NotImplementedError("MSAReadout is batch first, as the reference builds the layer")
+        super().__init__(d_model=d_model, nhead=nhead, dim_feedforward=dim_feedforward, dropout=dropout,
+                         batch_first=True)
+
+    def _attention(self, qkv, B):
+        at = self.self_attn
+        P = qkv.shape[0] // B
+        keep, scale = None, 1.0
+        if self.training and at.dropout > 0:
+            p = float(at.dropout)
+            keep = torch.empty((B, at.num_heads, P, P), dtype=torch.uint8, device=qkv.device)
+            keep, scale = (keep.zero_(), 0.0) if p >= 1.0 else (keep.bernoulli_(1.0 - p), 1.0 / (1.0 - p))
+        if MSA_FUSED and mha_supported(qkv, B, at.num_heads):
+            return mha_attention(qkv, B, at.num_heads, keep, scale)
+        return torch_attention(qkv, B, at.num_heads, keep, scale)
+
+    def forward(self, src, src_mask=None, src_key_padding_mask=None, is_causal=False):
+        if src_mask is not None or src_key_padding_mask is not None or is_causal:
+            raise NotImplementedError("MSAReadout attends over all tokens (no masks), as the reference calls the layer")
+        B, P, d = src.shape
+        at = self.self_attn
+        x = src.reshape(B * P, d)
+        qkv = linear(x, at.in_proj_weight, at.in_proj_bias)
+        o = self._attention(qkv, B)
+        if self.training and self.dropout1.p > 0:
+            y = x + self.dropout1(linear(o, at.out_proj.weight, at.out_proj.bias))
+        else:
+            y = linear(o, at.out_proj.weight, at.out_proj.bias, residual=x)
+        y = layer_norm_act(y, self.norm1.weight, self.norm1.bias, self.norm1.eps)
+        f = self.dropout(F.relu(linear(y, self.linear1.weight, self.linear1.bias)))
+        if self.training and self.dropout2.p > 0:
+            f = y + self.dropout2(linear(f, self.linear2.weight, self.linear2.bias))
+        else:
+            f = linear(f, self.linear2.weight, self.linear2.bias, residual=y)
+        return layer_norm_act(f, self.norm2.weight, self.norm2.bias, self.norm2.eps).reshape(B, P, d)
 
 
 class DeeperGCN(torch.nn.Module):
@@ -42,7 +111,7 @@ class DeeperGCN(torch.nn.Module):
             raise Exception('Unknown Conv Type')
         if args.gnn_encoder != 'linear':
             raise NotImplementedError("gnn_encoder=%r is outside the accelerated path" % (args.gnn_encoder,))
-        if args.pathway_global_node and args.pathway_readout not in (None, 'maxpool'):
+        if args.pathway_global_node and args.pathway_readout not in (None, 'maxpool', 'MSA'):
             raise NotImplementedError("pathway_readout=%r is outside the accelerated path" % (args.pathway_readout,))
 
         self.pca_only = args.pca_only
@@ -89,6 +158,9 @@ class DeeperGCN(torch.nn.Module):
             if not args.pre_readout_drop:
                 mods.append(nn.Dropout(0.5))
             self.readout_func = nn.Sequential(*mods)
+        elif self.pathway_global_node and self.pathway_readout == 'MSA':
+            self.pred_norm = nn.BatchNorm1d(self.pathway_num)
+            self.readout_func = MSAReadout(hidden_channels, 8, batch_first=True)
 
         if args.graph_pooling not in ("sum", "mean", "max"):
             raise Exception('Unknown Pool Type')
@@ -237,6 +309,10 @@ class DeeperGCN(torch.nn.Module):
             prow = h.index_select(0, rows)
             if self.pathway_readout is None:
                 h_graph = global_pool(prow, batch.index_select(0, rows), self.graph_pooling, n_graphs)
+            elif self.pathway_readout == 'MSA':
+                prow = self.readout_func(self.pred_norm(prow.reshape(-1, self.pathway_num, h.shape[-1])))
+                h_graph = global_pool(prow.reshape(-1, h.shape[-1]), batch.index_select(0, rows), self.graph_pooling,
+                                      n_graphs)
             else:  # maxpool
                 prow = prow.reshape(-1, self.pathway_num, h.shape[-1])
                 if self.feature_drop_flag:
