@@ -940,6 +940,28 @@ int mlgnn_mha_bwd(const float* grad_out, const float* qkv, const float* out, con
                   int64_t B, int64_t P, int64_t H, int64_t D, void* stream);
 
 /*
+ * Direct k x k convolution over a channel-last image (csrc/conv2d.hip), fp32: F.conv2d(x, w, bias, stride 1,
+ * padding k / 2) (+ ReLU), the convolutions of the PathCNN baseline and of the pathway head for k > 1.
+ *   x [B, H, W, Cin] and y [B, H, W, Cout] are the memory of channel-last [B, C, H, W] tensors; w [Cout, Cin, k, k] and
+ *   bias [Cout] (or NULL) as nn.Conv2d holds them.
+ *   mlgnn_conv2d_fwd: one launch; relu != 0 applies max(., 0) in the epilogue.
+ *   mlgnn_conv2d_bwd: grad_y [B, H, W, Cout]; with relu != 0 it is masked by y > 0 while it is staged (y: the forward's
+ *     output, may be NULL when relu == 0).  grad_x [B, H, W, Cin], grad_w [Cout, Cin, k, k], grad_bias [Cout]: each may
+ *     be NULL (not wanted).  At most three launches: grad_x, the partial weight / bias gradients, their reduction in a
+ *     fixed order.  workspace: mlgnn_conv2d_bwd_workspace_floats floats (needed when grad_w or grad_bias is asked for).
+ * Implicit GEMMs on v_mfma_f32_16x16x4_f32 (exact fp32), no atomics: bitwise reproducible.  Shapes
+ * (mlgnn_conv2d_supported): k in {3, 5}, 1 <= Cin, Cout <= 128, 1 <= W <= 32, H >= 1, every tensor below 4 GiB;
+ * MLGNN_E_SHAPE for anything else (shape errors are reported before NULL operands); B = 0 is a no-op.
+ */
+int mlgnn_conv2d_supported(int64_t B, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t k);
+int mlgnn_conv2d_fwd(const float* x, const float* w, const float* bias, float* y, int relu, int64_t B, int64_t H,
+                     int64_t W, int64_t Cin, int64_t Cout, int64_t k, void* stream);
+int64_t mlgnn_conv2d_bwd_workspace_floats(int64_t B, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t k);
+int mlgnn_conv2d_bwd(const float* grad_y, const float* x, const float* w, const float* y, int relu, float* grad_x,
+                     float* grad_w, float* grad_bias, float* workspace, int64_t workspace_floats, int64_t B, int64_t H,
+                     int64_t W, int64_t Cin, int64_t Cout, int64_t k, void* stream);
+
+/*
  * Measurement aid (bench.py: the box's streaming ceiling next to the 8 TB/s spec peak): dst = src, 16 bytes per lane,
  * non_temporal != 0: non-temporal loads and stores.  bytes a multiple of 16, 16-byte aligned pointers.
  */

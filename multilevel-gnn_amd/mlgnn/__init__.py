@@ -7,5 +7,6 @@ been built (``python __graft_entry__.py`` or ``python multilevel-gnn_amd/build_n
 from .gat import gat_aggregate  # noqa: F401
 from .graph import CSRGraph, as_graph  # noqa: F401
 from .mha import mha_attention  # noqa: F401
+from .conv import PathConv2d, conv2d, conv2d_supported  # noqa: F401
 from .ops import (LowRankEdge, RankOneEdge, TableEdge, edge_type_embedding, gen_aggregate, share_edge_gradient,  # noqa: F401
                   weighted_mean_aggregate)

@@ -110,6 +110,10 @@ SIGNATURES = {
     "mlgnn_mha_fwd": (_INT, [_P, _P, _F, _P, _P, _I64, _I64, _I64, _I64, _P]),
     "mlgnn_mha_bwd_workspace_floats": (_I64, [_I64, _I64, _I64, _I64]),
     "mlgnn_mha_bwd": (_INT, [_P, _P, _P, _P, _P, _F, _P, _P, _I64, _I64, _I64, _I64, _I64, _P]),
+    "mlgnn_conv2d_supported": (_INT, [_I64] * 6),
+    "mlgnn_conv2d_fwd": (_INT, [_P, _P, _P, _P, _INT] + [_I64] * 6 + [_P]),
+    "mlgnn_conv2d_bwd_workspace_floats": (_I64, [_I64] * 6),
+    "mlgnn_conv2d_bwd": (_INT, [_P, _P, _P, _P, _INT, _P, _P, _P, _P, _I64] + [_I64] * 6 + [_P]),
     "mlgnn_stream_copy": (_INT, [_P, _P, _I64, _INT, _P]),
     "mlgnn_gemm_bf16_nt_workgroups": (_INT, [_I64, _I64, _INT]),
     "mlgnn_gemm_bf16_nt": (_INT, [_c.POINTER(_P), _c.POINTER(_P), _c.POINTER(_I64), _c.POINTER(_I64), _c.POINTER(_I64),

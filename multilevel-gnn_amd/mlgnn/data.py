@@ -142,9 +142,12 @@ class SyntheticTCGA(torch.utils.data.Dataset):
     ``node_num`` gene nodes with one scalar value each, ONE topology shared by all patients
     (``multiloader.py:687-691``) with weighted edges incl. -1/+1 cross-omics edges (:664-671), a
     sorted gene -> (pathway, omics) membership table of ``n_members`` entries over 146 x 3 segments,
-    a binary label that depends on a few pathway nodes (so that training can reduce the loss)."""
+    a binary label that depends on a few pathway nodes (so that training can reduce the loss).
+    ``with_raw_data=True``: a sample also carries ``raw_data [1, n_members]``, the value of every member's gene node (0
+    for a member without a node) -- the field ``multiloader.py:83-86`` fills for the models without a gene graph
+    (PathCNN); drawn from the same tensors, so everything else is unchanged."""
 
-    def __init__(self, n_patients, node_num=5135, n_edges=60000, n_members=25015, pca_dim=2, seed=0):
+    def __init__(self, n_patients, node_num=5135, n_edges=60000, n_members=25015, pca_dim=2, seed=0, with_raw_data=False):
         gen = torch.Generator().manual_seed(seed)
         self.node_num, self.NN = node_num, node_num * 3
         NN = self.NN
@@ -164,15 +167,20 @@ class SyntheticTCGA(torch.utils.data.Dataset):
         signal = self.x[:, self.gene_pca_match.clamp(min=0)[:200], 0].mean(1)
         self.labels = (signal > signal.median()).long()
         self.age = torch.rand(n_patients, generator=gen)
+        self.with_raw_data = bool(with_raw_data)
 
     def __len__(self):
         return self.x.shape[0]
 
     def __getitem__(self, i):
         y = torch.tensor([1.0 - float(self.labels[i]), float(self.labels[i])])
-        return Data(x=self.x[i], edge_index=self.edge_index, edge_attr=self.edge_attr, y=y, age=float(self.age[i]),
-                    gene_pca_match=self.gene_pca_match[None, :], raw_indice=self.raw_indice[None, :],
-                    node_size=self.NN, pathway_node_attr=torch.zeros(1, 146, 3 * self.pca_dim))
+        d = Data(x=self.x[i], edge_index=self.edge_index, edge_attr=self.edge_attr, y=y, age=float(self.age[i]),
+                 gene_pca_match=self.gene_pca_match[None, :], raw_indice=self.raw_indice[None, :],
+                 node_size=self.NN, pathway_node_attr=torch.zeros(1, 146, 3 * self.pca_dim))
+        if self.with_raw_data:
+            present = self.gene_pca_match >= 0
+            d.raw_data = (self.x[i, self.gene_pca_match.clamp(min=0), 0] * present)[None, :]
+        return d
 
     def get_weight_balance(self, indexs, batch_size, weight_power=1.0):
         """``MyData.get_weight_balance`` (multiloader.py:321-326): per-class weights repeated per batch row."""

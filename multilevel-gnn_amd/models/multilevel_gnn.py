@@ -14,6 +14,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from mlgnn.conv import module_conv2d
 from mlgnn.dense import linear as dense_linear
 from mlgnn.project import segment_project
 from mlgnn.sage import flatten_channel_last, linear_act, linear_act_supported, node_embed, node_embed_supported
@@ -24,7 +25,8 @@ class HeadConv2d(nn.Conv2d):
     """``nn.Conv2d`` of the pathway head (multilevel_gnn.py:98-104) with the same parameters and ``state_dict`` keys.  A
     1x1 kernel (the reference's configs: ``conv_kernel_list: [1, 1]``) is a product over the channel dimension and runs
     as one GEMM on the channel-last view instead of through the convolution library, whose first call per shape
-    searches / compiles solvers at run time."""
+    searches / compiles solvers at run time.  A k = 3 or 5 kernel with padding k // 2 runs on the direct-convolution
+    kernels (:func:`mlgnn.conv.module_conv2d`); anything else is the stock module."""
 
     # MLGNN_HEAD_CONV2D=1: always the convolution library (tools/abort_repro.py: the configuration in which two full
     # test runs of round 2 aborted)
@@ -44,6 +46,8 @@ class HeadConv2d(nn.Conv2d):
                 y = torch.nn.functional.linear(xr, w2, self.bias)
                 y = torch.relu(y) if relu else y
             return y.permute(0, 3, 1, 2)
+        if not self.FORCE_LIBRARY and self.kernel_size != (1, 1):
+            return module_conv2d(self, x, relu)           # k = 3, 5: the direct-convolution kernels (mlgnn/conv.py)
         y = super().forward(x)
         return torch.relu(y) if relu else y
 

@@ -50,6 +50,7 @@ DEFAULTS = dict(
     conv_channel_list=[32, 64], conv_kernel_list=[1, 1], embedding_init_type="xavier", emb_val=0.01,
     input_drop=None, input_emb_drop=None, gnn_dropout=0.0, device_num=1, edge_type="grnboost2",
     reduction_method="linear_projection", freeze_mutual_select_init=False, random_state=12345, remain_all_tf=False,
+    pathcnn_kernel_size=3, more_conv=False,
 )
 
 
@@ -134,7 +135,7 @@ def run(args):
     torch.manual_seed(args.seed)
 
     small = dict(node_num=60, n_edges=500, n_members=900) if args.small else {}
-    data = SyntheticTCGA(args.patients, pca_dim=args.pca_dim, seed=args.seed, **small)
+    data = SyntheticTCGA(args.patients, pca_dim=args.pca_dim, seed=args.seed, with_raw_data=(args.model == "pathcnn"), **small)
     n_train = int(0.7 * len(data)) // (args.batch_size * world) * (args.batch_size * world)
     idx = torch.randperm(len(data), generator=torch.Generator().manual_seed(args.seed)).tolist()
     train_idx, valid_idx = idx[:n_train][rank::world], idx[n_train:]
@@ -143,6 +144,11 @@ def run(args):
     valid_loader = DataLoader(torch.utils.data.Subset(data, valid_idx), batch_size=args.batch_size, shuffle=False,
                               num_workers=args.num_workers)
 
+    if args.model == "pathcnn" and not args.learnable_pca:
+        # the synthetic cohort has no precomputed PCA image (pathway_node_attr is all zeros): the image is the learnable
+        # projection of raw_data
+        logging.info("pathcnn on the synthetic cohort: learnable_pca switched on")
+        args.learnable_pca = True
     model = get_model(args.model)(args)
     if args.model == "multilevel_gnn":
         if args.small:                      # shrink the hard-coded TCGA sizes (tests)
@@ -152,6 +158,11 @@ def run(args):
         model.set_pca_params(torch.randn(data.n_members, args.pca_dim) * 0.05, mask)
         model.set_info_mask(mask[:, None].clone())
         model.set_pathway_indexs(data.raw_indice.to(device))
+    elif args.model == "pathcnn":
+        mask = torch.ones(data.n_members)
+        model.set_pca_params(torch.randn(data.n_members, args.pca_dim) * 0.05, mask)
+        model.set_info_mask(mask[:, None].clone())
+        model.set_pathway_indexs((data.raw_indice // 3).to(device))
     model.to(device)
     broadcast_parameters(model)
     # train.py:112-114 (Adam + StepLR) and :63-66 (clip_grad_norm_(20) + step) as ONE fused update of the flat buffer
