@@ -962,6 +962,32 @@ int mlgnn_conv2d_bwd(const float* grad_y, const float* x, const float* w, const 
                      int64_t W, int64_t Cin, int64_t Cout, int64_t k, void* stream);
 
 /*
+ * The pooled pathway readout (csrc/pool_flatten.hip), fp32: max_pool2d over (ph, pw) windows (stride = window, no padding,
+ * floor mode) of a channel-last image, dropout, flatten in NCHW order and one appended column; one launch per direction.
+ *   x [B, H, W, C]: the memory of a channel-last [B, C, H, W] tensor.  Ho = H / ph, Wo = W / pw (the remainder rows and
+ *   columns are dropped).  out [B, C * Ho * Wo + (extra ? 1 : 0)]: out[b, (c * Ho + ho) * Wo + wo] = window maximum
+ *   * keep * keep_scale, out[b, C * Ho * Wo] = extra[b].
+ *   keep [B, C * Ho * Wo] bytes or NULL (then keep_scale is not used): the dropout flags, drawn by the caller; it multiplies.
+ *   extra [B] or NULL: the appended column (the age).
+ *   winner [B, C * Ho * Wo] bytes: the position dh * pw + dw of the maximum inside its window, ATen's rule (scan h then w
+ *   from the first element; a later element wins when it is greater or NaN).  NULL in the forward: not wanted
+ *   (inference); NULL in the backward only when ph * pw == 1.
+ *   mlgnn_pool_flatten_bwd: grad_out rows of C * Ho * Wo + (has_extra ? 1 : 0) floats; grad_x [B, H, W, C], every element
+ *   written exactly once: the winner gets grad_out * keep * keep_scale, everything else (the dropped rows and columns
+ *   too) 0.
+ * Copies and at most one fp32 multiply, no atomics: bitwise reproducible.  Shapes (mlgnn_pool_flatten_supported):
+ * 1 <= ph, pw <= 16, H >= ph, W >= pw, C >= 1, x and out (counted with the extra column) below 4 GiB; MLGNN_E_SHAPE for
+ * anything else (shape errors are reported before NULL operands); B = 0 is a no-op.
+ */
+int mlgnn_pool_flatten_supported(int64_t B, int64_t H, int64_t W, int64_t C, int64_t ph, int64_t pw);
+int mlgnn_pool_flatten_fwd(const float* x, const uint8_t* keep, float keep_scale, const float* extra,
+                           float* out, uint8_t* winner,
+                           int64_t B, int64_t H, int64_t W, int64_t C, int64_t ph, int64_t pw, void* stream);
+int mlgnn_pool_flatten_bwd(const float* grad_out, const uint8_t* keep, float keep_scale, const uint8_t* winner,
+                           float* grad_x, int64_t has_extra,
+                           int64_t B, int64_t H, int64_t W, int64_t C, int64_t ph, int64_t pw, void* stream);
+
+/*
  * Measurement aid (bench.py: the box's streaming ceiling next to the 8 TB/s spec peak): dst = src, 16 bytes per lane,
  * non_temporal != 0: non-temporal loads and stores.  bytes a multiple of 16, 16-byte aligned pointers.
  */

@@ -29,6 +29,7 @@ from mlgnn.dense import linear
 from mlgnn.mha import mha_attention, mha_supported
 from mlgnn.norm import layer_norm_act, layer_norm_act_fork
 from mlgnn.pool import global_pool
+from mlgnn.pool_flatten import module_pool_flatten
 from .gcn_lib.sparse.torch_vertex import GENConv
 from .gcn_lib.sparse.torch_nn import norm_layer
 
@@ -317,9 +318,10 @@ class DeeperGCN(torch.nn.Module):
                 prow = prow.reshape(-1, self.pathway_num, h.shape[-1])
                 if self.feature_drop_flag:
                     prow = self.feature_drop(prow)
-                h_graph = torch.flatten(F.max_pool1d(prow.transpose(1, 2), 4), start_dim=1)
-                if self.pre_concat_age:
-                    h_graph = torch.cat([h_graph, age[:, None]], dim=-1)
+                # (max_pool1d(prow^T, 4), flatten, cat with age: prow [B, P, d] is the channel-last image
+                # [B, C = d, H = P, W = 1] under the window (4, 1); feature_drop acts before the pool, so no dropout here)
+                h_graph = module_pool_flatten((4, 1), None, prow.transpose(1, 2).unsqueeze(-1),
+                                              age if self.pre_concat_age else None)
                 h_graph = self.readout_func(h_graph)
         else:
             h_graph = global_pool(h, batch, self.graph_pooling, n_graphs)

@@ -16,8 +16,9 @@ import torch.nn as nn
 
 from mlgnn.conv import module_conv2d
 from mlgnn.dense import linear as dense_linear
+from mlgnn.pool_flatten import module_pool_flatten
 from mlgnn.project import segment_project
-from mlgnn.sage import flatten_channel_last, linear_act, linear_act_supported, node_embed, node_embed_supported
+from mlgnn.sage import linear_act, linear_act_supported, node_embed, node_embed_supported
 from .gcn_lib.sparse.torch_vertex import GraphConv
 
 
@@ -159,12 +160,9 @@ class MultilevelGNN(nn.Module):
         if len(self.used_omics) != N_OMICS:
             cols = [c for o in self.used_omics for c in range(int(o) * self.pca_dim, (int(o) + 1) * self.pca_dim)]
             x = x[:, :, :, cols]
-        if (self.pathway_pool_dim, self.pca_pool_dim) != (1, 1):     # (a 1 x 1 window is the identity: kirc.yaml)
-            x = self.pooling(x)
-        x = self.drop1(x)
-        x = flatten_channel_last(x)                      # (:277 torch.flatten; a tiled transpose when x is channel-last)
-        if self.args.use_age:
-            x = torch.cat([x, age[:, None]], dim=-1)
+        # (:274-279 max-pool, drop1, torch.flatten, cat with age: one launch when x is channel-last; a 1 x 1 window is
+        # the identity, kirc.yaml, and still fuses the rest)
+        x = module_pool_flatten(self.pooling, self.drop1, x, age if self.args.use_age else None)
         # (the first Linear reads a [B, 64 * 146 * 3k] row per sample: a stream over its weight, mlgnn.dense.linear)
         for i, layer in enumerate(self.head):
             x = dense_linear(x, layer.weight, layer.bias) if (i == 0 and type(layer) is nn.Linear) else layer(x)

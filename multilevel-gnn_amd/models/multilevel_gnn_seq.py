@@ -10,6 +10,8 @@ omics selection is the ``only_mrna_pred`` switch (first two columns of the conv 
 import torch
 import torch.nn as nn
 
+from mlgnn.pool_flatten import module_pool_flatten
+
 from .multilevel_gnn import N_OMICS, N_PATHWAYS, HeadConv2d, MultilevelGNN
 
 
@@ -43,16 +45,12 @@ class PathwayHeadSeq(nn.Module):
     def forward(self, x, age=None):
         for layer in self.conv_model:
             x = layer(x)
+        age = age if self.args.use_age else None
         if not self.args.only_mrna_pred:
-            x = self.pooling(x)
-            x = self.drop1(x)
-            x = torch.flatten(x, start_dim=1)
+            x = module_pool_flatten(self.pooling, self.drop1, x, age)
         else:
             x = x[:, :, :, :2]           # literal 2 in the reference (:62): the mRNA block at pca_dim = 2
-            x = self.pooling(x)
-            x = torch.flatten(x, start_dim=1)
-        if self.args.use_age:
-            x = torch.cat([x, age[:, None]], dim=-1)
+            x = module_pool_flatten(self.pooling, None, x, age)          # (a sliced view: the torch lines)
         return self.head(x)
 
 

@@ -16,8 +16,8 @@ import torch.nn as nn
 
 from mlgnn.conv import PathConv2d
 from mlgnn.dense import linear as dense_linear
+from mlgnn.pool_flatten import module_pool_flatten
 from mlgnn.project import segment_project
-from mlgnn.sage import flatten_channel_last
 
 N_PATHWAYS = 146          # hard-coded in the reference's forward (:101,105) and head sizing (:82)
 N_OMICS = 3
@@ -118,12 +118,12 @@ class PathCNN(nn.Module):
             x = self.pre_linear(x)
         age = input_batch.age
         x = self._convs(x)
-        x = self.pooling(x)
+        age = age.to(x.dtype)
         if self.pca_compare:                                 # (:115-119: flatten -> pre_linear, no dropout)
-            x = self.pre_linear(flatten_channel_last(x))
-        else:
-            x = flatten_channel_last(self.drop1(x))
-        x = torch.cat([x, age[:, None].to(x.dtype)], dim=-1)
+            x = self.pre_linear(module_pool_flatten(self.pooling, None, x))
+            x = torch.cat([x, age[:, None]], dim=-1)
+        else:                                                # max-pool, drop1, flatten, cat with age: one launch
+            x = module_pool_flatten(self.pooling, self.drop1, x, age)
         # (the first Linear reads a [B, 64 * (146 / pool) * (3k / pool) + 1] row per sample: mlgnn.dense.linear)
         for i, layer in enumerate(self.head):
             x = dense_linear(x, layer.weight, layer.bias) if (i == 0 and type(layer) is nn.Linear) else layer(x)

@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from mlgnn.pool_flatten import module_pool_flatten
 from mlgnn.project import segment_project
 from .diff_pooling import DiffPool
 from .multilevel_gnn import N_OMICS, N_PATHWAYS, MultilevelGNN
@@ -212,12 +213,12 @@ class VAE(_PretrainBase):
             x = x.permute(0, 3, 2, 1).reshape(-1, args.pathway_num, width)
             x, link, ent = self.diff_pooling(x, self.get_pathway_adj().to(x.device))
             x = self.drop1(x.reshape(b, -1))
+            if args.use_age:
+                x = torch.cat([x, age[:, None]], dim=-1)
         else:
-            if args.reorder_type != "no_pooling":
-                x = self.pooling(x)
-            x = torch.flatten(self.drop1(x), start_dim=1)
-        if args.use_age:
-            x = torch.cat([x, age[:, None]], dim=-1)
+            # max-pool (the 1 x 1 window for 'no_pooling'), drop1, flatten, cat with age: one launch
+            x = module_pool_flatten(self.pooling if args.reorder_type != "no_pooling" else None, self.drop1, x,
+                                    age if args.use_age else None)
         return self.head(x), pca_feature, link, ent
 
     def reconstruct_head(self, args):

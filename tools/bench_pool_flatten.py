@@ -1,0 +1,120 @@
+#!/usr/bin/env python3
+"""The pooled pathway readout (max-pool, dropout, flatten, age) at the shipped configurations' shapes, fp32:
+
+  gbm : B = 32, C = 64, 146 x 6 image, window 4 x 2, age      (config/gbm.yaml)
+  lgg : B = 64, C = 64, 146 x 9 image, window 4 x 2, age      (config/lgg.yaml)
+  kirc: B = 64, C = 64, 146 x 9 image, window 1 x 1           (config/kirc.yaml)
+
+Times, with device events (mean of 50 runs after 10 warm-up runs, one process), the op ``mlgnn.pool_flatten`` against the
+torch lines it replaces (``MaxPool2d``, ``Dropout(0.25)`` in training mode, ``flatten_channel_last``, ``cat`` with age --
+what ``MLGNN_POOL_FLATTEN=0`` selects; here the switch ``mlgnn.pool_flatten.ENABLED`` is flipped inside one process so
+that both legs share the session), forward and forward + backward.  With ``--steps`` it also runs the gbm- and
+kirc-shape training step of tools/bench_tcga.py in child processes, once per switch setting, each under its own time
+limit.  Writes profiles/pool_flatten.json.  Development tool; run it under a time limit of its own
+(``timeout -k 10 600 python tools/bench_pool_flatten.py --steps``)."""
+import argparse
+import importlib
+import json
+import os
+import subprocess
+import sys
+
+import torch
+import torch.nn as nn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
+pf = importlib.import_module("mlgnn.pool_flatten")  # noqa: E402
+
+SHAPES = {"gbm": (32, 64, 146, 6, (4, 2), True), "lgg": (64, 64, 146, 9, (4, 2), True), "kirc": (64, 64, 146, 9, (1, 1), False)}
+
+
+def timed(fn, warmup, iters):
+    for _ in range(warmup):
+        fn()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    s.record()
+    for _ in range(iters):
+        fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / iters
+
+
+def bench_op(name, dev, warmup, iters):
+    B, C, H, W, window, with_age = SHAPES[name]
+    torch.manual_seed(1)
+    x = torch.randn(B, H, W, C, device=dev).permute(0, 3, 1, 2).requires_grad_()        # channel-last, as the models have it
+    age = torch.rand(B, device=dev) if with_age else None
+    pool, drop = nn.MaxPool2d(window), nn.Dropout(0.25)                                  # training mode: the flags are drawn
+    n = C * (H // window[0]) * (W // window[1])
+    cot = torch.randn(B, n + int(with_age), device=dev)
+
+    def forward():
+        return pf.module_pool_flatten(pool, drop, x, age)
+
+    def step():
+        x.grad = None
+        torch.autograd.backward(forward(), cot)
+
+    # bytes the op has to move: x in, out + winner + keep out; the backward: grad_out + winner + keep in, grad_x out
+    per = 5 + int(window != (1, 1))                                                       # (no winner bytes at 1 x 1)
+    entry = {"shape": name, "B": B, "C": C, "H": H, "W": W, "window": list(window), "age": with_age,
+             "mbytes_per_direction": (4 * B * C * H * W + per * B * n) / 1e6}
+    for leg, on in (("hip", True), ("torch", False)):
+        pf.ENABLED = on
+        before = dict(pf.POOL_STATS)
+        entry[leg] = {"forward_ms": timed(forward, warmup, iters), "forward_backward_ms": timed(step, warmup, iters)}
+        assert pf.POOL_STATS["torch" if on else "hip"] == before["torch" if on else "hip"]
+    pf.ENABLED = True
+    entry["speedup_over_torch"] = {k: entry["torch"][k] / entry["hip"][k] for k in entry["hip"]}
+    return entry
+
+
+def bench_step(shape, steps, warmup, limit):
+    """tools/bench_tcga.py in a fresh process per switch setting."""
+    entry = {"shape": shape}
+    for leg, flag in (("hip", "1"), ("torch", "0")):
+        cmd = [sys.executable, os.path.join(ROOT, "tools", "bench_tcga.py"), "--shape", shape, "--steps", str(steps),
+               "--warmup", str(warmup)]
+        run = subprocess.run(cmd, env=dict(os.environ, MLGNN_POOL_FLATTEN=flag), timeout=limit, check=True,
+                             stdout=subprocess.PIPE, text=True)
+        line = [ln for ln in run.stdout.splitlines() if ln.startswith("{")][-1]
+        entry[leg] = {"train_step_ms": json.loads(line)["ms_per_step"]}
+    entry["speedup_over_torch"] = entry["torch"]["train_step_ms"] / entry["hip"]["train_step_ms"]
+    return entry
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--steps", action="store_true", help="also time the gbm- and kirc-shape training step (bench_tcga.py)")
+    ap.add_argument("--step-limit", type=int, default=240, help="seconds each training-step process may take")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pool_flatten.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_pool_flatten.py needs the GPU: there is no CPU path to time")
+    dev = torch.device("cuda:0")
+    result = {"workload": "pooled pathway readout: max-pool, Dropout(0.25) (training), flatten, age; fp32, channel-last input",
+              "timing": "device events, mean of %d runs after %d warm-up runs; 'torch' = the replaced lines "
+                        "(MLGNN_POOL_FLATTEN=0)" % (a.iters, a.warmup),
+              "device": torch.cuda.get_device_name(0), "op": [], "train_step": []}
+    for name in ("gbm", "lgg", "kirc"):
+        entry = bench_op(name, dev, a.warmup, a.iters)
+        result["op"].append(entry)
+        print(json.dumps(entry), flush=True)
+    if a.steps:
+        for shape in ("gbm", "kirc"):
+            entry = bench_step(shape, 20, 5, a.step_limit)
+            result["train_step"].append(entry)
+            print(json.dumps(entry), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(result, fh, indent=1)
+        fh.write("\n")
+
+
+if __name__ == "__main__":
+    main()
