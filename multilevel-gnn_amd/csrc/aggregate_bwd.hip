@@ -645,7 +645,7 @@ __global__ __launch_bounds__(1024) void reduce_partials_quads_kernel(const float
 
 void launch_reduce_partials(const float* ws, float* out, int nblk, int cols, hipStream_t stream, bool accumulate) {
   const int acc = accumulate ? 1 : 0;
-  const bool vec_ok = cols % 4 == 0 && ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  const bool vec_ok = cols % 4 == 0 && aligned(ws, out);
   if (cols >= 4096 && vec_ok) {
     const int quads = cols / 4;
     hipLaunchKernelGGL(reduce_partials_wide_kernel, dim3((quads + kRedWQuads - 1) / kRedWQuads),
@@ -753,13 +753,10 @@ static int csr_aggregate_bwd_impl(const void* grad_out, const void* x, const voi
   a.cap = split ? hub->cap : kNoCap; a.vrows = nullptr; a.vcount = nullptr;
   if (add_root && learn_t) return MLGNN_E_MODE;       // `out` must be the bare aggregate for d/dt
 
-  const bool al = aligned16(grad_out) && aligned16(grad_x) && (!x || aligned16(x)) &&
-                  (!out || aligned16(out)) && (!aux || aligned16(aux)) && (!argmax || aligned16(argmax)) &&
-                  (!efull || aligned16(efull)) && (!grad_efull || aligned16(grad_efull)) &&
-                  (!eu || aligned16(eu)) && (!ev || aligned16(ev));
+  const bool al = aligned(grad_out, grad_x, x, out, aux, argmax, efull, grad_efull, eu, ev);
   {
-    const uintptr_t need = rk >= 4 ? 16 : 4 * (uintptr_t)(rk > 0 ? rk : 1);     // vector loads of the edge scalar table
-    if (ew_t && (reinterpret_cast<uintptr_t>(ew_t) % need) != 0) return MLGNN_E_ALIGN;
+    // vector loads of the edge scalar table
+    if (!(rk >= 4 ? aligned<16>(ew_t) : rk == 2 ? aligned<8>(ew_t) : aligned<4>(ew_t))) return MLGNN_E_ALIGN;
   }
   const int vec = bf16 ? ((d % 8 == 0 && al) ? 8 : 1) : ((d % 4 == 0 && al) ? 4 : 1);
   const dim3 block(kBlock);
@@ -776,20 +773,19 @@ static int csr_aggregate_bwd_impl(const void* grad_out, const void* x, const voi
     if (bf16 || vec != 4 || d != ((int64_t)4 << a.lpr_log2) || split || learn_t || wide) return MLGNN_E_MODE;
     if (!ln->h || !ln->mean || !ln->rstd || !ln->gamma || !ln->beta || !ln->grad_gamma_beta || !ln->workspace) return MLGNN_E_NULL;
     if (ln->workspace_floats < (int64_t)nblk * 2 * d) return MLGNN_E_WORKSPACE;
-    if (!aligned16(ln->h) || !aligned16(ln->gamma) || !aligned16(ln->beta) || (ln->grad_extra && !aligned16(ln->grad_extra)))
-      return MLGNN_E_ALIGN;
+    if (!aligned(ln->h, ln->gamma, ln->beta, ln->grad_extra)) return MLGNN_E_ALIGN;
     a.ln_h = ln->h; a.ln_mean = ln->mean; a.ln_rstd = ln->rstd; a.ln_gamma = ln->gamma; a.ln_beta = ln->beta;
     a.ln_extra = ln->grad_extra; a.ln_rowmax = ln->row_max; a.ln_ws = ln->workspace; a.ln_relu = ln->relu;
   }
   a.gt = nullptr; a.spread = nullptr;
   if (have_shift) {
-    if (!aligned16(grad_shifted) && vec != 1) return MLGNN_E_ALIGN;
+    if (!aligned(grad_shifted) && vec != 1) return MLGNN_E_ALIGN;
     a.gt = grad_shifted; a.spread = shift_flag;
   }
   if (want_shift) {
     float* base = workspace + part_floats;               // 16-byte aligned: part_floats is a multiple of 4 when d % 4 == 0
     if (!rowptr) return MLGNN_E_NULL;
-    if ((reinterpret_cast<uintptr_t>(base) & 15) == 0 || vec == 1) {
+    if (aligned(base) || vec == 1) {
       ShiftArgs sa;
       sa.go = grad_out; sa.lse = aux; sa.rowptr = rowptr; sa.N = (int)N; sa.d = (int)d; sa.lpr_log2 = a.lpr_log2;
       sa.spread = reinterpret_cast<int*>(base); sa.gt = base + 4;
@@ -811,7 +807,7 @@ static int csr_aggregate_bwd_impl(const void* grad_out, const void* x, const voi
   a.slot8 = nullptr;
   if (want_slots && rowptr) {
     float* base = workspace + part_floats;
-    if ((reinterpret_cast<uintptr_t>(base) & 15) == 0) {
+    if (aligned(base)) {
       SlotArgs sa;
       sa.argmax = argmax; sa.rowptr = rowptr; sa.N = (int)N; sa.d = (int)d;
       sa.spread = reinterpret_cast<int*>(base); sa.slot8 = reinterpret_cast<uint8_t*>(base + 4);
@@ -875,8 +871,10 @@ static int csr_aggregate_bwd_impl(const void* grad_out, const void* x, const voi
   static const bool short_on = [] { const char* e = getenv("MLGNN_SHORT_ROWS"); return !(e && e[0] == '0'); }();
   if (short_on && !bf16 && vec == 4 && (mode == M_IDENTITY || mode == M_WEIGHTED) && ag == A_SUM && short_width_ok(d) &&
       rk == 0 && !ln && !add_root && !wide && !grad_efull && (!a.mean || rowptr)) {
-    MLGNN_SHORT_DISPATCH(csr_short_bwd_kernel, d, mode == M_WEIGHTED, static_cast<const float*>(grad_out), rowptr_t, col_t,
-                         ew_t, rowptr, static_cast<float*>(grad_x), (int)N, a.mean, a.cap);
+    if (!launch_short([](auto l, auto w) { return &csr_short_bwd_kernel<l(), w()>; }, d, mode == M_WEIGHTED, N, s,
+                      static_cast<const float*>(grad_out), rowptr_t, col_t, ew_t, rowptr, static_cast<float*>(grad_x), (int)N,
+                      a.mean, a.cap))
+      return MLGNN_E_SHAPE;
     launched_blocks = 0;
   } else {
     run(a, 0, BC<false>{});

@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
+#include "launch.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
@@ -35,7 +36,6 @@ template <int MODE>
 __host__ __device__ constexpr int edge_scalars() { return MODE == M_WEIGHTED ? 1 : rank_of<MODE>(); }
 enum Aggr { A_SUM = 0, A_MAX = 2, A_SOFTMAX = 3, A_POWER = 4 };   // MEAN = SUM + epilogue flag
 
-template <int V> using IC = std::integral_constant<int, V>;
 template <typename T> struct TypeTag { using type = T; };
 template <bool V> using BC = std::integral_constant<bool, V>;
 
@@ -248,7 +248,6 @@ inline int pick_aggr(int aggr) {
 }
 
 inline bool is_gen_mode(int mode) { return mode >= M_GEN_NONE; }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // f(IC<MODE>, IC<AGGR>) for the valid (mode, aggregator) pairs
 template <int MODE, typename F>

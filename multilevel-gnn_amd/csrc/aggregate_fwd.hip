@@ -395,14 +395,11 @@ extern "C" int mlgnn_csr_aggregate_fwd(const void* x, const int32_t* rowptr, con
   const bool split = hub && hub->cap > 0 && col;
   a.cap = split ? hub->cap : kNoCap; a.vrows = nullptr; a.vcount = nullptr;
 
-  const bool al = aligned16(x) && aligned16(out) && (!efull || aligned16(efull)) &&
-                  (!aux || aligned16(aux)) && (!aux2 || aligned16(aux2)) && (!argmax || aligned16(argmax)) &&
-                  (!eu || aligned16(eu)) && (!ev || aligned16(ev));
+  const bool al = aligned(x, out, efull, aux, aux2, argmax, eu, ev);
   // the per-edge scalar table is read with 4 * rank byte loads (rank 2: float2, 4 / 8: float4) on every path
   {
     const int es = mode == M_WEIGHTED ? 1 : rank_of_mode(mode);
-    const uintptr_t need = es >= 4 ? 16 : 4 * (uintptr_t)(es > 0 ? es : 1);
-    if (ew && (reinterpret_cast<uintptr_t>(ew) % need) != 0) return MLGNN_E_ALIGN;
+    if (!(es >= 4 ? aligned<16>(ew) : es == 2 ? aligned<8>(ew) : aligned<4>(ew))) return MLGNN_E_ALIGN;
   }
   const bool bf16 = dtype == MLGNN_DTYPE_BF16;
   // channels per lane: 16-byte accesses (4 x fp32 / 8 x bf16) when the width allows, scalar otherwise
@@ -443,8 +440,9 @@ extern "C" int mlgnn_csr_aggregate_fwd(const void* x, const int32_t* rowptr, con
   static const bool short_on = [] { const char* e = getenv("MLGNN_SHORT_ROWS"); return !(e && e[0] == '0'); }();
   if (short_on && !bf16 && vec == 4 && (mode == M_IDENTITY || mode == M_WEIGHTED) && ag == A_SUM && short_width_ok(d) &&
       !aux && !aux2 && !argmax && !row_max && !add_root && !wide) {
-    MLGNN_SHORT_DISPATCH(csr_short_fwd_kernel, d, mode == M_WEIGHTED, static_cast<const float*>(x), rowptr, col, ew,
-                         static_cast<float*>(out), (int)N, a.mean, a.cap);
+    if (!launch_short([](auto l, auto w) { return &csr_short_fwd_kernel<l(), w()>; }, d, mode == M_WEIGHTED, N, s,
+                      static_cast<const float*>(x), rowptr, col, ew, static_cast<float*>(out), (int)N, a.mean, a.cap))
+      return MLGNN_E_SHAPE;
   } else {
     run(a, grid, BC<false>{});
   }

@@ -124,21 +124,14 @@ __global__ __launch_bounds__(kShortBlock) void csr_short_bwd_kernel(const float*
 // d in {4, 8, 16, 32, 64}: lane groups of 1 .. 16 lanes
 inline bool short_width_ok(int64_t d) { return d == 4 || d == 8 || d == 16 || d == 32 || d == 64; }
 
-#define MLGNN_SHORT_DISPATCH(KERNEL, d_, weighted_, ...)                                        \
-  do {                                                                                          \
-    const dim3 sg_(short_grid(N, kShortBlock / (int)((d_) / 4))), sb_(kShortBlock);             \
-    switch ((int)((d_) / 4)) {                                                                  \
-      case 1: if (weighted_) hipLaunchKernelGGL((KERNEL<1, true>), sg_, sb_, 0, s, __VA_ARGS__);  \
-              else hipLaunchKernelGGL((KERNEL<1, false>), sg_, sb_, 0, s, __VA_ARGS__); break;    \
-      case 2: if (weighted_) hipLaunchKernelGGL((KERNEL<2, true>), sg_, sb_, 0, s, __VA_ARGS__);  \
-              else hipLaunchKernelGGL((KERNEL<2, false>), sg_, sb_, 0, s, __VA_ARGS__); break;    \
-      case 4: if (weighted_) hipLaunchKernelGGL((KERNEL<4, true>), sg_, sb_, 0, s, __VA_ARGS__);  \
-              else hipLaunchKernelGGL((KERNEL<4, false>), sg_, sb_, 0, s, __VA_ARGS__); break;    \
-      case 8: if (weighted_) hipLaunchKernelGGL((KERNEL<8, true>), sg_, sb_, 0, s, __VA_ARGS__);  \
-              else hipLaunchKernelGGL((KERNEL<8, false>), sg_, sb_, 0, s, __VA_ARGS__); break;    \
-      default: if (weighted_) hipLaunchKernelGGL((KERNEL<16, true>), sg_, sb_, 0, s, __VA_ARGS__); \
-               else hipLaunchKernelGGL((KERNEL<16, false>), sg_, sb_, 0, s, __VA_ARGS__); break;  \
-    }                                                                                           \
-  } while (0)
+// Launches kernel_of(IC<LPR>{}, BC<WEIGHTED>{}) over the N rows on stream s; false, and no launch, when d / 4 is no LPR.
+template <class KernelOf, class... Args>
+inline bool launch_short(KernelOf&& kernel_of, int64_t d, bool weighted, int64_t N, hipStream_t s, Args... args) {
+  return dispatch_int<1, 2, 4, 8, 16>((int)(d / 4), [&](auto l) {
+    const dim3 grid(short_grid(N, kShortBlock / l())), block(kShortBlock);
+    if (weighted) hipLaunchKernelGGL(kernel_of(l, BC<true>{}), grid, block, 0, s, args...);
+    else hipLaunchKernelGGL(kernel_of(l, BC<false>{}), grid, block, 0, s, args...);
+  });
+}
 
 }  // namespace mlgnn

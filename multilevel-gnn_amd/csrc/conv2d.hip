@@ -23,6 +23,7 @@
 //     units, staging the x patch and the masked grad_y band per unit.  The bias gradient is the column sums of the
 //     staged band.  Partials go to the caller's workspace, a second launch adds them in column order.
 #include "common.h"
+#include "launch.h"
 #include "mlgnn.h"
 #include "tile_gemm.h"
 
@@ -338,11 +339,6 @@ WgradShape make_wgrad(const ConvShape& s, int64_t Cin, int64_t Cout) {
 
 int64_t wgrad_floats(const WgradShape& g) { return (int64_t)g.G * ((int64_t)g.ntp * 256 + kConvMaxC); }
 
-template <typename K>
-void allow_lds(K kernel, int bytes) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
 }  // namespace
 }  // namespace mlgnn
 
@@ -359,7 +355,7 @@ extern "C" int mlgnn_conv2d_fwd(const float* x, const float* w, const float* bia
   if (!x || !w || !y) return MLGNN_E_NULL;
   const ConvShape s = make_shape(B, H, W, Cin, Cout, k, Cin > Cout ? Cin : Cout, false, relu ? 1 : 0);
   const int lds = s.PR * s.PW * s.CS * 4;
-  allow_lds(&conv_kernel<false>, lds);
+  if (const hipError_t e = allow_dynamic_lds(&conv_kernel<false>, lds); e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(conv_kernel<false>, dim3((unsigned)(B * s.nb)), dim3(kBlock), lds, static_cast<hipStream_t>(stream),
                      x, (const float*)nullptr, w, bias, y, s);
   return (int)hipGetLastError();
@@ -389,7 +385,7 @@ extern "C" int mlgnn_conv2d_bwd(const float* grad_y, const float* x, const float
   if (grad_x != nullptr) {
     const ConvShape s = make_shape(B, H, W, Cout, Cin, k, cmax, false, 0);
     const int lds = s.PR * s.PW * s.CS * 4;
-    allow_lds(&conv_kernel<true>, lds);
+    if (const hipError_t e = allow_dynamic_lds(&conv_kernel<true>, lds); e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(conv_kernel<true>, dim3((unsigned)(B * s.nb)), dim3(kBlock), lds, st, grad_y, mask, w,
                        (const float*)nullptr, grad_x, s);
     const int rc = (int)hipGetLastError();
@@ -397,7 +393,7 @@ extern "C" int mlgnn_conv2d_bwd(const float* grad_y, const float* x, const float
   }
   if (want_w) {
     const int lds = (sw.PR * sw.PW * sw.CS + kConvBandPositions * g.GS + kConvBandPositions) * 4;
-    allow_lds(&conv_wgrad_kernel, lds);
+    if (const hipError_t e = allow_dynamic_lds(&conv_wgrad_kernel, lds); e != hipSuccess) return (int)e;
     const int groups = g.ntp / kConvTilesPerGroup;
     hipLaunchKernelGGL(conv_wgrad_kernel, dim3((unsigned)g.G, (unsigned)groups), dim3(kBlock), lds, st, x, grad_y, mask,
                        workspace, sw, g);

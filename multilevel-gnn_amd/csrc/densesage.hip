@@ -16,6 +16,7 @@
 // a fixed order (reduce_partials).  Limits: n <= 160, C <= 128, O <= 64; the adjacency gradient (pooled
 // levels below the first, where A itself was produced by DiffPool) additionally needs n <= 48.
 #include "common.h"
+#include "launch.h"
 #include "mlgnn.h"
 #include "tile_gemm.h"
 
@@ -304,8 +305,8 @@ extern "C" int mlgnn_dense_sage_fwd(const void* x, const void* adj, const void* 
   static size_t fwd_attr = 0;                   // (idempotent: a race only repeats the call)
   if (lds > fwd_attr) {
     const int most = (int)ds_fwd_lds_bytes(kDsMaxN, kDsMaxC, kDsMaxO);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_sage_fwd_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, most);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_sage_fwd_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, most);
+    if (const hipError_t e = allow_dynamic_lds(&dense_sage_fwd_kernel<float>, most); e != hipSuccess) return (int)e;
+    if (const hipError_t e = allow_dynamic_lds(&dense_sage_fwd_kernel<bf16_t>, most); e != hipSuccess) return (int)e;
     fwd_attr = (size_t)most;
   }
   if (dtype == MLGNN_DTYPE_BF16) hipLaunchKernelGGL(dense_sage_fwd_kernel<bf16_t>, dim3((unsigned)B), dim3(kDsBlock), lds, (hipStream_t)stream, a);
@@ -337,8 +338,8 @@ extern "C" int mlgnn_dense_sage_bwd(const void* grad_y, const void* y, const flo
   if (lds > bwd_attr) {
     const size_t most = ds_bwd_lds_bytes(kDsMaxN, kDsMaxC, kDsMaxO, false) > ds_bwd_lds_bytes(kDsMaxNAdj, kDsMaxC, kDsMaxO, true)
                             ? ds_bwd_lds_bytes(kDsMaxN, kDsMaxC, kDsMaxO, false) : ds_bwd_lds_bytes(kDsMaxNAdj, kDsMaxC, kDsMaxO, true);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_sage_bwd_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)most);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_sage_bwd_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)most);
+    if (const hipError_t e = allow_dynamic_lds(&dense_sage_bwd_kernel<float>, (int)most); e != hipSuccess) return (int)e;
+    if (const hipError_t e = allow_dynamic_lds(&dense_sage_bwd_kernel<bf16_t>, (int)most); e != hipSuccess) return (int)e;
     bwd_attr = most;
   }
   if (dtype == MLGNN_DTYPE_BF16) hipLaunchKernelGGL(dense_sage_bwd_kernel<bf16_t>, dim3((unsigned)B), dim3(kDsBlock), lds, s, a);

@@ -24,6 +24,7 @@
 // No atomics; every reduction is a fixed-order sum of per-workgroup partials: bitwise reproducible.
 // The split-K reduce is csrc/gemm_chain.hip; the fp32 three-term form of this chain is csrc/diffpool_large_f32.hip.
 #include "common.h"
+#include "launch.h"
 #include "gemm_chain.h"
 
 namespace mlgnn {
@@ -565,7 +566,7 @@ extern "C" int mlgnn_diffpool_large_fwd(const void* z, const void* adj, const vo
       (out_dtype != MLGNN_DTYPE_F32 && out_dtype != MLGNN_DTYPE_BF16)) return MLGNN_E_DTYPE;
   const DplLayout L = dpl_layout(N, K, C);
   if (workspace_bytes < (int64_t)L.total * B) return MLGNN_E_WORKSPACE;
-  if (((uintptr_t)z | (uintptr_t)adj | (uintptr_t)s_out | (uintptr_t)workspace | (uintptr_t)s_logits) & 15) return MLGNN_E_ALIGN;
+  if (!aligned(z, adj, s_out, workspace, s_logits)) return MLGNN_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
   unsigned char* ws = (unsigned char*)workspace;
   const int64_t WS = (int64_t)L.total;                // bytes between the per-graph workspaces (a multiple of 256)
@@ -674,8 +675,7 @@ extern "C" int mlgnn_diffpool_large_bwd(const void* z, const void* adj, const vo
       (grad_dtype != MLGNN_DTYPE_F32 && grad_dtype != MLGNN_DTYPE_BF16)) return MLGNN_E_DTYPE;
   const int64_t W = mlgnn_diffpool_large_bwd_workspace_bytes(N, K, C, adj_symmetric);
   if (workspace_bytes < W * B) return MLGNN_E_WORKSPACE;
-  if (((uintptr_t)s_logits | (uintptr_t)grad_logits | (uintptr_t)workspace | (uintptr_t)adj | (uintptr_t)grad_x |
-       (uintptr_t)grad_adj_out | (uintptr_t)grad_z) & 15) return MLGNN_E_ALIGN;
+  if (!aligned(s_logits, grad_logits, workspace, adj, grad_x, grad_adj_out, grad_z)) return MLGNN_E_ALIGN;
   const DplLayout L = dpl_layout(N, K, C);
   const int64_t WS = (int64_t)L.total;
   const int batch = (int)B;

@@ -10,6 +10,7 @@
 // backward of the bf16 chain (through their launchers in csrc/gemm_chain.h).
 // Reference: the same call, models/diff_pooling.py:59-65 on fp32 tensors.
 #include "common.h"
+#include "launch.h"
 #include "gemm_chain.h"
 
 namespace mlgnn {
@@ -181,8 +182,7 @@ extern "C" int mlgnn_diffpool_large_f32_fwd(const float* z, const float* adj, co
   if (!z || !adj || !s_logits || !s_out || !x_out || !adj_out || !scal_out || !stats || !workspace) return MLGNN_E_NULL;
   const Dpl32Layout L = dpl32_layout(N, K, C);
   if (workspace_bytes < (int64_t)L.total * B) return MLGNN_E_WORKSPACE;
-  if (((uintptr_t)z | (uintptr_t)adj | (uintptr_t)s_out | (uintptr_t)workspace | (uintptr_t)s_logits | (uintptr_t)x_out |
-       (uintptr_t)adj_out) & 15) return MLGNN_E_ALIGN;
+  if (!aligned(z, adj, s_out, workspace, s_logits, x_out, adj_out)) return MLGNN_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
   unsigned char* ws = (unsigned char*)workspace;
   const int64_t WS = (int64_t)L.total, W2 = WS / 2, W4 = WS / 4;
@@ -282,8 +282,7 @@ extern "C" int mlgnn_diffpool_large_f32_bwd(const float* adj, const float* s_log
   const Dpl32Bwd Wl = dpl32_bwd_layout(N, K, C, adj_symmetric);
   const int64_t W = (int64_t)Wl.total, Wh = W / 2, Wf = W / 4;
   if (workspace_bytes < W * B) return MLGNN_E_WORKSPACE;
-  if (((uintptr_t)s_logits | (uintptr_t)grad_logits | (uintptr_t)workspace | (uintptr_t)adj | (uintptr_t)grad_x |
-       (uintptr_t)grad_adj_out | (uintptr_t)grad_z | (uintptr_t)saved | (uintptr_t)grad_adj) & 15) return MLGNN_E_ALIGN;
+  if (!aligned(s_logits, grad_logits, workspace, adj, grad_x, grad_adj_out, grad_z, saved, grad_adj)) return MLGNN_E_ALIGN;
   const Dpl32Layout L = dpl32_layout(N, K, C);
   const int64_t WS = (int64_t)L.total, W2 = WS / 2, W4 = WS / 4;
   const int batch = (int)B, adj_batch = adj_batched ? batch : 1;

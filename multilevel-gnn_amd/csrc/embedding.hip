@@ -10,6 +10,7 @@
 // Layout: lane groups of d/4 lanes hold one cotangent row (float4 per lane), 64 / (d/4) rows per wave and load
 // instruction, four load instructions in flight; 64-bit row offsets (the cotangent of a 10 M-edge batch is 5 GB).
 #include "common.h"
+#include "launch.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
@@ -264,7 +265,7 @@ extern "C" int64_t mlgnn_table_grad_bytes(int64_t T, int64_t d) {
 extern "C" int mlgnn_table_grad_begin(const float* grad_out, int64_t rows, int64_t d, void* accumulator, void* stream) {
   if (rows <= 0 || d <= 0 || d % 4 != 0 || rows * d > ((int64_t)1 << 40)) return MLGNN_E_SHAPE;
   if (!grad_out || !accumulator) return MLGNN_E_NULL;
-  if (((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(accumulator)) & 15) != 0) return MLGNN_E_ALIGN;
+  if (!aligned(grad_out, accumulator)) return MLGNN_E_ALIGN;
   // at most `rows` winners add to one table entry: |sum| < rows * 2^bits must stay below 2^62
   int lg = 0;
   while (((int64_t)1 << lg) < rows + 1) ++lg;
@@ -300,7 +301,7 @@ extern "C" int mlgnn_embedding_bwd(const float* grad_e, const int32_t* perm, con
   if (T < 0 || T > INT32_MAX || d <= 0 || d % 4 != 0 || d > 4096) return MLGNN_E_SHAPE;
   if (T == 0) return 0;
   if (!grad_e || !perm || !rowptr || !grad_table) return MLGNN_E_NULL;
-  if (((reinterpret_cast<uintptr_t>(grad_e) | reinterpret_cast<uintptr_t>(grad_table)) & 15) != 0) return MLGNN_E_ALIGN;
+  if (!aligned(grad_e, grad_table)) return MLGNN_E_ALIGN;
   EmbArgs a;
   a.ge = grad_e; a.perm = perm; a.rowptr = rowptr; a.out = grad_table; a.T = (int)T; a.d = (int)d;
   a.lpr_log2 = lanes_per_row_log2(d, 4);
@@ -334,9 +335,7 @@ extern "C" int mlgnn_max_table_grad(const float* grad_out, const int32_t* argmax
                                     int64_t T, int accumulate, void* stream) {
   if (!mlgnn_max_table_grad_supported(N, d, T)) return MLGNN_E_SHAPE;
   if (!grad_out || !argmax || !rows_by_dst || !grad_table || !workspace) return MLGNN_E_NULL;
-  if (((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(argmax) | reinterpret_cast<uintptr_t>(workspace) |
-        reinterpret_cast<uintptr_t>(grad_table)) & 15) != 0)
-    return MLGNN_E_ALIGN;
+  if (!aligned(grad_out, argmax, workspace, grad_table)) return MLGNN_E_ALIGN;
   MaxTableArgs a;
   a.go = grad_out; a.argmax = argmax; a.rows_dst = rows_by_dst; a.partials = workspace;
   a.N = (int)N; a.d = (int)d; a.T = (int)T;
@@ -345,9 +344,7 @@ extern "C" int mlgnn_max_table_grad(const float* grad_out, const int32_t* argmax
   const size_t lds = (size_t)T * 1024 * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(max_table_grad_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 36 * 1024 * (int)sizeof(float));
-    if (e != hipSuccess) return (int)e;
+    if (const hipError_t e = allow_dynamic_lds(max_table_grad_kernel, 36 * 1024 * (int)sizeof(float)); e != hipSuccess) return (int)e;
     attr_set = true;
   }
   hipStream_t s = (hipStream_t)stream;
@@ -365,13 +362,11 @@ extern "C" int mlgnn_max_table_grad_by_type(const float* grad_out, const int32_t
   if (N <= 0 || N > INT32_MAX || T < 0 || T > INT32_MAX || d <= 0 || d % 4 != 0 || d > 4096) return MLGNN_E_SHAPE;
   if (T == 0) return 0;
   if (!grad_out || !argmax || !dst_sorted || !pos_sorted || !rowptr || !grad_table) return MLGNN_E_NULL;
-  if (((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(argmax) | reinterpret_cast<uintptr_t>(grad_table)) &
-       15) != 0)
-    return MLGNN_E_ALIGN;
+  if (!aligned(grad_out, argmax, grad_table)) return MLGNN_E_ALIGN;
   MaxTypeArgs a;
   a.go = grad_out; a.argmax = argmax; a.dst_s = dst_sorted; a.pos_s = pos_sorted; a.rowptr = rowptr; a.out = grad_table;
   a.rel_s = rel_sorted; a.slot8 = nullptr; a.spread = nullptr;
-  if (slots && rel_sorted && (reinterpret_cast<uintptr_t>(slots) & 15) == 0) {     // {int32 spread flag, 12 bytes, slots [N, d]}
+  if (slots && rel_sorted && aligned(slots)) {     // {int32 spread flag, 12 bytes, slots [N, d]}
     a.spread = static_cast<const int*>(slots);
     a.slot8 = static_cast<const uint8_t*>(slots) + 16;
   }

@@ -21,6 +21,7 @@
 // + E*H*4 (per-edge d logit, written once) + 2*N*d*4.
 #include <type_traits>
 #include "common.h"
+#include "launch.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
@@ -481,8 +482,6 @@ GatShape make_shape(int64_t N, int64_t H, int64_t C, float neg_slope, float act_
   return s;
 }
 
-template <int V> using IC = std::integral_constant<int, V>;
-
 template <typename F>
 void for_layout(const GatShape& s, F&& f) {
   if (s.C % 4 == 0) f(IC<4>{}, IC<1>{});
@@ -497,7 +496,6 @@ int stream_blocks(const GatShape& s) {
 }
 
 int64_t pad64(int64_t floats) { return (floats + 63) / 64 * 64; }
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 }  // namespace mlgnn
@@ -511,7 +509,7 @@ extern "C" int mlgnn_gat_scores(const float* z, const float* att_src, const floa
   if (!shape_ok(N, H, C)) return MLGNN_E_SHAPE;
   if (N == 0) return 0;
   if (!z || !att_src || !att_dst || !a_src || !a_dst) return MLGNN_E_NULL;
-  if (vec_of(C) == 4 && !(aligned16(z) && aligned16(att_src) && aligned16(att_dst))) return MLGNN_E_ALIGN;
+  if (vec_of(C) == 4 && !aligned(z, att_src, att_dst)) return MLGNN_E_ALIGN;
   const GatShape s = make_shape(N, H, C, 0.f, 1.f);
   hipStream_t st = static_cast<hipStream_t>(stream);
   for_layout(s, [&](auto vec, auto q) {
@@ -528,7 +526,7 @@ extern "C" int mlgnn_gat_aggregate_fwd(const float* z, const float* a_src, const
   if (!shape_ok(N, H, C) || E < 0 || E >= ((int64_t)1 << 31) || !(act_slope >= 0.f)) return MLGNN_E_SHAPE;
   if (N == 0) return 0;
   if (!z || !a_src || !a_dst || !rowptr || !y || !lse || (E > 0 && !col)) return MLGNN_E_NULL;
-  if (vec_of(C) == 4 && !(aligned16(z) && aligned16(y) && (!bias || aligned16(bias)))) return MLGNN_E_ALIGN;
+  if (vec_of(C) == 4 && !aligned(z, y, bias)) return MLGNN_E_ALIGN;
   const GatShape s = make_shape(N, H, C, negative_slope, act_slope);
   const GatFwdArgs a{z, a_src, a_dst, bias, rowptr, col, y, lse, row_max};
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -559,9 +557,8 @@ extern "C" int mlgnn_gat_aggregate_bwd(const float* grad_y, const float* y, cons
       (E > 0 && (!col_t || !pos_t)) || (!grad_att_src) != (!grad_att_dst))
     return MLGNN_E_NULL;
   if (workspace_floats < mlgnn_gat_bwd_workspace_floats(N, E, H, C)) return MLGNN_E_WORKSPACE;
-  if (!aligned16(workspace)) return MLGNN_E_ALIGN;
-  if (vec_of(C) == 4 && !(aligned16(grad_y) && aligned16(y) && aligned16(z) && aligned16(att_src) && aligned16(att_dst) &&
-                          (!bias || aligned16(bias)) && (!grad_z || aligned16(grad_z))))
+  if (!aligned(workspace)) return MLGNN_E_ALIGN;
+  if (vec_of(C) == 4 && !aligned(grad_y, y, z, att_src, att_dst, bias, grad_z))
     return MLGNN_E_ALIGN;
   const GatShape s = make_shape(N, H, C, negative_slope, act_slope);
   const int d = s.d, blocks = stream_blocks(s);

@@ -40,6 +40,7 @@
 // all eight waves doing both DMA and MFMA (48 us), a second pair of MFMA waves splitting K with an LDS reduce (42 us),
 // a fifth stage / three K-steps in flight (same), s_setprio around the MFMAs (same).
 #include "gemm_nt.h"
+#include "launch.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
@@ -314,20 +315,20 @@ int gemm_nt_launch(const GemmDesc& d, hipStream_t s) {
     const GemmSeg& g = d.seg[i];
     if (!g.a || !g.b) return MLGNN_E_NULL;
     if (g.K <= 0 || g.K % kGemmBK || g.lda % 8 || g.ldb % 8 || g.lda < g.K || g.ldb < g.K) return MLGNN_E_SHAPE;
-    if (((uintptr_t)g.a | (uintptr_t)g.b) & 15) return MLGNN_E_ALIGN;
+    if (!aligned(g.a, g.b)) return MLGNN_E_ALIGN;
     p.ktiles += g.K / kGemmBK;
   }
   if (d.splits > p.ktiles) return MLGNN_E_SHAPE;
   if (d.splits > 1 && !d.slab) return MLGNN_E_NULL;
   if (!d.slab && !d.c && !d.ct && !d.dot) return MLGNN_E_NULL;
-  if (d.ct && (d.ldct % 8 || ((uintptr_t)d.ct & 15))) return MLGNN_E_ALIGN;
+  if (d.ct && (d.ldct % 8 || !aligned(d.ct))) return MLGNN_E_ALIGN;
   p.tiles_m = d.M / kGemmTile;
   p.tiles_n = d.N / kGemmTile;
   constexpr int kStages = 4;                   // 5 (three K-steps in flight, all 160 KB of LDS) measured the same
   constexpr int lds = kStages * kGStageBytes;
   static bool attr_set = false;                // idempotent: a race only repeats the call
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_kernel<kStages>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (const hipError_t e = allow_dynamic_lds(&gemm_nt_kernel<kStages>, lds); e != hipSuccess) return (int)e;
     attr_set = true;
   }
   if (d.batch > 1) {          // every problem's operands and results must keep the 16-byte alignment checked above

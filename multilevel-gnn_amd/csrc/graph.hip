@@ -14,6 +14,7 @@
 // Everything is enqueued on the caller's stream; no host synchronisation, workspace from the caller.
 #include <hipcub/hipcub.hpp>
 #include "common.h"
+#include "launch.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
@@ -525,7 +526,7 @@ extern "C" int mlgnn_edge_table_to_csr(const float* attr, int64_t row_stride, in
   const int threads = 256;
   hipStream_t s = (hipStream_t)stream;
   int64_t done = 0;
-  if (width == 1 && (((uintptr_t)eid | (uintptr_t)eid_t | (uintptr_t)by_dst | (uintptr_t)by_src) & 15) == 0 && E >= 4) {
+  if (width == 1 && aligned(eid, eid_t, by_dst, by_src) && E >= 4) {
     const int64_t n4 = E / 4;
     hipLaunchKernelGGL(edge_table_w1_kernel, dim3((unsigned)((n4 + threads - 1) / threads)), dim3(threads), 0, s, attr,
                        row_stride, (const int4*)eid, (const int4*)eid_t, (float4*)by_dst, (float4*)by_src, n4);

@@ -32,6 +32,7 @@
 // log-sum-exp of the softmax aggregation that produced x, also dX 2^(-lse) (the rescaled cotangent that aggregation's
 // backward gathers, csrc/aggregate_bwd.hip).  All partial results are reduced in a fixed order: bitwise reproducible.
 #include "common.h"
+#include "launch.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
@@ -718,9 +719,7 @@ extern "C" int mlgnn_linear_bwd(const float* go, const float* w, const float* x,
   if (epilogue == LB_LN && (!rstd || !gamma || !beta)) return MLGNN_E_NULL;
   if (epilogue == LB_SHIFT && (!lse || !grad_shifted || !shift_flag)) return MLGNN_E_NULL;
   if (workspace_floats < mlgnn_linear_bwd_workspace_floats(N, M, K, epilogue)) return MLGNN_E_WORKSPACE;
-  if (((reinterpret_cast<uintptr_t>(go) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(x) |
-        reinterpret_cast<uintptr_t>(rstd)) & 15) != 0)
-    return MLGNN_E_ALIGN;
+  if (!aligned(go, w, x, rstd)) return MLGNN_E_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   const int cols = (int)(M * K + M + (epilogue == LB_LN ? 2 * K : 0));
   float* parts = workspace + (int64_t)kLbParts * cols;           // [go | x | (unused)]
@@ -739,8 +738,8 @@ extern "C" int mlgnn_linear_bwd(const float* go, const float* w, const float* x,
 #define MLGNN_LB_LAUNCH(M_, K_, EPI_)                                                                        \
   {                                                                                                          \
     constexpr int lds_bytes = lb_lds_bytes<M_, K_>();                                                        \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_bwd_kernel<M_, K_, EPI_>),               \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);                        \
+    if (const hipError_t e_ = allow_dynamic_lds(&linear_bwd_kernel<M_, K_, EPI_>, lds_bytes); e_ != hipSuccess) \
+      return (int)e_;                                                                                        \
     hipLaunchKernelGGL((linear_bwd_kernel<M_, K_, EPI_>), dim3(grid), dim3(kLbThreads), lds_bytes, s, a);    \
   }
   if (epilogue == LB_PLAIN) { lse = nullptr; grad_shifted = nullptr; a.spread = nullptr; }

@@ -8,6 +8,7 @@
 // Reference: torch_nn.py:54-75 (the Linears of MLP).  R, J multiples of 128; the rows are padded to a multiple of 128
 // inside the workspace (zero rows), y / dx are [Npad, .] buffers whose first N rows are the result.
 #include "common.h"
+#include "launch.h"
 #include "gemm_chain.h"
 
 namespace mlgnn {
@@ -43,7 +44,7 @@ extern "C" int mlgnn_linear_f32x3_fwd(const float* x, const float* w, const floa
   if (!lin3_ok(N, R, J)) return MLGNN_E_SHAPE;
   if (!x || !w || !y || !workspace) return MLGNN_E_NULL;
   if (workspace_bytes < mlgnn_linear_f32x3_fwd_workspace_bytes(N, R, J)) return MLGNN_E_WORKSPACE;
-  if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)y | (uintptr_t)workspace | (uintptr_t)bias) & 15) return MLGNN_E_ALIGN;
+  if (!aligned(x, w, y, workspace, bias)) return MLGNN_E_ALIGN;
   const int64_t Np = lin3_pad(N);
   hipStream_t st = (hipStream_t)stream;
   unsigned char* ws = (unsigned char*)workspace;
@@ -89,8 +90,7 @@ extern "C" int mlgnn_linear_f32x3_bwd(const float* grad_out, const float* x, con
   if (!lin3_ok(N, R, J)) return MLGNN_E_SHAPE;
   if (!grad_out || !x || !w || !grad_w || !workspace) return MLGNN_E_NULL;
   if (workspace_bytes < mlgnn_linear_f32x3_bwd_workspace_bytes(N, R, J)) return MLGNN_E_WORKSPACE;
-  if (((uintptr_t)grad_out | (uintptr_t)x | (uintptr_t)w | (uintptr_t)grad_x | (uintptr_t)grad_w | (uintptr_t)workspace) & 15)
-    return MLGNN_E_ALIGN;
+  if (!aligned(grad_out, x, w, grad_x, grad_w, workspace)) return MLGNN_E_ALIGN;
   const int64_t Np = lin3_pad(N);
   const int splits = lin3_splits(Np, R, J);
   hipStream_t st = (hipStream_t)stream;

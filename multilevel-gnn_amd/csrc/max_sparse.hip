@@ -314,9 +314,7 @@ extern "C" int mlgnn_max_winners(const float* grad_out, const int32_t* argmax, c
                                  int64_t N, int64_t d, void* stream) {
   if (!ms_shape_ok(N, d)) return MLGNN_E_SHAPE;
   if (!grad_out || !argmax || !rowptr || !records || !meta) return MLGNN_E_NULL;
-  if (((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(argmax) | reinterpret_cast<uintptr_t>(records)) & 15) != 0 ||
-      (reinterpret_cast<uintptr_t>(meta) & 7) != 0)
-    return MLGNN_E_ALIGN;
+  if (!aligned(grad_out, argmax, records) || !aligned<8>(meta)) return MLGNN_E_ALIGN;
   const int lpr_log2 = lanes_per_row_log2(d, 4);
   const int rows_per_unit = kMsWaves * (kWave >> lpr_log2);
   const size_t lds = (size_t)rows_per_unit * kMsBins * sizeof(uint32_t);
@@ -331,8 +329,7 @@ extern "C" int mlgnn_max_sparse_bwd(const void* records, const void* meta, const
                                     const float* root, float* grad_x, int64_t N, int64_t d, void* stream) {
   if (!ms_shape_ok(N, d)) return MLGNN_E_SHAPE;
   if (!records || !meta || !rowptr_t || !pos_t || !grad_x) return MLGNN_E_NULL;
-  if (((reinterpret_cast<uintptr_t>(grad_x) | reinterpret_cast<uintptr_t>(root) | reinterpret_cast<uintptr_t>(records)) & 15) != 0)
-    return MLGNN_E_ALIGN;
+  if (!aligned(grad_x, root, records)) return MLGNN_E_ALIGN;
   const size_t lds = (size_t)kMsWaves * 8 * d * sizeof(float);
   static MsOcc occ;
   hipLaunchKernelGGL(max_sparse_bwd_kernel,
@@ -347,7 +344,7 @@ extern "C" int mlgnn_max_sparse_table_grad(const void* records, const void* meta
   if (!ms_shape_ok(N, d) || T < 0 || T > INT32_MAX) return MLGNN_E_SHAPE;
   if (T == 0) return 0;
   if (!records || !meta || !pos_sorted || !rowptr || !grad_table) return MLGNN_E_NULL;
-  if ((reinterpret_cast<uintptr_t>(records) & 15) != 0) return MLGNN_E_ALIGN;
+  if (!aligned(records)) return MLGNN_E_ALIGN;
   const size_t lds = (size_t)kMsWaves * 8 * d * sizeof(float);
   static MsOcc occ;
   const int blocks = ms_grid(max_sparse_table_grad_kernel, lds, (T + kMsWaves - 1) / kMsWaves, occ);

@@ -24,6 +24,7 @@
 #include <cmath>
 #include <type_traits>
 #include "common.h"
+#include "launch.h"
 #include "mlgnn.h"
 
 // Only the fused multiply-adds written as fmaf() below: the compiler contracts nothing on its own, so the scaled score
@@ -279,14 +280,12 @@ bool shape_ok(int64_t B, int64_t P, int64_t H, int64_t D) {
          && bwd_lds_bytes(P, D) <= kMhaLdsBytes && B * P * 3 * H * D * 4 < ((int64_t)1 << 32);
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-MhaShape make_shape(int64_t B, int64_t P, int64_t H, int64_t D, bool aligned) {
+MhaShape make_shape(int64_t B, int64_t P, int64_t H, int64_t D, bool vec_aligned) {
   MhaShape s;
   s.B = (int)B; s.P = (int)P; s.H = (int)H; s.D = (int)D;
   s.ds = (int)(D | 1);
   s.dl_log2 = lanes_per_row_log2(D, 1);
-  s.vec4 = (D % 4 == 0 && aligned) ? 1 : 0;
+  s.vec4 = (D % 4 == 0 && vec_aligned) ? 1 : 0;
   s.scale = (float)(1.0 / sqrt((double)D));
   return s;
 }
@@ -311,16 +310,18 @@ extern "C" int mlgnn_mha_fwd(const float* qkv, const uint8_t* keep, float keep_s
   if (!shape_ok(B, P, H, D)) return MLGNN_E_SHAPE;
   if (B == 0 || P == 0) return 0;
   if (!qkv || !out || !lse) return MLGNN_E_NULL;
-  const MhaShape s = make_shape(B, P, H, D, aligned16(qkv));
+  const MhaShape s = make_shape(B, P, H, D, aligned(qkv));
   const int waves = fwd_lds_bytes(P, D, kMhaWavesWide) <= kMhaLdsBytes ? kMhaWavesWide : kMhaWaves;
   const int lds = (int)fwd_lds_bytes(P, D, waves);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = as_stream(stream);
+  hipError_t lds_err = hipSuccess;
   for_passes(P, [&](auto np) {
     auto kernel = &mha_fwd_kernel<decltype(np)::value>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    lds_err = allow_dynamic_lds(kernel, lds);
+    if (lds_err != hipSuccess) return;
     hipLaunchKernelGGL(kernel, dim3((unsigned)(B * H)), dim3(waves * kWave), lds, st, qkv, keep, keep_scale, out, lse, s);
   });
-  return (int)hipGetLastError();
+  return lds_err != hipSuccess ? (int)lds_err : (int)hipGetLastError();
 }
 
 // both phases of the backward run inside the workgroup that owns the (b, h) pair: no workspace (0 floats, NULL is fine)
@@ -337,15 +338,17 @@ extern "C" int mlgnn_mha_bwd(const float* grad_out, const float* qkv, const floa
   if (!grad_out || !qkv || !out || !lse || !grad_qkv) return MLGNN_E_NULL;
   const int64_t need = mlgnn_mha_bwd_workspace_floats(B, P, H, D);
   if (workspace_floats < need || (need > 0 && !workspace)) return MLGNN_E_WORKSPACE;
-  const MhaShape s = make_shape(B, P, H, D, aligned16(qkv) && aligned16(grad_out));
+  const MhaShape s = make_shape(B, P, H, D, aligned(qkv, grad_out));
   const int waves = bwd_lds_bytes(P, D, kMhaWavesWide) <= kMhaLdsBytes ? kMhaWavesWide : kMhaWaves;
   const int lds = (int)bwd_lds_bytes(P, D, waves);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = as_stream(stream);
+  hipError_t lds_err = hipSuccess;
   for_passes(P, [&](auto np) {
     auto kernel = &mha_bwd_kernel<decltype(np)::value>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    lds_err = allow_dynamic_lds(kernel, lds);
+    if (lds_err != hipSuccess) return;
     hipLaunchKernelGGL(kernel, dim3((unsigned)(B * H)), dim3(waves * kWave), lds, st, grad_out, qkv, lse, keep, keep_scale,
                        grad_qkv, s);
   });
-  return (int)hipGetLastError();
+  return lds_err != hipSuccess ? (int)lds_err : (int)hipGetLastError();
 }

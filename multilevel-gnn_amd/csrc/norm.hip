@@ -10,6 +10,7 @@
 // lane), a wave works on 64/LPR rows at once, row statistics are xor-shuffle reductions inside
 // the lane group.  HBM-bound: forward 2*rows*d*4 bytes, backward 3*rows*d*4 bytes (+ 8 B/row stats).
 #include "common.h"
+#include "launch.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
@@ -237,29 +238,16 @@ static bool ln_ok_t(int64_t d, int dtype) {
   const int v = ln_vec(dtype, d);
   return d > 0 && d <= 64 * v && d % v == 0;
 }
-static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-#define MLGNN_LN_LAUNCH(KERNEL, lpr, ...)                                         \
-  switch (lpr) {                                                                  \
-    case 0: hipLaunchKernelGGL((KERNEL<0>), __VA_ARGS__); break;                  \
-    case 1: hipLaunchKernelGGL((KERNEL<1>), __VA_ARGS__); break;                  \
-    case 2: hipLaunchKernelGGL((KERNEL<2>), __VA_ARGS__); break;                  \
-    case 3: hipLaunchKernelGGL((KERNEL<3>), __VA_ARGS__); break;                  \
-    case 4: hipLaunchKernelGGL((KERNEL<4>), __VA_ARGS__); break;                  \
-    case 5: hipLaunchKernelGGL((KERNEL<5>), __VA_ARGS__); break;                  \
-    default: hipLaunchKernelGGL((KERNEL<6>), __VA_ARGS__); break;                 \
-  }
-
-#define MLGNN_LNT_LAUNCH(KERNEL, T, VEC, lpr, ...)                                \
-  switch (lpr) {                                                                  \
-    case 0: hipLaunchKernelGGL((KERNEL<T, VEC, 0>), __VA_ARGS__); break;          \
-    case 1: hipLaunchKernelGGL((KERNEL<T, VEC, 1>), __VA_ARGS__); break;          \
-    case 2: hipLaunchKernelGGL((KERNEL<T, VEC, 2>), __VA_ARGS__); break;          \
-    case 3: hipLaunchKernelGGL((KERNEL<T, VEC, 3>), __VA_ARGS__); break;          \
-    case 4: hipLaunchKernelGGL((KERNEL<T, VEC, 4>), __VA_ARGS__); break;          \
-    case 5: hipLaunchKernelGGL((KERNEL<T, VEC, 5>), __VA_ARGS__); break;          \
-    default: hipLaunchKernelGGL((KERNEL<T, VEC, 6>), __VA_ARGS__); break;         \
-  }
+// f(T{}, IC<VEC>{}, IC<LPR_LOG2>{}) for the lane layout of (dtype, d); false, and nothing called, when lpr is no layout.
+// WIDE_F32: the op has the fp32 layout of two 16-byte loads per lane for d > 256 (LayerNorm has, MsgNorm has not).
+template <bool WIDE_F32, class F>
+static bool for_ln_layout(int dtype, int64_t d, int lpr, F&& f) {
+  auto with = [&](auto t, auto vec) { return dispatch_int<0, 1, 2, 3, 4, 5, 6>(lpr, [&](auto l) { f(t, vec, l); }); };
+  if (dtype == MLGNN_DTYPE_BF16) return with(bf16_t{}, IC<8>{});
+  if (d <= 256) return with(float{}, IC<4>{});
+  if constexpr (WIDE_F32) return with(float{}, IC<8>{});
+  return false;
+}
 
 }  // namespace mlgnn
 
@@ -278,22 +266,19 @@ extern "C" int mlgnn_layernorm_act_fwd(const void* x, const float* gamma, const 
   if (rows < 0 || rows > INT32_MAX || !ln_ok_t(d, dtype)) return MLGNN_E_SHAPE;
   if (rows == 0) return 0;
   if (!x || !gamma || !beta || !out || !mean || !rstd) return MLGNN_E_NULL;
-  if (!a16(x) || !a16(out) || !a16(gamma) || !a16(beta)) return MLGNN_E_ALIGN;
+  if (!aligned(x, out, gamma, beta)) return MLGNN_E_ALIGN;
   LnArgs a{};
   a.x = x; a.gamma = gamma; a.beta = beta; a.out = out; a.mean = mean; a.rstd = rstd;
   a.rowmax = row_max; a.keep = keep_mask; a.keep_scale = keep_scale;
   if (keep_mask && d % ln_vec(dtype, d) != 0) return MLGNN_E_SHAPE;
-  if (keep_mask && (reinterpret_cast<uintptr_t>(keep_mask) % 8) != 0) return MLGNN_E_ALIGN;    // read 4 / 8 flags at a time
+  if (!aligned<8>(keep_mask)) return MLGNN_E_ALIGN;    // read 4 / 8 flags at a time
   a.rows = (int)rows; a.d = (int)d; a.eps = eps; a.relu = relu;
   const int lpr = lanes_per_row_log2(d, ln_vec(dtype, d));
   const dim3 grid(ln_grid(rows, lpr)), block(kBlock);
-  if (dtype == MLGNN_DTYPE_F32 && d > 256) {
-    MLGNN_LNT_LAUNCH(layernorm_act_fwd_kernel, float, 8, lpr, grid, block, 0, (hipStream_t)stream, a)
-  } else if (dtype == MLGNN_DTYPE_F32) {
-    MLGNN_LNT_LAUNCH(layernorm_act_fwd_kernel, float, 4, lpr, grid, block, 0, (hipStream_t)stream, a)
-  } else {
-    MLGNN_LNT_LAUNCH(layernorm_act_fwd_kernel, bf16_t, 8, lpr, grid, block, 0, (hipStream_t)stream, a)
-  }
+  if (!for_ln_layout<true>(dtype, d, lpr, [&](auto t, auto vec, auto l) {
+        hipLaunchKernelGGL((layernorm_act_fwd_kernel<decltype(t), vec(), l()>), grid, block, 0, as_stream(stream), a);
+      }))
+    return MLGNN_E_SHAPE;
   return (int)hipGetLastError();
 }
 
@@ -310,22 +295,19 @@ extern "C" int mlgnn_layernorm_act_bwd(const void* grad_out, const void* x, cons
   const int nblk = ln_grid(rows, lpr);
   if (workspace_floats < (int64_t)nblk * 2 * d) return MLGNN_E_WORKSPACE;
   if (rows > 0 && (!grad_out || !x || !gamma || !beta || !rstd || !grad_x)) return MLGNN_E_NULL;
-  if (!a16(x) || !a16(grad_out) || !a16(grad_x) || !a16(gamma) || !a16(beta) || !a16(grad_extra)) return MLGNN_E_ALIGN;
-  if (keep_mask && (reinterpret_cast<uintptr_t>(keep_mask) % 8) != 0) return MLGNN_E_ALIGN;
+  if (!aligned(x, grad_out, grad_x, gamma, beta, grad_extra)) return MLGNN_E_ALIGN;
+  if (!aligned<8>(keep_mask)) return MLGNN_E_ALIGN;
   LnArgs a{};
   a.x = x; a.go = grad_out; a.gamma = gamma; a.beta = beta;
   a.gextra = grad_extra; a.keep = keep_mask; a.keep_scale = keep_scale;
   a.mean = (float*)mean; a.rstd = (float*)rstd; a.gx = grad_x; a.ws = workspace; a.rowmax = row_max;
   a.rows = (int)rows; a.d = (int)d; a.relu = relu;
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = as_stream(stream);
   const dim3 grid(nblk), block(kBlock);
-  if (dtype == MLGNN_DTYPE_F32 && d > 256) {
-    MLGNN_LNT_LAUNCH(layernorm_act_bwd_kernel, float, 8, lpr, grid, block, 0, s, a)
-  } else if (dtype == MLGNN_DTYPE_F32) {
-    MLGNN_LNT_LAUNCH(layernorm_act_bwd_kernel, float, 4, lpr, grid, block, 0, s, a)
-  } else {
-    MLGNN_LNT_LAUNCH(layernorm_act_bwd_kernel, bf16_t, 8, lpr, grid, block, 0, s, a)
-  }
+  if (!for_ln_layout<true>(dtype, d, lpr, [&](auto t, auto vec, auto l) {
+        hipLaunchKernelGGL((layernorm_act_bwd_kernel<decltype(t), vec(), l()>), grid, block, 0, s, a);
+      }))
+    return MLGNN_E_SHAPE;
   int err = (int)hipGetLastError();
   if (err) return err;
   launch_reduce_partials(workspace, grad_gamma_beta, nblk, 2 * (int)d, s);
@@ -463,17 +445,16 @@ extern "C" int mlgnn_msgnorm_add_fwd(const void* x, const void* m, const float* 
   if (rows < 0 || rows > INT32_MAX || !mn_ok(d, dtype)) return MLGNN_E_SHAPE;
   if (rows == 0) return 0;
   if (!x || !m || !scale || !h) return MLGNN_E_NULL;
-  if (!a16(x) || !a16(m) || !a16(h)) return MLGNN_E_ALIGN;
+  if (!aligned(x, m, h)) return MLGNN_E_ALIGN;
   MnArgs a{};
   a.x = x; a.m = m; a.scale = scale; a.h = h; a.rows = (int)rows; a.d = (int)d;
   const int vec = dtype == MLGNN_DTYPE_BF16 ? 8 : 4;
   const int lpr = lanes_per_row_log2(d, vec);
   const dim3 grid(ln_grid(rows, lpr)), block(kBlock);
-  if (dtype == MLGNN_DTYPE_BF16) {
-    MLGNN_LNT_LAUNCH(msgnorm_add_fwd_kernel, bf16_t, 8, lpr, grid, block, 0, (hipStream_t)stream, a)
-  } else {
-    MLGNN_LNT_LAUNCH(msgnorm_add_fwd_kernel, float, 4, lpr, grid, block, 0, (hipStream_t)stream, a)
-  }
+  if (!for_ln_layout<false>(dtype, d, lpr, [&](auto t, auto vec, auto l) {
+        hipLaunchKernelGGL((msgnorm_add_fwd_kernel<decltype(t), vec(), l()>), grid, block, 0, as_stream(stream), a);
+      }))
+    return MLGNN_E_SHAPE;
   return (int)hipGetLastError();
 }
 
@@ -489,16 +470,15 @@ extern "C" int mlgnn_msgnorm_add_bwd(const void* grad_h, const void* x, const vo
   const int nblk = ln_grid(rows, lpr);
   if (workspace_floats < nblk) return MLGNN_E_WORKSPACE;
   if (rows > 0 && (!grad_h || !x || !m || !grad_x || !grad_m)) return MLGNN_E_NULL;
-  if (!a16(x) || !a16(m) || !a16(grad_h) || !a16(grad_x) || !a16(grad_m)) return MLGNN_E_ALIGN;
+  if (!aligned(x, m, grad_h, grad_x, grad_m)) return MLGNN_E_ALIGN;
   MnArgs a{};
   a.x = x; a.m = m; a.gh = grad_h; a.scale = scale;
   a.gx = grad_x; a.gm = grad_m; a.ws = workspace; a.rows = (int)rows; a.d = (int)d;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == MLGNN_DTYPE_BF16) {
-    MLGNN_LNT_LAUNCH(msgnorm_add_bwd_kernel, bf16_t, 8, lpr, dim3(nblk), dim3(kBlock), 0, s, a)
-  } else {
-    MLGNN_LNT_LAUNCH(msgnorm_add_bwd_kernel, float, 4, lpr, dim3(nblk), dim3(kBlock), 0, s, a)
-  }
+  hipStream_t s = as_stream(stream);
+  if (!for_ln_layout<false>(dtype, d, lpr, [&](auto t, auto vec, auto l) {
+        hipLaunchKernelGGL((msgnorm_add_bwd_kernel<decltype(t), vec(), l()>), dim3(nblk), dim3(kBlock), 0, s, a);
+      }))
+    return MLGNN_E_SHAPE;
   int err = (int)hipGetLastError();
   if (err) return err;
   launch_reduce_partials(workspace, grad_scale, nblk, 1, s);

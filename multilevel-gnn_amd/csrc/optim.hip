@@ -16,6 +16,7 @@
 // parallelism the flags can ride at the tail of the gradient all-reduce and every rank steps the union of what any
 // rank reached (mlgnn/dist.py); an element finds its parameter by bisection over the parameter offsets.
 #include "common.h"
+#include "launch.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
@@ -161,9 +162,7 @@ extern "C" int mlgnn_adam_step(float* params, float* grads, float* exp_avg, floa
   if (!params || !grads || !exp_avg || !exp_avg_sq || !workspace) return MLGNN_E_NULL;
   if (live && (!param_offsets || n_params == 0)) return MLGNN_E_NULL;
   if (!(bias2_sqrt > 0.f)) return MLGNN_E_MODE;
-  if (((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(exp_avg) |
-        reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) != 0)
-    return MLGNN_E_ALIGN;
+  if (!aligned(params, grads, exp_avg, exp_avg_sq)) return MLGNN_E_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   if (max_norm > 0.f)
     hipLaunchKernelGGL(adam_sumsq_kernel, dim3(kAdamPartials), dim3(256), 0, s, grads, n, workspace);

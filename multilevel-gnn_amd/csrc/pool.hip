@@ -6,6 +6,7 @@
 // Two deterministic stages, no atomics: (graph, slice) workgroups reduce a row slice each, then the
 // slices of a graph are folded in order.  HBM-bound: reads N*d*4 bytes once.
 #include "common.h"
+#include "launch.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
@@ -120,7 +121,7 @@ extern "C" int mlgnn_segment_pool_fwd(const void* x, const int32_t* ptr, void* o
   if (B == 0) return 0;
   if (!x || !ptr || !out || !workspace || (kind == 2 && !argmax)) return MLGNN_E_NULL;
   if (workspace_bytes < B * slices * d * 8) return MLGNN_E_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(x) & 15) != 0) return MLGNN_E_ALIGN;
+  if (!aligned(x)) return MLGNN_E_ALIGN;
   PoolArgs a;
   a.x = (const float*)x; a.ptr = ptr; a.part = (float*)workspace;
   a.part_arg = (int*)((char*)workspace + (size_t)B * slices * d * 4);

@@ -12,6 +12,7 @@
 // out_t / gout_t [B*S, K, C] (channel-contiguous; the host permutes the 30 MB result to [B,C,S,K]).
 // HBM-bound: algorithmic bytes = M*C*4 (gathered rows) + M*(4+4+4K) (tables) + B*S*K*C*4.
 #include "common.h"
+#include "launch.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
@@ -395,26 +396,14 @@ __global__ __launch_bounds__(kBlock) void segment_project_bwd_w_kernel(const Pro
   }
 }
 
-#define MLGNN_PROJ_LAUNCH(KERNEL, T, VEC, K, ...)                                            \
-  switch (K) {                                                                               \
-    case 1: hipLaunchKernelGGL((KERNEL<T, VEC, 1>), __VA_ARGS__); break;                     \
-    case 2: hipLaunchKernelGGL((KERNEL<T, VEC, 2>), __VA_ARGS__); break;                     \
-    case 3: hipLaunchKernelGGL((KERNEL<T, VEC, 3>), __VA_ARGS__); break;                     \
-    default: hipLaunchKernelGGL((KERNEL<T, VEC, 4>), __VA_ARGS__); break;                    \
-  }
-// storage type x channels per lane: 16-byte accesses (4 x fp32 / 8 x bf16) when width and alignment allow, else scalar
-#define MLGNN_PROJ_DISPATCH(KERNEL, bf16, wide, K, ...)                                      \
-  do {                                                                                       \
-    if (bf16) {                                                                              \
-      if (wide) { MLGNN_PROJ_LAUNCH(KERNEL, bf16_t, 8, K, __VA_ARGS__) }                     \
-      else { MLGNN_PROJ_LAUNCH(KERNEL, bf16_t, 1, K, __VA_ARGS__) }                          \
-    } else {                                                                                 \
-      if (wide) { MLGNN_PROJ_LAUNCH(KERNEL, float, 4, K, __VA_ARGS__) }                      \
-      else { MLGNN_PROJ_LAUNCH(KERNEL, float, 1, K, __VA_ARGS__) }                           \
-    }                                                                                        \
-  } while (0)
-
-static bool p16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// f(T{}, IC<VEC>{}, IC<K>{}): storage type x channels per lane x output columns.  16-byte accesses (4 x fp32 / 8 x bf16)
+// when width and alignment allow (wide), else scalar; false, and nothing called, when K is not in 1 .. 4.
+template <class F>
+static bool for_proj_layout(bool bf16, bool wide, int64_t K, F&& f) {
+  auto with = [&](auto t, auto vec) { return dispatch_int<1, 2, 3, 4>((int)K, [&](auto k) { f(t, vec, k); }); };
+  if (bf16) return wide ? with(bf16_t{}, IC<8>{}) : with(bf16_t{}, IC<1>{});
+  return wide ? with(float{}, IC<4>{}) : with(float{}, IC<1>{});
+}
 
 // n_groups = 0: the plain layout (segs_per_sample unused); otherwise whole samples of S segments, S a multiple of n_groups
 static bool proj_layout_ok(int64_t n_segments, int64_t S, int64_t n_groups) {
@@ -440,12 +429,15 @@ extern "C" int mlgnn_segment_project_fwd(const void* x, const float* w, const in
   a.out = out_t; a.rows = (int)n_segments; a.C = (int)C; a.G = (int)G;
   a.S = (int)segs_per_sample; a.n_groups = (int)n_groups;
   const dim3 grid(grid_for_rows(n_segments)), block(kBlock);
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = as_stream(stream);
   const bool bf16 = dtype == MLGNN_DTYPE_BF16;
   const int vec = bf16 ? 8 : 4;
-  const bool wide = C % vec == 0 && p16(x) && p16(out_t);
+  const bool wide = C % vec == 0 && aligned(x, out_t);
   a.lpr_log2 = lanes_per_row_log2(C, wide ? vec : 1);
-  MLGNN_PROJ_DISPATCH(segment_project_fwd_kernel, bf16, wide, (int)K, grid, block, 0, s, a);
+  if (!for_proj_layout(bf16, wide, K, [&](auto t, auto v, auto k) {
+        hipLaunchKernelGGL((segment_project_fwd_kernel<decltype(t), v(), k()>), grid, block, 0, s, a);
+      }))
+    return MLGNN_E_SHAPE;
   return (int)hipGetLastError();
 }
 
@@ -461,11 +453,11 @@ extern "C" int mlgnn_segment_project_bwd(const void* gout_t, const void* x, cons
       n_segments > INT32_MAX) return MLGNN_E_SHAPE;
   if (!proj_layout_ok(n_segments, segs_per_sample, n_groups)) return MLGNN_E_SHAPE;
   if (!gout_t || !w) return MLGNN_E_NULL;
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = as_stream(stream);
   const dim3 block(kBlock);
   const bool bf16 = dtype == MLGNN_DTYPE_BF16;
   const int vec = bf16 ? 8 : 4;
-  const bool wide = (C % vec == 0) && p16(gout_t) && (!x || p16(x)) && (!grad_x || p16(grad_x));
+  const bool wide = (C % vec == 0) && aligned(gout_t, x, grad_x);
   if (grad_x && n_rows > 0) {
     if (!node_ptr || !mem_seg) return MLGNN_E_NULL;
     ProjArgs a{};
@@ -479,10 +471,15 @@ extern "C" int mlgnn_segment_project_bwd(const void* gout_t, const void* x, cons
     static const bool unit_on = [] { const char* e = getenv("MLGNN_PROJ_UNIT"); return !(e && e[0] == '0'); }();
     const int lane_groups = kWave >> a.lpr_log2;
     const dim3 ugrid(grid_for_rows((n_rows + 7) / 8));
-    if (lane_groups >= 4) MLGNN_PROJ_DISPATCH(segment_project_bwd_x_kernel, bf16, wide, (int)K, grid, block, 0, s, a);
-    else if (unit_on && lane_groups == 2) MLGNN_PROJ_DISPATCH(segment_project_bwd_x_unit2_kernel, bf16, wide, (int)K, ugrid, block, 0, s, a);
-    else if (unit_on && lane_groups == 1 && K <= 2) MLGNN_PROJ_DISPATCH(segment_project_bwd_x_unit1_kernel, bf16, wide, (int)K, ugrid, block, 0, s, a);
-    else MLGNN_PROJ_DISPATCH(segment_project_bwd_x_wave_kernel, bf16, wide, (int)K, grid, block, 0, s, a);
+    const int form = lane_groups >= 4 ? 0 : (unit_on && lane_groups == 2) ? 1 : (unit_on && lane_groups == 1 && K <= 2) ? 2 : 3;
+    if (!for_proj_layout(bf16, wide, K, [&](auto t, auto v, auto k) {
+          using T = decltype(t);
+          if (form == 0) hipLaunchKernelGGL((segment_project_bwd_x_kernel<T, v(), k()>), grid, block, 0, s, a);
+          else if (form == 1) hipLaunchKernelGGL((segment_project_bwd_x_unit2_kernel<T, v(), k()>), ugrid, block, 0, s, a);
+          else if (form == 2) hipLaunchKernelGGL((segment_project_bwd_x_unit1_kernel<T, v(), k()>), ugrid, block, 0, s, a);
+          else hipLaunchKernelGGL((segment_project_bwd_x_wave_kernel<T, v(), k()>), grid, block, 0, s, a);
+        }))
+      return MLGNN_E_SHAPE;
     const int err = (int)hipGetLastError();
     if (err) return err;
   }
@@ -495,7 +492,10 @@ extern "C" int mlgnn_segment_project_bwd(const void* gout_t, const void* x, cons
     a.S = (int)segs_per_sample; a.n_groups = (int)n_groups;
     const dim3 grid(grid_for_rows(n_segments));
     a.lpr_log2 = lanes_per_row_log2(C, wide ? vec : 1);
-    MLGNN_PROJ_DISPATCH(segment_project_bwd_w_kernel, bf16, wide, (int)K, grid, block, 0, s, a);
+    if (!for_proj_layout(bf16, wide, K, [&](auto t, auto v, auto k) {
+          hipLaunchKernelGGL((segment_project_bwd_w_kernel<decltype(t), v(), k()>), grid, block, 0, s, a);
+        }))
+      return MLGNN_E_SHAPE;
     const int err = (int)hipGetLastError();
     if (err) return err;
   }

@@ -12,6 +12,7 @@
 //
 // All three are HBM-bound streams: 16-byte accesses, one pass, nothing kept.
 #include "common.h"
+#include "launch.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
@@ -293,29 +294,24 @@ static int stream_grid(int64_t n_units) {
 
 using namespace mlgnn;
 
-#define MLGNN_LPR_SWITCH(LPR_, BODY)                  \
-  switch (LPR_) {                                     \
-    case 1: { constexpr int L = 1; BODY } break;      \
-    case 2: { constexpr int L = 2; BODY } break;      \
-    case 4: { constexpr int L = 4; BODY } break;      \
-    case 8: { constexpr int L = 8; BODY } break;      \
-    case 16: { constexpr int L = 16; BODY } break;    \
-    case 32: { constexpr int L = 32; BODY } break;    \
-    default: { constexpr int L = 64; BODY } break;    \
-  }
+// f(IC<L>{}) for the L = J / 4 lanes per row that width_ok admits
+template <class F>
+static bool for_row_lanes(int64_t J, F&& f) { return dispatch_int<1, 2, 4, 8, 16, 32, 64>((int)(J / 4), f); }
 
 extern "C" int mlgnn_leaky_relu_bwd(const float* grad_out, const float* y, const float* row_scale, float slope,
                                     float* grad_z, float* grad_z_row_max, int64_t N, int64_t J, void* stream) {
   if (N < 0 || N > INT32_MAX || !width_ok(J)) return MLGNN_E_SHAPE;
   if (N == 0) return 0;
   if (!grad_out || !y || !grad_z) return MLGNN_E_NULL;
-  if (((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(grad_z)) & 15) != 0)
-    return MLGNN_E_ALIGN;
+  if (!aligned(grad_out, y, grad_z)) return MLGNN_E_ALIGN;
   const int64_t units = N * (J / 4);
-  hipStream_t s = (hipStream_t)stream;
-  MLGNN_LPR_SWITCH((int)(J / 4), hipLaunchKernelGGL((leaky_relu_bwd_kernel<L>), dim3(stream_grid(units)), dim3(256), 0, s,
-                   reinterpret_cast<const float4*>(grad_out), reinterpret_cast<const float4*>(y), row_scale, slope,
-                   reinterpret_cast<float4*>(grad_z), grad_z_row_max, units);)
+  hipStream_t s = as_stream(stream);
+  if (!for_row_lanes(J, [&](auto l) {
+        hipLaunchKernelGGL((leaky_relu_bwd_kernel<l()>), dim3(stream_grid(units)), dim3(256), 0, s,
+                           reinterpret_cast<const float4*>(grad_out), reinterpret_cast<const float4*>(y), row_scale, slope,
+                           reinterpret_cast<float4*>(grad_z), grad_z_row_max, units);
+      }))
+    return MLGNN_E_SHAPE;
   return (int)hipGetLastError();
 }
 
@@ -324,11 +320,14 @@ extern "C" int mlgnn_node_embed_fwd(const float* x, const float* embedding, floa
   if (batch < 0 || nodes <= 0 || nodes > INT32_MAX || batch * nodes > INT32_MAX || !width_ok(C)) return MLGNN_E_SHAPE;
   if (batch == 0) return 0;
   if (!x || !embedding || !h) return MLGNN_E_NULL;
-  if (((reinterpret_cast<uintptr_t>(embedding) | reinterpret_cast<uintptr_t>(h)) & 15) != 0) return MLGNN_E_ALIGN;
+  if (!aligned(embedding, h)) return MLGNN_E_ALIGN;
   const int64_t units = batch * nodes * (C / 4);
-  hipStream_t s = (hipStream_t)stream;
-  MLGNN_LPR_SWITCH((int)(C / 4), hipLaunchKernelGGL((node_embed_fwd_kernel<L>), dim3(stream_grid(units)), dim3(256), 0, s, x,
-                   reinterpret_cast<const float4*>(embedding), reinterpret_cast<float4*>(h), h_row_max, units, (int)nodes);)
+  hipStream_t s = as_stream(stream);
+  if (!for_row_lanes(C, [&](auto l) {
+        hipLaunchKernelGGL((node_embed_fwd_kernel<l()>), dim3(stream_grid(units)), dim3(256), 0, s, x,
+                           reinterpret_cast<const float4*>(embedding), reinterpret_cast<float4*>(h), h_row_max, units, (int)nodes);
+      }))
+    return MLGNN_E_SHAPE;
   return (int)hipGetLastError();
 }
 
@@ -337,14 +336,16 @@ extern "C" int mlgnn_node_embed_bwd(const float* x, const float* grad_h, float* 
   if (batch < 0 || batch > INT32_MAX || nodes <= 0 || nodes > INT32_MAX || batch * nodes > INT32_MAX || !width_ok(C))
     return MLGNN_E_SHAPE;
   if (!grad_embedding) return MLGNN_E_NULL;
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = as_stream(stream);
   if (batch == 0) return (int)hipMemsetAsync(grad_embedding, 0, (size_t)(nodes * C) * sizeof(float), s);
   if (!x || !grad_h) return MLGNN_E_NULL;
-  if (((reinterpret_cast<uintptr_t>(grad_h) | reinterpret_cast<uintptr_t>(grad_embedding)) & 15) != 0) return MLGNN_E_ALIGN;
+  if (!aligned(grad_h, grad_embedding)) return MLGNN_E_ALIGN;
   const int64_t units = nodes * (C / 4);
-  MLGNN_LPR_SWITCH((int)(C / 4), hipLaunchKernelGGL((node_embed_bwd_kernel<L>), dim3((unsigned)((units + 255) / 256)), dim3(256),
-                   0, s, x, reinterpret_cast<const float4*>(grad_h), reinterpret_cast<float4*>(grad_embedding), (int)nodes,
-                   (int)batch);)
+  if (!for_row_lanes(C, [&](auto l) {
+        hipLaunchKernelGGL((node_embed_bwd_kernel<l()>), dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, x,
+                           reinterpret_cast<const float4*>(grad_h), reinterpret_cast<float4*>(grad_embedding), (int)nodes, (int)batch);
+      }))
+    return MLGNN_E_SHAPE;
   return (int)hipGetLastError();
 }
 
@@ -352,7 +353,7 @@ extern "C" int mlgnn_stream_copy(const void* src, void* dst, int64_t bytes, int 
   if (bytes < 0 || bytes % 16 != 0) return MLGNN_E_SHAPE;
   if (bytes == 0) return 0;
   if (!src || !dst) return MLGNN_E_NULL;
-  if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) != 0) return MLGNN_E_ALIGN;
+  if (!aligned(src, dst)) return MLGNN_E_ALIGN;
   if (non_temporal)
     hipLaunchKernelGGL(stream_copy_kernel<true>, dim3(256 * 8), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const float4*>(src), reinterpret_cast<float4*>(dst), bytes / 16);
@@ -361,18 +362,6 @@ extern "C" int mlgnn_stream_copy(const void* src, void* dst, int64_t bytes, int 
                        reinterpret_cast<const float4*>(src), reinterpret_cast<float4*>(dst), bytes / 16);
   return (int)hipGetLastError();
 }
-
-#define MLGNN_R_SWITCH(R_, BODY)                    \
-  switch (R_) {                                     \
-    case 1: { constexpr int RR = 1; BODY } break;   \
-    case 2: { constexpr int RR = 2; BODY } break;   \
-    case 3: { constexpr int RR = 3; BODY } break;   \
-    case 4: { constexpr int RR = 4; BODY } break;   \
-    case 5: { constexpr int RR = 5; BODY } break;   \
-    case 6: { constexpr int RR = 6; BODY } break;   \
-    case 7: { constexpr int RR = 7; BODY } break;   \
-    default: { constexpr int RR = 8; BODY } break;  \
-  }
 
 static bool narrow_ok(int64_t N, int64_t R, int64_t J) {
   // J = 4 * lanes with 8, 16, 32 or 64 lanes per row (32 .. 256 columns); 1 .. 8 input columns
@@ -386,24 +375,29 @@ extern "C" int64_t mlgnn_narrow_linear_bwd_workspace_floats(int64_t R, int64_t J
   return (int64_t)kNarrowBlocks * J * (R + 1);
 }
 
-#define MLGNN_NARROW_LPR(J_, BODY)                      \
-  switch ((int)(J_ / 4)) {                              \
-    case 8: { constexpr int L = 8; BODY } break;        \
-    case 16: { constexpr int L = 16; BODY } break;      \
-    case 32: { constexpr int L = 32; BODY } break;      \
-    default: { constexpr int L = 64; BODY } break;      \
-  }
+// f(IC<L>{}, IC<R>{}) for the L = J / 4 lanes per row and the R input columns that narrow_ok admits
+template <class F>
+static bool for_narrow_layout(int64_t J, int64_t R, F&& f) {
+  bool found = false;
+  dispatch_int<8, 16, 32, 64>((int)(J / 4), [&](auto l) {
+    found = dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>((int)R, [&](auto r) { f(l, r); });
+  });
+  return found;
+}
 
 extern "C" int mlgnn_narrow_linear_fwd(const float* x, const float* w, const float* bias, float* out, int64_t N, int64_t R,
                                        int64_t J, void* stream) {
   if (!narrow_ok(N, R, J)) return MLGNN_E_SHAPE;
   if (N == 0) return 0;
   if (!x || !w || !out) return MLGNN_E_NULL;
-  if ((reinterpret_cast<uintptr_t>(out) & 15) != 0) return MLGNN_E_ALIGN;
+  if (!aligned(out)) return MLGNN_E_ALIGN;
   const int64_t units = N * (J / 4);
-  hipStream_t s = (hipStream_t)stream;
-  MLGNN_NARROW_LPR(J, MLGNN_R_SWITCH((int)R, hipLaunchKernelGGL((narrow_linear_fwd_kernel<L, RR>), dim3(stream_grid(units)),
-                   dim3(256), 0, s, x, w, bias, reinterpret_cast<float4*>(out), units);))
+  hipStream_t s = as_stream(stream);
+  if (!for_narrow_layout(J, R, [&](auto l, auto r) {
+        hipLaunchKernelGGL((narrow_linear_fwd_kernel<l(), r()>), dim3(stream_grid(units)), dim3(256), 0, s, x, w, bias,
+                           reinterpret_cast<float4*>(out), units);
+      }))
+    return MLGNN_E_SHAPE;
   return (int)hipGetLastError();
 }
 
@@ -413,11 +407,14 @@ extern "C" int mlgnn_narrow_linear_bwd(const float* grad_out, const float* x, fl
   if (!grad_w_b || !workspace) return MLGNN_E_NULL;
   if (N > 0 && (!grad_out || !x)) return MLGNN_E_NULL;
   if (workspace_floats < mlgnn_narrow_linear_bwd_workspace_floats(R, J)) return MLGNN_E_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(grad_out) & 15) != 0) return MLGNN_E_ALIGN;
+  if (!aligned(grad_out)) return MLGNN_E_ALIGN;
   const int64_t units = N * (J / 4);
-  hipStream_t s = (hipStream_t)stream;
-  MLGNN_NARROW_LPR(J, MLGNN_R_SWITCH((int)R, hipLaunchKernelGGL((narrow_linear_bwd_kernel<L, RR>), dim3(kNarrowBlocks), dim3(256),
-                   0, s, reinterpret_cast<const float4*>(grad_out), x, workspace, units);))
+  hipStream_t s = as_stream(stream);
+  if (!for_narrow_layout(J, R, [&](auto l, auto r) {
+        hipLaunchKernelGGL((narrow_linear_bwd_kernel<l(), r()>), dim3(kNarrowBlocks), dim3(256), 0, s,
+                           reinterpret_cast<const float4*>(grad_out), x, workspace, units);
+      }))
+    return MLGNN_E_SHAPE;
   const int err = (int)hipGetLastError();
   if (err) return err;
   launch_reduce_partials(workspace, grad_w_b, kNarrowBlocks, (int)(J * (R + 1)), s);

@@ -14,6 +14,7 @@
 //
 // Deterministic: no atomics, fixed summation orders.
 #include "common.h"
+#include "launch.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
@@ -238,13 +239,13 @@ extern "C" int mlgnn_skinny_linear_fwd(const float* x, const float* w, const flo
                                        int64_t workspace_floats, int64_t M, int64_t J, int64_t K, void* stream) {
   if (!sk_ok(M, J, K)) return MLGNN_E_SHAPE;
   if (!x || !w || !y || !workspace) return MLGNN_E_NULL;
-  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w)) & 15) != 0) return MLGNN_E_ALIGN;
+  if (!aligned(x, w)) return MLGNN_E_ALIGN;
   int kps;
   const int splits = sk_plan(J, K, &kps);
   if (workspace_floats < (int64_t)splits * M * J) return MLGNN_E_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   constexpr int lds_bytes = (kSkM + kSkJ) * kSkLd * 4;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&skinny_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  if (const hipError_t e = allow_dynamic_lds(&skinny_fwd_kernel, lds_bytes); e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(skinny_fwd_kernel, dim3((unsigned)((J + kSkJ - 1) / kSkJ), (unsigned)splits), dim3(kSkThreads), lds_bytes, s,
                      x, w, bias, workspace, (int)M, (int)J, (int)K, kps);
   launch_reduce_partials(workspace, y, splits, (int)(M * J), s);          // K ranges in order: bitwise reproducible
@@ -255,9 +256,7 @@ extern "C" int mlgnn_skinny_linear_bwd(const float* grad_out, const float* x, co
                                        float* grad_b, int64_t M, int64_t J, int64_t K, void* stream) {
   if (!sk_ok(M, J, K)) return MLGNN_E_SHAPE;
   if (!grad_out || (grad_x && !w) || (grad_w && !x)) return MLGNN_E_NULL;
-  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(grad_x) |
-        reinterpret_cast<uintptr_t>(grad_w)) & 15) != 0)
-    return MLGNN_E_ALIGN;
+  if (!aligned(x, w, grad_x, grad_w)) return MLGNN_E_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   const unsigned kt = (unsigned)((K + kSkK - 1) / kSkK);
   if (grad_x) hipLaunchKernelGGL(skinny_dx_kernel, dim3(kt), dim3(kSkThreads), 0, s, grad_out, w, grad_x, (int)M, (int)J, (int)K);

@@ -22,6 +22,7 @@
 // the k-step loop that scales, splits and issues 3 MFMAs (v_mfma_f32_32x32x16_f16) per 32-column tile.
 // HBM-bound: reads N*R*4, writes N*J*4.
 #include "common.h"
+#include "launch.h"
 #include "dense_bf16.h"
 #include "mlgnn.h"
 
@@ -593,9 +594,7 @@ static int tallgemm_nt_any(const void* a, const void* bt, int bt_transposed, con
     if (tb_tiles_per_slice(R, J) == 0) return MLGNN_E_SHAPE;
     if (!a || !bt || !c || !workspace) return MLGNN_E_NULL;
     if (workspace_bytes < R * J * 2) return MLGNN_E_WORKSPACE;
-    if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(bt) | reinterpret_cast<uintptr_t>(workspace)) & 15) != 0 ||
-        ((reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(residual)) & 3) != 0)
-      return MLGNN_E_ALIGN;
+    if (!aligned(a, bt, workspace) || !aligned<4>(c, residual)) return MLGNN_E_ALIGN;
     return tallgemm_bf16(a, bt, bias, residual, c, workspace, N, R, J, (hipStream_t)stream);
   }
   if (!tg_dims_ok(R, J)) return MLGNN_E_SHAPE;
@@ -614,8 +613,7 @@ static int tallgemm_nt_any(const void* a, const void* bt, int bt_transposed, con
     if (!shift->lse || !shift->rowptr || !shift->gt || !shift->flag) return MLGNN_E_NULL;
   }
   if (workspace_bytes < R * J * 4 + kTgHeader * 16) return MLGNN_E_WORKSPACE;
-  if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(bt) | reinterpret_cast<uintptr_t>(workspace)) & 15) != 0)
-    return MLGNN_E_ALIGN;
+  if (!aligned(a, bt, workspace)) return MLGNN_E_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   if (shift) {
     int err0 = (int)hipMemsetAsync(shift->flag, 0, 16, s);
@@ -648,8 +646,9 @@ static int tallgemm_nt_any(const void* a, const void* bt, int bt_transposed, con
   bool launched = false;
 #define MLGNN_TG_LAUNCH2(JT_, KS_, LN_, POST_, SHIFT_)                                                 \
   {                                                                                                   \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tallgemm_kernel<JT_, KS_, LN_, POST_, SHIFT_>),  \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kTgMaxLds + 4096);          \
+    if (const hipError_t e_ = allow_dynamic_lds(&tallgemm_kernel<JT_, KS_, LN_, POST_, SHIFT_>, kTgMaxLds + 4096); \
+        e_ != hipSuccess)                                                                             \
+      return (int)e_;                                                                                 \
     hipLaunchKernelGGL((tallgemm_kernel<JT_, KS_, LN_, POST_, SHIFT_>), g, b, lds, s, p);              \
     launched = true;                                                                                  \
   }
@@ -746,9 +745,7 @@ extern "C" int mlgnn_tallgemm_dual(const float* a, const float* a2, const float*
   if (!a || (!a2 && R2 > 0) || !bt || !c || !workspace) return MLGNN_E_NULL;
   if (R2 == 0) a2 = a;                                    // (never dereferenced: every k-step comes from a)
   if (workspace_bytes < R * J * 4 + kTgHeader * 16) return MLGNN_E_WORKSPACE;
-  if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(a2) | reinterpret_cast<uintptr_t>(bt) |
-        reinterpret_cast<uintptr_t>(workspace)) & 15) != 0)
-    return MLGNN_E_ALIGN;
+  if (!aligned(a, a2, bt, workspace)) return MLGNN_E_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   const int n_frag_lanes = (int)(R / 16) * (int)(J / 32) * 64;
   hipLaunchKernelGGL(tallgemm_split_weight_kernel, dim3((n_frag_lanes + 255) / 256), dim3(256), 0, s, bt,
@@ -770,8 +767,9 @@ extern "C" int mlgnn_tallgemm_dual(const float* a, const float* a2, const float*
   bool launched = false;
 #define MLGNN_TG_DUAL(JT_, KS_)                                                                                  \
   if (!launched && J == 32 * JT_ && R == 16 * KS_) {                                                             \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tallgemm_kernel<JT_, KS_, 0, false, false, true>),  \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kTgMaxLds + 4096);                     \
+    if (const hipError_t e_ = allow_dynamic_lds(&tallgemm_kernel<JT_, KS_, 0, false, false, true>, kTgMaxLds + 4096); \
+        e_ != hipSuccess)                                                                                        \
+      return (int)e_;                                                                                            \
     hipLaunchKernelGGL((tallgemm_kernel<JT_, KS_, 0, false, false, true>), dim3(grid), dim3(kTgBlock), lds, s, p); \
     launched = true;                                                                                             \
   }
@@ -809,8 +807,7 @@ extern "C" int mlgnn_tallgemm_lnbwd(const float* go, const float* w, int w_trans
   if (N == 0) return (int)hipMemsetAsync(grad_gamma_beta, 0, 2 * J * sizeof(float), s);
   if (!go || !w || !xhat || !rstd || !gamma || !beta || !grad_h || !row_max_out || !workspace) return MLGNN_E_NULL;
   if (workspace_bytes < mlgnn_tallgemm_lnbwd_workspace_bytes(R, J)) return MLGNN_E_WORKSPACE;
-  if (((reinterpret_cast<uintptr_t>(go) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(workspace)) & 15) != 0)
-    return MLGNN_E_ALIGN;
+  if (!aligned(go, w, workspace)) return MLGNN_E_ALIGN;
   const int n_frag_lanes = (int)(R / 16) * (int)(J / 32) * 64;
   hipLaunchKernelGGL(tallgemm_split_weight_kernel, dim3((n_frag_lanes + 255) / 256), dim3(256), 0, s, w,
                      (f16x8*)workspace, (int)J, (int)R, w_transposed);
@@ -842,8 +839,8 @@ extern "C" int mlgnn_tallgemm_lnbwd(const float* go, const float* w, int w_trans
     bool launched = false;
 #define MLGNN_TG_LNBWD(JT_, KS_)                                                                      \
   if (!launched && J == 32 * JT_ && R == 16 * KS_) {                                                  \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tallgemm_kernel<JT_, KS_, 3>),           \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kTgMaxLds + 4096);          \
+    if (const hipError_t e_ = allow_dynamic_lds(&tallgemm_kernel<JT_, KS_, 3>, kTgMaxLds + 4096); e_ != hipSuccess) \
+      return (int)e_;                                                                                 \
     hipLaunchKernelGGL((tallgemm_kernel<JT_, KS_, 3>), g, b, lds, s, p);                               \
     launched = true;                                                                                  \
   }

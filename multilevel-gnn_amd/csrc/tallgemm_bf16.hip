@@ -16,6 +16,7 @@
 // contiguous bytes of a row (2-byte stores of the natural layout would touch 64-byte pieces).  The permutation is
 // free: it only changes which weight row goes where in the LDS image.
 #include "common.h"
+#include "launch.h"
 #include "dense_bf16.h"
 #include "mlgnn.h"
 
@@ -213,25 +214,18 @@ int tallgemm_bf16(const void* a, const void* bt, const float* bias, const void* 
   const int per_slice = 256 / slices > 0 ? 256 / slices : 1;    // one workgroup per CU in total
   if (gx > per_slice) gx = per_slice;
   const dim3 pg((n_img + 255) / 256), pb(256), g(gx, slices), b(kTbBlock);
-#define MLGNN_TB_CASE(JT_)                                                                                   \
-  case JT_:                                                                                                  \
-    hipLaunchKernelGGL((tallgemm_bf16_pack_kernel<JT_>), pg, pb, 0, s, (const uint4*)bt, (uint4*)workspace,  \
-                       (int)J, (int)R);                                                                      \
-    if (lse) {                                                                                               \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tallgemm_bf16_kernel<JT_, true>),            \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kTbMaxLds);                      \
-      hipLaunchKernelGGL((tallgemm_bf16_kernel<JT_, true>), g, b, lds, s, p);                                \
-    } else {                                                                                                 \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tallgemm_bf16_kernel<JT_, false>),           \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kTbMaxLds);                      \
-      hipLaunchKernelGGL((tallgemm_bf16_kernel<JT_, false>), g, b, lds, s, p);                               \
-    }                                                                                                        \
-    break;
-  switch (jt) {
-    MLGNN_TB_CASE(1) MLGNN_TB_CASE(2) MLGNN_TB_CASE(4) MLGNN_TB_CASE(8)
-    default: return MLGNN_E_SHAPE;
-  }
-#undef MLGNN_TB_CASE
+  hipError_t lds_err = hipSuccess;
+  if (!dispatch_int<1, 2, 4, 8>(jt, [&](auto t) {
+        hipLaunchKernelGGL((tallgemm_bf16_pack_kernel<t()>), pg, pb, 0, s, (const uint4*)bt, (uint4*)workspace, (int)J, (int)R);
+        auto run = [&](auto kernel) {
+          lds_err = allow_dynamic_lds(kernel, kTbMaxLds);
+          if (lds_err == hipSuccess) hipLaunchKernelGGL(kernel, g, b, lds, s, p);
+        };
+        if (lse) run(&tallgemm_bf16_kernel<t(), true>);
+        else run(&tallgemm_bf16_kernel<t(), false>);
+      }))
+    return MLGNN_E_SHAPE;
+  if (lds_err != hipSuccess) return (int)lds_err;
   return (int)hipGetLastError();
 }
 
@@ -250,11 +244,8 @@ extern "C" int mlgnn_tallgemm_bf16_shift(const void* a, const void* bt, const fl
   if (!mlgnn_tallgemm_bf16_shift_supported(N, R, J)) return MLGNN_E_SHAPE;
   if (!a || !bt || !lse || !c || !grad_shifted || !shift_flag || !workspace) return MLGNN_E_NULL;
   if (workspace_bytes < R * J * 2) return MLGNN_E_WORKSPACE;
-  if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(bt) | reinterpret_cast<uintptr_t>(workspace)) & 15) != 0 ||
-      ((reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(grad_shifted)) & 3) != 0 ||
-      (reinterpret_cast<uintptr_t>(lse) & 7) != 0)
-    return MLGNN_E_ALIGN;
-  hipStream_t s = (hipStream_t)stream;
+  if (!aligned(a, bt, workspace) || !aligned<4>(c, grad_shifted) || !aligned<8>(lse)) return MLGNN_E_ALIGN;
+  hipStream_t s = as_stream(stream);
   int err = (int)hipMemsetAsync(shift_flag, 0, 16, s);
   if (err) return err;
   return tallgemm_bf16(a, bt, nullptr, nullptr, c, workspace, N, R, J, s, lse, grad_shifted, shift_flag);

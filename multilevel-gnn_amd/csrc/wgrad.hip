@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "launch.h"
 #include "dense_bf16.h"
 #include "mlgnn.h"
 
@@ -469,7 +470,7 @@ extern "C" int mlgnn_linear_wgrad(const void* grad_out, const void* x, const flo
     if (N == 0) return (int)hipMemsetAsync(grad_w_b, 0, (size_t)(M * K + M) * sizeof(float), (hipStream_t)stream);
     if (!grad_out || !x) return MLGNN_E_NULL;
     if (workspace_floats < (int64_t)slabs * (M * K + M)) return MLGNN_E_WORKSPACE;
-    if (((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(x)) & 15) != 0) return MLGNN_E_ALIGN;
+    if (!aligned(grad_out, x)) return MLGNN_E_ALIGN;
     return linear_wgrad_bf16(grad_out, x, grad_w_b, workspace, N, M, K, (hipStream_t)stream);
   }
   if (dtype != MLGNN_DTYPE_F32) return MLGNN_E_DTYPE;

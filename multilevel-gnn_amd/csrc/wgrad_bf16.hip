@@ -17,6 +17,7 @@
 // Traffic: every M block streams x once and every K block streams grad_out once -- 2 passes over one of them at
 // 512 x 256 -- against 2 N M K FLOP that take a fifth of that time on the bf16 matrix cores: HBM-bound.
 #include "common.h"
+#include "launch.h"
 #include "dense_bf16.h"
 #include "mlgnn.h"
 
@@ -211,8 +212,8 @@ int linear_wgrad_bf16(const void* grad_out, const void* x, float* grad_w_b, floa
 #define MLGNN_WB_CASE(TM_, TK_)                                                                               \
   if (tm == TM_ && tk == TK_) {                                                                               \
     const int lds = 2 * kWbStage * (wb_stride(64 * TM_) + wb_stride(128 * TK_));                              \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_wgrad_bf16_kernel<TM_, TK_>),            \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);                               \
+    if (const hipError_t e_ = allow_dynamic_lds(&linear_wgrad_bf16_kernel<TM_, TK_>, lds); e_ != hipSuccess)  \
+      return (int)e_;                                                                                         \
     hipLaunchKernelGGL((linear_wgrad_bf16_kernel<TM_, TK_>), grid, block, lds, s, a);                         \
   }
   MLGNN_WB_CASE(4, 2) MLGNN_WB_CASE(4, 1) MLGNN_WB_CASE(2, 2) MLGNN_WB_CASE(2, 1) MLGNN_WB_CASE(1, 2) MLGNN_WB_CASE(1, 1)
