@@ -10,7 +10,7 @@
 //             (A x) W^T = A (x W^T): the [n,C] neighbour mean never exists, only the [n,O] projection
 //   backward  g = (gy - y <y, gy>) * rinv;   gP = A^T (g / deg);
 //             gx = gP W_rel + g W_root;   gW_rel = gP^T x;   gW_root = g^T x;   gb = colsum g;
-//             gA_ij = (<g_i, P_j> - [rowsum_i > 1] c_i) / deg_i,   c_i = sum_j A_ij <g_i, P_j> / deg_i
+//             gA_ij = (<g_i, P_j> - [rowsum_i >= 1] c_i) / deg_i,  c_i = sum_j A_ij <g_i, P_j> / deg_i
 // Every product runs on v_mfma_f32_16x16x4_f32 (exact fp32 FMA chains, 1e-4 parity) with operands read in
 // MFMA layout from global memory or LDS; weight gradients leave as one partial per workgroup and are summed in
 // a fixed order (reduce_partials).  Limits: n <= 160, C <= 128, O <= 64; the adjacency gradient (pooled
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(kDsBlock) void dense_sage_bwd_kernel(const DsArgs p
       float c = lane < n ? ab[(size_t)r * n + lane] * M(r, lane) : 0.f;      // n <= 48 < 64 lanes
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
-      const float ci = raw[r] > 1.0f ? c / deg[r] : 0.f;                     // clamp(rowsum, 1) passes gradient above 1
+      const float ci = raw[r] >= 1.0f ? c / deg[r] : 0.f;                    // clamp(rowsum, min=1) passes gradient from 1 on
       if (lane < n) stored_write<T>(p.gadj, ga_off + (size_t)r * n + lane, (M(r, lane) - ci) / deg[r]);
     }
   }

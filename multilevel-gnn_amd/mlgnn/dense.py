@@ -727,7 +727,9 @@ class _DiffPoolFused(torch.autograd.Function):
         B, N, C = z.shape
         K = S.shape[2]
         batched = adj.dim() == 3 and adj.shape[0] == B and B > 1
-        coef = torch.stack([g_link.float() / (adj.numel() * norm), g_ent.float() / (B * N)]).contiguous()
+        # A == S S^T exactly (norm 0): torch.norm has a zero gradient there, and 0/0 would turn every gradient into NaN
+        c_link = torch.where(norm > 0, g_link.float() / (adj.numel() * norm), 0.0)
+        coef = torch.stack([c_link, g_ent.float() / (B * N)]).contiguous()
         gz = torch.empty_like(z)
         gs = torch.empty_like(S)
         need_adj = ctx.needs_input_grad[1]

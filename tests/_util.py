@@ -106,3 +106,34 @@ def assert_close(a, b, tol=1e-4, what="", elementwise=False):
         return
     err = float((a - b).abs().max())
     assert err <= tol * scale, "%s: max|diff|=%.3e > %.1e*%.3g" % (what, err, tol, scale)
+
+
+def own_scale_excess(a, b, tol=1e-4, frac=1.0):
+    """The elementwise form of :func:`assert_close` WITHOUT its ``max(1, .)`` floor: every entry on its own,
+    ``|a-b| <= frac * (tol * |b| + 0.1 * tol * |b|_inf)`` -- a tensor of size 1e-6 (the link-loss gradient of DiffPool) is
+    held relative to itself.  Where ``b`` is identically zero ``a`` must be exactly zero.  -> ``None`` when held, else a
+    description of the worst entry (``frac``: the share of the bound that is allowed)."""
+    a, b = torch.as_tensor(a).detach().double().cpu(), torch.as_tensor(b).detach().double().cpu()
+    if a.shape != b.shape:
+        return "shape %s vs %s" % (tuple(a.shape), tuple(b.shape))
+    if a.numel() == 0:
+        return None
+    if not bool(torch.isfinite(b).all()):
+        return "the reference is not finite"
+    if not bool(torch.isfinite(a).all()):
+        return "%d non-finite entries" % int((~torch.isfinite(a)).sum())
+    if not bool(b.any()):
+        return None if not bool(a.any()) else "reference identically zero, got max |%.3e|" % float(a.abs().max())
+    bound = frac * (tol * b.abs() + 0.1 * tol * float(b.abs().max()))
+    ratio = (a - b).abs() / bound
+    worst = int(ratio.argmax())
+    if float(ratio.max()) <= 1.0:
+        return None
+    return "entry %d: |%.6e - %.6e| = %.2f x the bound %.3e (|ref|_inf %.3e, tol %.1e, share %.2f)" % (
+        worst, float(a.flatten()[worst]), float(b.flatten()[worst]), float(ratio.max()), float(bound.flatten()[worst]),
+        float(b.abs().max()), tol, frac)
+
+
+def assert_close_own_scale(a, b, tol=1e-4, what="", frac=1.0):
+    msg = own_scale_excess(a, b, tol, frac)
+    assert msg is None, "%s: %s" % (what, msg)

@@ -14,7 +14,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _util import assert_close
+from _util import assert_close, assert_close_own_scale
 from oracle import gcn_lib as G
 from oracle import models as OM
 from oracle import primitives as P
@@ -34,6 +34,7 @@ class Entry:
     params: tuple = ()                      # shared by both uses in the double-use check
     tol: float = 1e-4
     norm_tol: bool = False                  # relative Frobenius error instead of the max form (bf16 product chains)
+    own_scale: bool = False                 # elementwise, relative to the gradient's own maximum (no max(1, .) floor)
     use: tuple = None                       # outputs that get a cotangent (default: all)
     patch: dict = field(default_factory=dict)   # mlgnn.ops switches for the case
     dtype: torch.dtype = torch.float32
@@ -430,6 +431,11 @@ REGISTRY = {
     "diff_pool": Entry("_DiffPoolFused", _dpool_build(3, 37, 10, 32), ("z", "adj", "s"), _dpool_call, _dpool_ref),
     "diff_pool-x-only": Entry("_DiffPoolFused", _dpool_build(3, 37, 10, 32), ("z", "adj", "s"), _dpool_call, _dpool_ref,
                               use=(0,)),
+    # the two losses alone: gradients of 1e-3 .. 1e-5 under the scalar cotangent of 100, held against their own scale
+    "diff_pool-link-only": Entry("_DiffPoolFused", _dpool_build(3, 37, 10, 32), ("z", "adj", "s"), _dpool_call, _dpool_ref,
+                                 use=(2,), own_scale=True),
+    "diff_pool-ent-only": Entry("_DiffPoolFused", _dpool_build(3, 37, 10, 32), ("z", "adj", "s"), _dpool_call, _dpool_ref,
+                                use=(3,), own_scale=True),
     "diff_pool_large-bf16": Entry("_DiffPoolLarge", _dpool_build(1, 256, 128, 128, True), ("z", "adj", "s"), _dpool_call,
                                   _dpool_ref, tol=2.0 ** -6, norm_tol=True, dtype=BF16),
     "diff_pool_large-bf16-x-only": Entry("_DiffPoolLarge", _dpool_build(1, 256, 128, 128, True), ("z", "s"), _dpool_call,
@@ -604,6 +610,8 @@ def _check(entry, got, ref, what):
         # softmax rows summing to one -- leaves bf16 rounding noise, which is held to 2^-6 * 1e-3 absolute instead)
         err = float(torch.linalg.norm(got.double().cpu() - ref)) / max(float(torch.linalg.norm(ref)), 1e-3)
         assert err <= entry.tol, (what, err)
+    elif entry.own_scale:
+        assert_close_own_scale(got, ref, entry.tol, what)
     else:
         assert_close(got, ref, entry.tol, what)
 
