@@ -988,6 +988,27 @@ int mlgnn_pool_flatten_bwd(const float* grad_out, const uint8_t* keep, float kee
                            int64_t B, int64_t H, int64_t W, int64_t C, int64_t ph, int64_t pw, void* stream);
 
 /*
+ * The MMD term of the VAE pre-training loss (csrc/mmd.hip), fp32, for all pathways at once: one launch per direction,
+ * one workgroup per pathway, both operands of a pathway in LDS.
+ *   z, prior [B, P, H]: the latent and the prior draw; pathway p owns the n = B rows z[:, p, :] and prior[:, p, :].
+ *   kind 0 (imq): k(a, b) = c / (c_eps + |a - b|^2), each term the sum over the pairs i != j;
+ *   kind 1 (rbf): k(a, b) = exp(-(|a - b|^2 / H) / c), each term the mean over all n^2 pairs (diagonal included);
+ *   anything else MLGNN_E_MODE.  c = 2 H z_var and c_eps = 1e-7 + c are formed in double by the caller.
+ *   mlgnn_mmd_fwd: terms [P, 3] = (T_pp, T_zz, T_pz) or NULL (not wanted), mmd [P] = T_pp + T_zz - 2 T_pz.
+ *   mlgnn_mmd_bwd: grad_z [B, P, H] = grad_mmd[p] * d mmd_p / d z, every element written exactly once; the kernel values
+ *     are recomputed from z and prior (nothing else is saved); prior has no gradient.
+ * Squared distances are sums of (a_d - b_d)^2; plain IEEE arithmetic (NaN and Inf travel as through the torch lines); no
+ * atomics, reductions in a fixed order: bitwise reproducible.  Shapes (mlgnn_mmd_supported): B >= 0, P >= 0,
+ * 1 <= H <= 256, B <= 256, B * H <= 8192, z below 4 GiB; MLGNN_E_SHAPE for anything else (shape errors are reported
+ * before NULL operands); B = 0 or P = 0 is a no-op.
+ */
+int mlgnn_mmd_supported(int64_t B, int64_t P, int64_t H);
+int mlgnn_mmd_fwd(const float* z, const float* prior, float* terms, float* mmd, int kind, float c_eps, float c,
+                  int64_t B, int64_t P, int64_t H, void* stream);
+int mlgnn_mmd_bwd(const float* z, const float* prior, const float* grad_mmd, float* grad_z, int kind, float c_eps, float c,
+                  int64_t B, int64_t P, int64_t H, void* stream);
+
+/*
  * Measurement aid (bench.py: the box's streaming ceiling next to the 8 TB/s spec peak): dst = src, 16 bytes per lane,
  * non_temporal != 0: non-temporal loads and stores.  bytes a multiple of 16, 16-byte aligned pointers.
  */

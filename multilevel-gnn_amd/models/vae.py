@@ -8,7 +8,8 @@ Same constructor, methods, return values and ``state_dict`` keys.  Level 0 (Grap
 projection run on the CSR / segment kernels, the pooled levels on the fused DiffPool / DenseSAGE kernels.  Two
 loops of the reference are replaced by batched forms with identical results: the per-pathway ``corrcoef`` loop of
 the encoder loss (438 launches -> one batched covariance) and, for the uniform-width ``foreach`` decoder, the
-438-block Python loop (-> one batched GEMM + one gathered row-dot over all output genes).
+438-block Python loop (-> one batched GEMM + one gathered row-dot over all output genes).  A third, the per-pathway
+``compute_mmd`` loop of ``vae_loss``, is one launch per direction (``mlgnn.mmd``) on one ``[B, 438, H]`` prior draw.
 ``get_embedding_similarity`` (spreadsheet ETL) is outside the accelerated path.
 """
 import math
@@ -17,6 +18,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from mlgnn import mmd as mlgnn_mmd
 from mlgnn.pool_flatten import module_pool_flatten
 from mlgnn.project import segment_project
 from .diff_pooling import DiffPool
@@ -250,12 +252,21 @@ class VAE(_PretrainBase):
                                   "accelerated path")
 
     # ------------------------------------------------------------------ losses
-    def vae_loss(self, x_predict, x, z, q_z):
+    def vae_loss(self, x_predict, x, z, q_z, prior=None):
+        """``prior`` ([B, P, H], optional): the prior draw of the MMD term, pathway ``i`` reads ``prior[:, i, :]``.
+        Without it the kernel path draws one ``randn_like(z)`` and the loop one ``[B, H]`` draw per pathway."""
         n = x.size(0)
         recons_loss = F.mse_loss(x_predict, x)
-        mmd_loss = torch.stack([self.compute_mmd(z[:, i, :]) for i in range(z.shape[1])]).mean()
-        kld_loss = torch.distributions.kl_divergence(q_z, torch.distributions.Normal(0, 1.)).sum(-1).mean()
         a = self.args
+        if mlgnn_mmd.ENABLED and a.mmd_kernel_type in mlgnn_mmd.KINDS and mlgnn_mmd.mmd_supported(z):
+            # all pathways in one launch per direction (csrc/mmd.hip)
+            mmd_loss = mlgnn_mmd.mmd_per_pathway(z, torch.randn_like(z) if prior is None else prior,
+                                                 a.mmd_kernel_type, a.z_var).mean()
+        else:
+            mlgnn_mmd.MMD_STATS["torch"] += 1
+            mmd_loss = torch.stack([self.compute_mmd(z[:, i, :], None if prior is None else prior[:, i, :])
+                                    for i in range(z.shape[1])]).mean()
+        kld_loss = torch.distributions.kl_divergence(q_z, torch.distributions.Normal(0, 1.)).sum(-1).mean()
         loss = a.mmd_beta * recons_loss + (1. - a.mmd_alpha) * a.kld_weight * kld_loss + \
             (a.mmd_alpha + a.mmd_reg_weight - 1.) / (n * (n - 1)) * mmd_loss
         return {'loss': loss, 'Reconstruction_Loss': recons_loss, 'MMD': mmd_loss, 'KLD': -kld_loss}
@@ -293,9 +304,9 @@ class VAE(_PretrainBase):
         kernel = c / (eps + c + (x1 - x2).pow(2).sum(dim=-1))
         return kernel.sum() - kernel.diag().sum()           # off-diagonal mass
 
-    def compute_mmd(self, z):
+    def compute_mmd(self, z, prior=None):
         z = z.reshape(-1, z.shape[-1])
-        prior = torch.randn_like(z)
+        prior = torch.randn_like(z) if prior is None else prior.reshape(-1, z.shape[-1])
         return self.compute_kernel(prior, prior).mean() + self.compute_kernel(z, z).mean() - \
             2 * self.compute_kernel(prior, z).mean()
 
