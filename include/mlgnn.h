@@ -1009,6 +1009,38 @@ int mlgnn_mmd_bwd(const float* z, const float* prior, const float* grad_mmd, flo
                   int64_t B, int64_t P, int64_t H, void* stream);
 
 /*
+ * The per-pathway decoders of the pre-training models (csrc/pathway_decoder.hip), fp32: P two-layer MLPs with ragged
+ * widths, one launch per direction, one workgroup per block.
+ *   h [B, P, H]; block p maps the rows h[:, p, :] to out[:, out_off[p] : out_off[p + 1]] = relu(h_p W1_p^T + b1_p) W2_p^T + b2_p.
+ *   The parameters are packed: w1 holds the blocks [hid_p, H] row-major, block p at H * hid_off[p]; b1 block p at
+ *   hid_off[p]; w2 the blocks [n_p, hid_p] row-major, block p at w2_off[p]; b2 block p at out_off[p].  hid_off, out_off,
+ *   w2_off: int64 device arrays of P + 1 entries (hid_p = hid_off[p + 1] - hid_off[p], n_p likewise); out is [B, N],
+ *   N = total_out = out_off[P].  max_hid >= every hid_p and max_out >= every n_p size the launch; a block whose table
+ *   entries do not fit them (or 1 <= hid_p, 0 <= n_p, out_off[p + 1] <= N) is skipped, not read.
+ *   mlgnn_pathway_decoder_fwd: writes every element of the columns of every block (n_p = 0: none).
+ *   mlgnn_pathway_decoder_bwd: g [B, N] = d out; dh [B, P, H], dw1, db1, dw2, db2 (packed like the parameters), each NULL
+ *     when not wanted (all NULL: nothing is launched); every element of a wanted output is written exactly once, a block
+ *     with n_p = 0 writes zeros to its dh slab, dw1 and db1.  hid is recomputed from h (nothing else is saved); a unit
+ *     whose hid is exactly 0 gets no gradient (torch's relu backward).
+ * Plain fp32 multiply-adds, every sum in index order; no atomics: bitwise reproducible.
+ * Shapes (mlgnn_pathway_decoder_supported): 0 <= B <= 256, P >= 0, 1 <= H <= 128, 1 <= max_hid <= 256,
+ * 0 <= max_out <= total_out, the backward's LDS image within 160 KiB,
+ *   B * (max(H4, 16) + hid4) + max(B * hid4, 2112) <= 40960   (H4, hid4 = H, max_hid rounded up to a multiple of 4)
+ * -- B <= 64 with H <= 128 and max_hid <= 256 fits, and so does B <= 256 with H, max_hid <= 32; n_p is not limited --, and
+ * every tensor below 2^31 elements (B * P * H, B * total_out, P * max_hid * H, total_out * max_hid).  MLGNN_E_SHAPE for
+ * anything else (shape errors are reported before NULL operands); B = 0 or P = 0 is a no-op.
+ */
+int mlgnn_pathway_decoder_supported(int64_t B, int64_t P, int64_t H, int64_t max_hid, int64_t max_out, int64_t total_out);
+int mlgnn_pathway_decoder_fwd(const float* h, const float* w1, const float* b1, const float* w2, const float* b2,
+                              const int64_t* hid_off, const int64_t* out_off, const int64_t* w2_off, float* out,
+                              int64_t B, int64_t P, int64_t H, int64_t max_hid, int64_t max_out, int64_t total_out,
+                              void* stream);
+int mlgnn_pathway_decoder_bwd(const float* h, const float* w1, const float* b1, const float* w2, const float* g,
+                              const int64_t* hid_off, const int64_t* out_off, const int64_t* w2_off, float* dh, float* dw1,
+                              float* db1, float* dw2, float* db2, int64_t B, int64_t P, int64_t H, int64_t max_hid,
+                              int64_t max_out, int64_t total_out, void* stream);
+
+/*
  * Measurement aid (bench.py: the box's streaming ceiling next to the 8 TB/s spec peak): dst = src, 16 bytes per lane,
  * non_temporal != 0: non-temporal loads and stores.  bytes a multiple of 16, 16-byte aligned pointers.
  */

@@ -120,6 +120,9 @@ SIGNATURES = {
     "mlgnn_mmd_supported": (_INT, [_I64] * 3),
     "mlgnn_mmd_fwd": (_INT, [_P, _P, _P, _P, _INT, _F, _F] + [_I64] * 3 + [_P]),
     "mlgnn_mmd_bwd": (_INT, [_P, _P, _P, _P, _INT, _F, _F] + [_I64] * 3 + [_P]),
+    "mlgnn_pathway_decoder_supported": (_INT, [_I64] * 6),
+    "mlgnn_pathway_decoder_fwd": (_INT, [_P] * 9 + [_I64] * 6 + [_P]),
+    "mlgnn_pathway_decoder_bwd": (_INT, [_P] * 13 + [_I64] * 6 + [_P]),
     "mlgnn_stream_copy": (_INT, [_P, _P, _I64, _INT, _P]),
     "mlgnn_gemm_bf16_nt_workgroups": (_INT, [_I64, _I64, _INT]),
     "mlgnn_gemm_bf16_nt": (_INT, [_c.POINTER(_P), _c.POINTER(_P), _c.POINTER(_I64), _c.POINTER(_I64), _c.POINTER(_I64),

@@ -10,6 +10,8 @@ loops of the reference are replaced by batched forms with identical results: the
 the encoder loss (438 launches -> one batched covariance) and, for the uniform-width ``foreach`` decoder, the
 438-block Python loop (-> one batched GEMM + one gathered row-dot over all output genes).  A third, the per-pathway
 ``compute_mmd`` loop of ``vae_loss``, is one launch per direction (``mlgnn.mmd``) on one ``[B, 438, H]`` prior draw.
+The per-pathway decoders (``foreach`` and ``foreach_diffhidden``) run as one launch per direction too
+(``mlgnn.decoder``) where the kernels take the shape; the block loop and the batched form remain for the rest.
 ``get_embedding_similarity`` (spreadsheet ETL) is outside the accelerated path.
 """
 import math
@@ -18,6 +20,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from mlgnn import decoder as mlgnn_decoder
 from mlgnn import mmd as mlgnn_mmd
 from mlgnn.pool_flatten import module_pool_flatten
 from mlgnn.project import segment_project
@@ -69,6 +72,11 @@ class _PretrainBase(MultilevelGNN):
             # output gene g is produced by block _out_block[g] (blocks are concatenated in order)
             self.register_buffer("_out_block", torch.repeat_interleave(torch.arange(len(counts)), counts),
                                  persistent=False)
+            # where block i lives in the packed parameters of mlgnn.pathway_decoders (blocks in state_dict order)
+            tables = mlgnn_decoder.offset_tables([b[0].out_features for b in blocks], counts.tolist())
+            for name, table in zip(("_dec_hid_off", "_dec_out_off", "_dec_w2_off"), tables):
+                self.register_buffer(name, table, persistent=False)
+            self._dec_limits = mlgnn_decoder.table_limits(*tables)
 
     def _build_diff_pooling(self, args):
         if args.reorder_type == "diff_pooling":
@@ -118,6 +126,17 @@ class _PretrainBase(MultilevelGNN):
     def foreach_decoder(self, h):
         """``cat_i decoder[i](h[:, i, :])`` -> ``[B, n_genes]``."""
         blocks = list(self.decoder)
+        if mlgnn_decoder.ENABLED and h.is_cuda and h.dim() == 3 and h.shape[1] == len(blocks) \
+                and mlgnn_decoder.decoder_supported(h, *self._dec_limits):
+            # every block in one launch per direction (csrc/pathway_decoder.hip); the packing's backward is views, so
+            # the gradients land on the blocks' own parameters
+            w1 = torch.cat([b[0].weight.reshape(-1) for b in blocks])
+            b1 = torch.cat([b[0].bias for b in blocks])
+            w2 = torch.cat([b[2].weight.reshape(-1) for b in blocks])
+            b2 = torch.cat([b[2].bias for b in blocks])
+            return mlgnn_decoder.pathway_decoders(h, w1, b1, w2, b2, self._dec_hid_off, self._dec_out_off,
+                                                  self._dec_w2_off, limits=self._dec_limits)
+        mlgnn_decoder.DECODER_STATS["torch"] += 1
         if len({b[0].out_features for b in blocks}) != 1:            # ragged hidden widths: block by block
             return torch.cat([b(h[:, i, :]) for i, b in enumerate(blocks)], dim=-1)
         w1 = torch.stack([b[0].weight for b in blocks])              # [P, D, H]
