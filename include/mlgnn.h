@@ -1041,6 +1041,33 @@ int mlgnn_pathway_decoder_bwd(const float* h, const float* w1, const float* b1, 
                               int64_t max_out, int64_t total_out, void* stream);
 
 /*
+ * The VQ-VAE quantiser (csrc/vq.hip), fp32: nearest code word of every latent row, straight-through output, loss and
+ * both gradients; the [N, K] distance matrix is never formed.
+ *   z [N, D] the latent rows, codebook [K, D].
+ *   mlgnn_vq_fwd: index [N] (int32) = the code with the smallest squared distance, the distance being the fp32 sum of
+ *     (z_d - w_d)^2 (even and odd d each in index order, the two sums added) -- a function of the two rows' values alone.  torch.argmin's order: the lowest
+ *     index wins a tie, a NaN distance is below every number and the first NaN wins (a NaN row gets index 0).
+ *     out [N, D] = z + (codebook[index] - z), those two roundings.  partials [ceil(N / MLGNN_VQ_ROWS)]: workgroup b's sum
+ *     of (codebook[index[n]] - z[n])^2 over its rows n in [b, b + 1) * MLGNN_VQ_ROWS.  loss (one float, or NULL: not
+ *     wanted, one launch less) = m * beta + m with m = (sum of the partials) / (N D).
+ *   mlgnn_vq_bwd: index as mlgnn_vq_fwd wrote it (entries in [0, K); they are not checked).  g_out [N, D] = d out and
+ *     g_loss (one float on the device) = d loss, either may be NULL (= zero).  Outputs, each NULL when not wanted:
+ *       grad_z [N, D] = g_out + g_loss * 2 beta / (N D) * (z - codebook[index]);
+ *       grad_codebook [K, D] = g_loss * 2 / (N D) * sum over {n : index[n] = k}, in ascending n, of (codebook[k] - z[n]);
+ *     g_out does not enter it (the straight-through output has no path to the codebook); a code without members gets
+ *     zeros, and so does every code when g_loss is NULL.  Every element of a wanted output is written exactly once.
+ * No atomics, every reduction in a fixed order: bitwise reproducible.  Shapes (mlgnn_vq_supported): N >= 0,
+ * 1 <= K <= 65536, 1 <= D <= 128, N * D < 2^30 (z below 4 GiB); MLGNN_E_SHAPE for anything else (shape errors are
+ * reported before NULL operands); N = 0 is a no-op (nothing is read or written).
+ */
+#define MLGNN_VQ_ROWS 64
+int mlgnn_vq_supported(int64_t N, int64_t K, int64_t D);
+int mlgnn_vq_fwd(const float* z, const float* codebook, int32_t* index, float* out, float* partials, float* loss, float beta,
+                 int64_t N, int64_t K, int64_t D, void* stream);
+int mlgnn_vq_bwd(const float* z, const float* codebook, const int32_t* index, const float* g_out, const float* g_loss,
+                 float* grad_z, float* grad_codebook, float beta, int64_t N, int64_t K, int64_t D, void* stream);
+
+/*
  * Measurement aid (bench.py: the box's streaming ceiling next to the 8 TB/s spec peak): dst = src, 16 bytes per lane,
  * non_temporal != 0: non-temporal loads and stores.  bytes a multiple of 16, 16-byte aligned pointers.
  */

@@ -123,6 +123,9 @@ SIGNATURES = {
     "mlgnn_pathway_decoder_supported": (_INT, [_I64] * 6),
     "mlgnn_pathway_decoder_fwd": (_INT, [_P] * 9 + [_I64] * 6 + [_P]),
     "mlgnn_pathway_decoder_bwd": (_INT, [_P] * 13 + [_I64] * 6 + [_P]),
+    "mlgnn_vq_supported": (_INT, [_I64] * 3),
+    "mlgnn_vq_fwd": (_INT, [_P] * 6 + [_F] + [_I64] * 3 + [_P]),
+    "mlgnn_vq_bwd": (_INT, [_P] * 7 + [_F] + [_I64] * 3 + [_P]),
     "mlgnn_stream_copy": (_INT, [_P, _P, _I64, _INT, _P]),
     "mlgnn_gemm_bf16_nt_workgroups": (_INT, [_I64, _I64, _INT]),
     "mlgnn_gemm_bf16_nt": (_INT, [_c.POINTER(_P), _c.POINTER(_P), _c.POINTER(_I64), _c.POINTER(_I64), _c.POINTER(_I64),

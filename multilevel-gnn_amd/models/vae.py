@@ -12,6 +12,8 @@ the encoder loss (438 launches -> one batched covariance) and, for the uniform-w
 ``compute_mmd`` loop of ``vae_loss``, is one launch per direction (``mlgnn.mmd``) on one ``[B, 438, H]`` prior draw.
 The per-pathway decoders (``foreach`` and ``foreach_diffhidden``) run as one launch per direction too
 (``mlgnn.decoder``) where the kernels take the shape; the block loop and the batched form remain for the rest.
+The quantiser of ``VQ_VAE`` picks its codes, forms the straight-through output and the loss in one launch
+(``mlgnn.vq``) instead of building the ``[N, K]`` distance matrix; the torch lines remain for what the kernels refuse.
 ``get_embedding_similarity`` (spreadsheet ETL) is outside the accelerated path.
 """
 import math
@@ -22,6 +24,7 @@ import torch.nn.functional as F
 
 from mlgnn import decoder as mlgnn_decoder
 from mlgnn import mmd as mlgnn_mmd
+from mlgnn import vq as mlgnn_vq
 from mlgnn.pool_flatten import module_pool_flatten
 from mlgnn.project import segment_project
 from .diff_pooling import DiffPool
@@ -333,7 +336,8 @@ class VAE(_PretrainBase):
 class VectorQuantizer(nn.Module):
     """Nearest-code-word quantiser with commitment + embedding loss and a straight-through gradient (reference
     vq_vae.py:36-82, after the sonnet VQ-VAE).  The code vector is gathered by index instead of multiplying a one-hot
-    matrix by the codebook."""
+    matrix by the codebook.  fp32 device latents run on ``mlgnn.vector_quantize`` (``MLGNN_VQ_FUSED``); everything else
+    on the torch lines below."""
 
     def __init__(self, num_embeddings, embedding_dim, beta=0.25):
         super().__init__()
@@ -342,8 +346,12 @@ class VectorQuantizer(nn.Module):
         self.embedding.weight.data.uniform_(-1, 1)
 
     def forward(self, latents):
-        flat = latents.reshape(-1, self.D)
         w = self.embedding.weight
+        if mlgnn_vq.ENABLED and latents.is_cuda and mlgnn_vq.vq_supported(latents, w):
+            # index, straight-through output and loss in one launch, no [N, K] distance matrix (csrc/vq.hip)
+            return mlgnn_vq.vector_quantize(latents, w, self.beta)
+        mlgnn_vq.VQ_STATS["torch"] += 1
+        flat = latents.reshape(-1, self.D)
         dist = (flat ** 2).sum(1, keepdim=True) + (w ** 2).sum(1) - 2 * flat @ w.t()
         q = self.embedding(torch.argmin(dist, dim=1)).view(latents.shape)
         vq_loss = F.mse_loss(q.detach(), latents) * self.beta + F.mse_loss(q, latents.detach())
