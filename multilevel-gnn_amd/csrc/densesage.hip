@@ -11,10 +11,14 @@
 //   backward  g = (gy - y <y, gy>) * rinv;   gP = A^T (g / deg);
 //             gx = gP W_rel + g W_root;   gW_rel = gP^T x;   gW_root = g^T x;   gb = colsum g;
 //             gA_ij = (<g_i, P_j> - [rowsum_i >= 1] c_i) / deg_i,  c_i = sum_j A_ij <g_i, P_j> / deg_i
-// Every product runs on v_mfma_f32_16x16x4_f32 (exact fp32 FMA chains, 1e-4 parity) with operands read in
-// MFMA layout from global memory or LDS; weight gradients leave as one partial per workgroup and are summed in
-// a fixed order (reduce_partials).  Limits: n <= 160, C <= 128, O <= 64; the adjacency gradient (pooled
-// levels below the first, where A itself was produced by DiffPool) additionally needs n <= 48.
+// Every product runs on v_mfma_f32_16x16x4_f32 (exact fp32 FMA chains, 1e-4 parity).  The FORWARD fetches no operand from
+// global memory inside a tile loop: x, the two weights and then the adjacency are LDS images, filled from the flat global
+// block with 16-byte loads where the pointers allow; a wave keeps one column tile of the output for the whole kernel and
+// holds that tile's two weight fragments, read once from the weight images, in registers (tile_gemm.h).  The BACKWARD
+// reads g and gP from LDS and the adjacency, the weights and x in MFMA layout from global memory, per k-step of each tile
+// (the adjacency-gradient recompute of P included).  Weight gradients leave as one partial
+// per workgroup and are summed in a fixed order (reduce_partials).  Limits: n <= 160, C <= 128, O <= 64; the adjacency
+// gradient (pooled levels below the first, where A itself was produced by DiffPool) additionally needs n <= 48.
 #include "common.h"
 #include "launch.h"
 #include "mlgnn.h"
@@ -26,23 +30,29 @@ constexpr int kDsMaxN = 160, kDsMaxC = 128, kDsMaxO = 64, kDsMaxNAdj = 48;
 // 16 waves per pooled graph: the products are chains of small latency-bound tiles, and the tiles of one product
 // are independent -- more waves, not more work per wave, is what shortens the critical path
 constexpr int kDsBlock = 1024, kDsWaves = kDsBlock / kWave;
-constexpr int kDsSO = kDsMaxO + 1;            // odd LDS strides: row and transposed reads stay conflict free
 constexpr float kDsNormEps = 1e-12f;          // F.normalize eps
+// forward: a wave keeps one of the O/16 <= 4 column tiles, 16/4 = 4 waves share the n/16 <= 10 row tiles of it
+constexpr int kDsFwdTiles = 3;
+static_assert(kDsFwdTiles * (kDsWaves / (kDsMaxO / 16)) >= kDsMaxN / 16, "row tiles of one column tile per wave");
 
 struct DsArgs {                    // x, adj, weights, gy, y, y_out, gx, gadj: T (fp32 or bf16 storage); bias, rinv, ws: fp32
   const void* x; const void* adj; const void* w_rel; const void* w_root; const float* bias;
   const void* gy; const void* y; const float* rinv_in;
   void* y_out; float* rinv; void* gx; void* gadj; float* ws;
   int n; int C; int O; int adj_batched; int normalize; int ws_cols;
+  int vec16;                       // forward only: x, adj and the weights start on 16-byte boundaries, the images are
+                                   // filled with 16-byte loads (else scalar loads throughout)
 };
 
-// row sums of the adjacency: one wavefront per row, lanes across the columns (coalesced), shuffle reduction
+// row sums of the adjacency: one wavefront per row, lanes across the columns (coalesced), shuffle reduction.
+// `stride` is the row pitch of `ab`: n for the global block, the image's for the forward's LDS image (same lane order,
+// same sums)
 template <typename AB>
-__device__ __forceinline__ void ds_degrees(const AB ab, int n, float* deg, float* raw) {
+__device__ __forceinline__ void ds_degrees(const AB ab, int n, int stride, float* deg, float* raw) {
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   for (int r = wave; r < n; r += kDsWaves) {
     float s = 0.f;
-    for (int j = lane; j < n; j += kWave) s += ab[(size_t)r * n + j];
+    for (int j = lane; j < n; j += kWave) s += ab[(size_t)r * stride + j];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
     if (lane == 0) {
@@ -53,26 +63,78 @@ __device__ __forceinline__ void ds_degrees(const AB ab, int n, float* deg, float
 }
 
 // LDS images are sized by the ACTUAL (padded) widths of the call (dynamic shared memory, odd row strides so that row and
-// transposed reads stay conflict free): a 32-channel conv needs 42 KB forward / 44 KB backward instead of the 125 / 106 KB
-// of the largest supported shape, and two 16-wave workgroups then share a CU -- the 384 pooled graphs of a
-// BASELINE configs[1] batch run as one resident round instead of two.
-struct DsLds { int so, sx, np; };
+// transposed reads stay conflict free).  Forward: the x image [np][sx] and the two weight images [op][sx]; once the weight
+// fragments are in registers P [np][so] goes over them, and once x W^T is done the adjacency image [np][sa] goes over x.
+// An image's columns are padded with zeros to the next multiple of 32, the k extent of a tile_gemm block, so its readers
+// need no bound.  Backward: g and gP, [np][so] each.
+//   largest shape (n 160, C 128, O 64): forward 146 KB, backward 85 KB;   level 1 of the workload (146, 128, 37): 132 / 64 KB;
+//   a 32 -> 32 conv on 37 nodes: 19 KB / 29 KB with the adjacency gradient.
+struct DsLds { int so, sx, sa, np, op; };
 __host__ __device__ inline DsLds ds_lds(int n, int C, int O) {
   DsLds l;
   l.np = (n + 15) & ~15;
-  l.so = ((O + 15) & ~15) + 1;
-  l.sx = C + 1 + (C & 1);                      // odd
+  l.op = (O + 15) & ~15;
+  l.so = l.op + 1;
+  l.sx = ((C + 31) & ~31) + 1;
+  l.sa = ((n + 31) & ~31) + 1;
   return l;
+}
+// forward, in floats, without deg: [x image | W_rel image | W_root image] until the weight fragments are in registers,
+// then [adjacency image ... P]: P sits at the end, the adjacency image at the start
+__host__ __device__ inline int ds_fwd_floats(const DsLds& l) {
+  const int first = l.np * l.sx + 2 * l.op * l.sx, then = l.np * (l.sx > l.sa ? l.sx : l.sa) + l.np * l.so;
+  return first > then ? first : then;
 }
 inline size_t ds_fwd_lds_bytes(int n, int C, int O) {
   const DsLds l = ds_lds(n, C, O);
-  return ((size_t)l.np * l.so + (size_t)l.np * l.sx + l.np) * 4;
+  return ((size_t)ds_fwd_floats(l) + l.np) * 4;
 }
 inline size_t ds_bwd_lds_bytes(int n, int C, int O, bool adj_grad) {
   const DsLds l = ds_lds(n, C, O);
   size_t f = (size_t)2 * l.np * l.so + 2 * l.np;
   if (adj_grad) f += (size_t)l.np * l.so + (size_t)l.np * (l.np + 1);
   return f * 4;
+}
+
+// elements [first, first + V * count) of the flat [rows][cols] block at src -> img[r * stride + c], V per load.  One
+// integer division per thread; after it (r, c) advance by the block's constant step.
+template <typename T, int V>
+__device__ __forceinline__ void ds_stage_run(float* img, int stride, const T* src, int cols, int first, int count) {
+  const int step = V * kDsBlock, dr = step / cols, dc = step - dr * cols;
+  int e = first + V * (int)threadIdx.x;
+  int r = e / cols, c = e - r * cols;
+  for (int i = threadIdx.x; i < count; i += kDsBlock, e += step) {
+    float v[V];
+    load_t<T, V>(v, src + e);
+    int rr = r, cc = c;
+#pragma unroll
+    for (int q = 0; q < V; ++q) {
+      img[rr * stride + cc] = v[q];
+      if (++cc == cols) { cc = 0; ++rr; }
+    }
+    c += dc; r += dr;
+    if (c >= cols) { c -= cols; ++r; }
+  }
+}
+
+// The LDS image [rows_p][stride] of one graph's flat [rows][cols] block: rows past `rows` and columns cols .. cols_p - 1
+// are zero.  n = 146 or 37 leaves rows, and for 37 whole graphs, only 4-byte aligned, so the image is filled from the flat
+// block and not row by row: scalar loads up to the first 16-byte boundary, 16-byte loads, a scalar tail (vec16), or scalar
+// loads throughout.
+template <typename T>
+__device__ __forceinline__ void ds_stage(float* img, int stride, const T* src, int rows, int cols, int rows_p,
+                                         int cols_p, int vec16) {
+  constexpr int V = 16 / (int)sizeof(T);
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int total = rows * cols;
+  int head = total;
+  if (vec16) head = min(total, (int)(((0 - reinterpret_cast<uintptr_t>(src)) & 15) / sizeof(T)));
+  const int nvec = (total - head) / V;
+  ds_stage_run<T, 1>(img, stride, src, cols, 0, head);
+  if (nvec > 0) ds_stage_run<T, V>(img, stride, src, cols, head, nvec);
+  ds_stage_run<T, 1>(img, stride, src, cols, head + V * nvec, total - head - V * nvec);
+  for (int r = wave; r < rows_p; r += kDsWaves)
+    for (int c = (r < rows ? cols : 0) + lane; c < cols_p; c += kWave) img[r * stride + c] = 0.f;
 }
 
 template <typename T>
@@ -82,60 +144,84 @@ __global__ __launch_bounds__(kDsBlock) void dense_sage_fwd_kernel(const DsArgs p
   const int lane = tid & (kWave - 1), wave = tid / kWave;
   const int n = p.n, C = p.C, O = p.O;
   const DsLds L = ds_lds(n, C, O);
-  const int SO = L.so, SX = L.sx;
-  float* Pm_ = ds_smem;                        // [NP][SO]  x W_rel^T, then the un-normalised output
-  float* Xm_ = Pm_ + (size_t)L.np * SO;        // [NP][SX]  the pooled graph's features, staged once (both products read them)
-  float* deg = Xm_ + (size_t)L.np * SX;        // [NP]
+  const int SO = L.so, SX = L.sx, SA = L.sa;
+  float* Xm_ = ds_smem;                        // [NP][SX]  the pooled graph's features, staged once (both products read them)
+  float* Wr_ = Xm_ + (size_t)L.np * SX;        // [OP][SX]  W_rel and W_root, from coalesced loads, until every wave holds
+  float* Wt_ = Wr_ + (size_t)L.op * SX;        // [OP][SX]  its two fragments
+  float* Am_ = Xm_;                            // [NP][SA]  then the adjacency, in the region x has vacated
+  float* deg = ds_smem + ds_fwd_floats(L);     // [NP]
+  float* Pm_ = deg - (size_t)L.np * SO;        // [NP][SO]  x W_rel^T, then the un-normalised output (over the weight images)
 #define P(r, c) Pm_[(r) * SO + (c)]
 #define X(r, c) Xm_[(r) * SX + (c)]
-  const StoredIn<T> xb{static_cast<const T*>(p.x) + (size_t)b * n * C};
-  const StoredIn<T> ab{static_cast<const T*>(p.adj) + (p.adj_batched ? (size_t)b * n * n : 0)};
-  const StoredIn<T> w_rel{static_cast<const T*>(p.w_rel)}, w_root{static_cast<const T*>(p.w_root)};
+#define A(r, c) Am_[(r) * SA + (c)]
+  const T* xg = static_cast<const T*>(p.x) + (size_t)b * n * C;
+  const T* ag = static_cast<const T*>(p.adj) + (p.adj_batched ? (size_t)b * n * n : 0);
   const int NP = (n + 15) & ~15, OP = (O + 15) & ~15;
   const int Nt = NP / 16, Ot = OP / 16;
   const int l15 = lane & 15, lq = lane >> 4;
+  // tile -> wave: the column tile j0 is this wave's for the whole kernel (its two weight fragments are loaded once, and
+  // x W_root^T stays in registers until the epilogue); the kDsWaves / Ot waves of a column tile share its row tiles
+  const int wpc = kDsWaves / Ot, j0 = (wave % Ot) * 16, first = wave / Ot;
+  const bool active = first < wpc;
 
-  ds_degrees(ab, n, deg, nullptr);
-  for (int idx = tid; idx < NP * C; idx += kDsBlock) {               // coalesced; rows past n are zero
-    const int r = idx / C, c = idx % C;
-    X(r, c) = r < n ? xb[idx] : 0.f;
-  }
+  ds_stage<T>(Xm_, SX, xg, n, C, NP, SX - 1, p.vec16);
+  ds_stage<T>(Wr_, SX, static_cast<const T*>(p.w_rel), O, C, OP, SX - 1, p.vec16);
+  ds_stage<T>(Wt_, SX, static_cast<const T*>(p.w_root), O, C, OP, SX - 1, p.vec16);
   __syncthreads();
-  // ---- P = x W_rel^T  [n, O] ----------------------------------------------------------------------
-  for (int t = wave; t < Nt * Ot; t += kDsWaves) {
-    const int i0 = (t / Ot) * 16, j0 = (t % Ot) * 16;
-    const f32x4 acc = tile_gemm(C,
-        [&](int i, int k) { return k < C ? X(i0 + i, k) : 0.f; },
-        [&](int k, int j) { return (j0 + j < O && k < C) ? w_rel[(size_t)(j0 + j) * C + k] : 0.f; });
+  f32x4 keep[kDsFwdTiles];                      // x W_root^T
+  // ---- P = x W_rel^T  [n, O] and x W_root^T in one pass over the x image --------------------------------------------
+  for_k_blocks<kDsMaxC / 32>((C + 31) >> 5, [&](auto kb) {
+    constexpr int KB = decltype(kb)::value;
+    float wr[8 * KB], wt[8 * KB];
+    if (active) {
+      frag_load<KB>(wr, [&](int k) { return Wr_[(j0 + l15) * SX + k]; });
+      frag_load<KB>(wt, [&](int k) { return Wt_[(j0 + l15) * SX + k]; });
+    }
+    __syncthreads();                             // the weight images are free: P is written over them
+    if (active) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) P(i0 + lq * 4 + r, j0 + l15) = acc[r];
-  }
+      for (int s = 0; s < kDsFwdTiles; ++s) {
+        const int i0 = (first + s * wpc) * 16;
+        if (i0 < NP) {
+          f32x4 acc;
+          tile_gemm2_b_resident<KB>(wr, wt, [&](int i, int k) { return X(i0 + i, k); }, acc, keep[s]);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) P(i0 + lq * 4 + r, j0 + l15) = acc[r];
+        }
+      }
+    }
+  });
+  __syncthreads();                               // P is complete, every read of the x image is done
+  ds_stage<T>(Am_, SA, ag, n, n, NP, (n + 31) & ~31, p.vec16);
   __syncthreads();
-  // ---- out = (A P) / deg + x W_root^T + b: every wave owns whole tiles, written back after a barrier -----
-  f32x4 keep[(kDsMaxN / 16) * (kDsMaxO / 16) / kDsWaves + 1];
-  int nk = 0;
-  for (int t = wave; t < Nt * Ot; t += kDsWaves, ++nk) {
-    const int i0 = (t / Ot) * 16, j0 = (t % Ot) * 16;
-    f32x4 acc = tile_gemm(n,
-        [&](int i, int k) { return (i0 + i < n && k < n) ? ab[(size_t)(i0 + i) * n + k] : 0.f; },
-        [&](int k, int j) { return k < n ? P(k, j0 + j) : 0.f; });
-    const f32x4 root = tile_gemm(C,
-        [&](int i, int k) { return k < C ? X(i0 + i, k) : 0.f; },
-        [&](int k, int j) { return (j0 + j < O && k < C) ? w_root[(size_t)(j0 + j) * C + k] : 0.f; });
+  ds_degrees(Am_, n, SA, deg, nullptr);
+  // ---- A P: every wave owns whole tiles, written back after a barrier ------------------------------------------------
+  f32x4 agg[kDsFwdTiles];
+  if (active) {
+#pragma unroll
+    for (int s = 0; s < kDsFwdTiles; ++s) {
+      const int i0 = (first + s * wpc) * 16;
+      if (i0 < NP)
+        agg[s] = tile_gemm(n,
+            [&](int i, int k) { return A(i0 + i, k); },
+            [&](int k, int j) { return k < n ? P(k, j0 + j) : 0.f; });
+    }
+  }
+  __syncthreads();                               // every read of P as the projection is done; deg is complete
+  // ---- out = (A P) / deg + x W_root^T + b ------------------------------------------------------------------------------
+  if (active) {
     const float bj = (p.bias && j0 + l15 < O) ? p.bias[j0 + l15] : 0.f;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = i0 + lq * 4 + r;
-      acc[r] = acc[r] / deg[min(row, n - 1)] + root[r] + bj;
-    }
-    keep[nk] = acc;
-  }
-  __syncthreads();                               // every read of P as the projection is done
-  nk = 0;
-  for (int t = wave; t < Nt * Ot; t += kDsWaves, ++nk) {
-    const int i0 = (t / Ot) * 16, j0 = (t % Ot) * 16;
+    for (int s = 0; s < kDsFwdTiles; ++s) {
+      const int i0 = (first + s * wpc) * 16;
+      if (i0 < NP) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) P(i0 + lq * 4 + r, j0 + l15) = keep[nk][r];
+        for (int r = 0; r < 4; ++r) {
+          const int row = i0 + lq * 4 + r;
+          P(row, j0 + l15) = agg[s][r] / deg[min(row, n - 1)] + keep[s][r] + bj;
+        }
+      }
+    }
   }
   __syncthreads();
   // ---- row normalisation and store ----------------------------------------------------------------
@@ -151,6 +237,7 @@ __global__ __launch_bounds__(kDsBlock) void dense_sage_fwd_kernel(const DsArgs p
 }
 #undef P
 #undef X
+#undef A
 
 template <typename T>
 __global__ __launch_bounds__(kDsBlock) void dense_sage_bwd_kernel(const DsArgs p) {
@@ -179,7 +266,7 @@ __global__ __launch_bounds__(kDsBlock) void dense_sage_bwd_kernel(const DsArgs p
   const int Nt = NP / 16, Ot = OP / 16, Ct = CP / 16;
   const int l15 = lane & 15, lq = lane >> 4;
 
-  ds_degrees(ab, n, deg, raw);
+  ds_degrees(ab, n, n, deg, raw);
   // ---- g = (gy - y <y, gy>) * rinv, zero padded ------------------------------------------------------
   for (int r = wave; r < NP; r += kDsWaves) {
     float gv = 0.f, yv = 0.f;
@@ -301,6 +388,7 @@ extern "C" int mlgnn_dense_sage_fwd(const void* x, const void* adj, const void* 
   a.x = x; a.adj = adj; a.w_rel = w_rel; a.w_root = w_root;
   a.bias = bias; a.y_out = y; a.rinv = rinv;
   a.n = (int)n; a.C = (int)C; a.O = (int)O; a.adj_batched = adj_batched; a.normalize = normalize;
+  a.vec16 = aligned<16>(x, adj, w_rel, w_root) ? 1 : 0;
   const size_t lds = ds_fwd_lds_bytes((int)n, (int)C, (int)O);
   static size_t fwd_attr = 0;                   // (idempotent: a race only repeats the call)
   if (lds > fwd_attr) {
