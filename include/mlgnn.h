@@ -1068,6 +1068,42 @@ int mlgnn_vq_bwd(const float* z, const float* codebook, const int32_t* index, co
                  float* grad_z, float* grad_codebook, float beta, int64_t N, int64_t K, int64_t D, void* stream);
 
 /*
+ * The latent head of the VAE and its loss terms (csrc/vae_latent.hip), fp32, for all pathways at once: one workgroup per
+ * pathway with its rows in LDS; one launch forward, one backward plus one that adds the parameter-gradient partials.
+ *   x [B, P, H] (contiguous): pathway p owns the n = B rows x[:, p, :].  w_mu, w_ls [H, H] (row o = output o), b_mu, b_ls [H].
+ *   mlgnn_vae_latent_fwd:
+ *     mu [B, P, H] = x_p w_mu^T + b_mu,  sigma [B, P, H] = exp(x_p w_ls^T + b_ls);
+ *     std_sum [P]  = sum_h std_b(mu[:, p, h]), unbiased (divisor B - 1), two passes, the second on centred values;
+ *     corr_sum [P] = sum over i != j of |clamp(c_ij / d_i / d_j, -1, 1)|, c = m~^T m~ / (B - 1) over the centred columns
+ *       m~ of mu_p, d_i = sqrt(c_ii): a zero-variance column makes it NaN (H >= 2), H = 1 has no pair and gives 0;
+ *     kld_sum [P]  = sum over b, h of (s^2 + mu^2 - 1) / 2 - log s with s = sigma + 1e-7, the closed form of
+ *       kl_divergence(Normal(mu, s), Normal(0, 1)).
+ *     Each of the three sums may be NULL (not wanted; its work is skipped).
+ *   mlgnn_vae_latent_bwd: mu, sigma as the forward wrote them (nothing else is saved).  Cotangents g_mu, g_sigma
+ *     [B, P, H] and g_std, g_corr, g_kld [P], each may be NULL (= zero).  Outputs, each NULL when not wanted (all NULL:
+ *     nothing is launched; work that only an absent output needs is skipped):
+ *       d mu = g_mu + g_kld mu + g_std m~ / ((B - 1) std) + the corr stream (clamp passes gradient on [-1, 1] inclusive,
+ *         |r| has the gradient sign(r)), d log-sigma = (g_sigma + g_kld (s - 1 / s)) sigma;
+ *       grad_x [B, P, H] = dmu w_mu + dls w_ls;  grad_w_mu, grad_w_ls [H, H] = sum over the rows of dmu^T x, dls^T x;
+ *       grad_b_mu, grad_b_ls [H] = sum over the rows of dmu, dls.
+ *     A parameter gradient is the sum over a pathway's rows in row order, then over the pathways in index order, through
+ *     workspace: P * (2 H H + 2 H) floats, required when any of the four is wanted (MLGNN_E_WORKSPACE otherwise).
+ *     Every element of a wanted output is written exactly once.
+ * Plain IEEE arithmetic (NaN and Inf travel as through the torch lines); no atomics, every sum in a fixed order: bitwise
+ * reproducible.  Shapes (mlgnn_vae_latent_supported): 2 <= B <= 256, P >= 0, 1 <= H <= 128, B * H <= 8192, x below
+ * 4 GiB; MLGNN_E_SHAPE for anything else (shape errors are reported before NULL operands); P = 0 is a no-op.
+ */
+int mlgnn_vae_latent_supported(int64_t B, int64_t P, int64_t H);
+int mlgnn_vae_latent_fwd(const float* x, const float* w_mu, const float* b_mu, const float* w_ls, const float* b_ls,
+                         float* mu, float* sigma, float* std_sum, float* corr_sum, float* kld_sum, int64_t B, int64_t P,
+                         int64_t H, void* stream);
+int mlgnn_vae_latent_bwd(const float* x, const float* w_mu, const float* w_ls, const float* mu, const float* sigma,
+                         const float* g_mu, const float* g_sigma, const float* g_std, const float* g_corr,
+                         const float* g_kld, float* grad_x, float* grad_w_mu, float* grad_b_mu, float* grad_w_ls,
+                         float* grad_b_ls, float* workspace, int64_t workspace_floats, int64_t B, int64_t P, int64_t H,
+                         void* stream);
+
+/*
  * Measurement aid (bench.py: the box's streaming ceiling next to the 8 TB/s spec peak): dst = src, 16 bytes per lane,
  * non_temporal != 0: non-temporal loads and stores.  bytes a multiple of 16, 16-byte aligned pointers.
  */

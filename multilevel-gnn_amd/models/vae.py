@@ -12,6 +12,8 @@ the encoder loss (438 launches -> one batched covariance) and, for the uniform-w
 ``compute_mmd`` loop of ``vae_loss``, is one launch per direction (``mlgnn.mmd``) on one ``[B, 438, H]`` prior draw.
 The per-pathway decoders (``foreach`` and ``foreach_diffhidden``) run as one launch per direction too
 (``mlgnn.decoder``) where the kernels take the shape; the block loop and the batched form remain for the rest.
+The latent head of ``VAE.encoder`` -- ``enc_mu``, ``exp(enc_log_sigma)``, the batch-std and correlation losses -- and
+the KL sums of ``vae_loss`` are one launch per direction as well (``mlgnn.latent``); the torch lines remain for the rest.
 The quantiser of ``VQ_VAE`` picks its codes, forms the straight-through output and the loss in one launch
 (``mlgnn.vq``) instead of building the ``[N, K]`` distance matrix; the torch lines remain for what the kernels refuse.
 ``get_embedding_similarity`` (spreadsheet ETL) is outside the accelerated path.
@@ -23,6 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from mlgnn import decoder as mlgnn_decoder
+from mlgnn import latent as mlgnn_latent
 from mlgnn import mmd as mlgnn_mmd
 from mlgnn import vq as mlgnn_vq
 from mlgnn.pool_flatten import module_pool_flatten
@@ -166,6 +169,17 @@ class VAE(_PretrainBase):
         """-> ``(q_z, cat([mu, sigma], -1), [loss_std, 0, loss_corr], gene_feature [B,G,C])``."""
         pooled, gene_feature = self._project(input_batch)
         x = pooled.permute(0, 2, 1, 3).flatten(2)
+        xc = x.contiguous() if mlgnn_latent.ENABLED and x.is_cuda and x.dtype == torch.float32 else None
+        if xc is not None and mlgnn_latent.vae_latent_supported(xc):
+            # the head, both encoder losses and the KL sums in one launch per direction (csrc/vae_latent.hip)
+            mu, sigma, std_sum, corr_sum, kld_sum = mlgnn_latent.vae_latent(
+                xc, self.enc_mu.weight, self.enc_mu.bias, self.enc_log_sigma.weight, self.enc_log_sigma.bias)
+            _, P, H = mu.shape
+            q_z = torch.distributions.Normal(loc=mu, scale=sigma + mlgnn_latent.EPS)
+            q_z.kld_sum = kld_sum                               # vae_loss: kl_divergence(q_z, N(0, 1)) summed per pathway
+            return (q_z, torch.cat([mu, sigma], dim=-1), [-std_sum.sum() / (P * H), 0, corr_sum.sum() / (P * H * H)],
+                    gene_feature)
+        mlgnn_latent.LATENT_STATS["torch"] += 1
         mu = self.enc_mu(x)
         sigma = torch.exp(self.enc_log_sigma(x))
         loss_std = -mu.flatten(1).permute(1, 0).std(1).mean()
@@ -288,7 +302,11 @@ class VAE(_PretrainBase):
             mlgnn_mmd.MMD_STATS["torch"] += 1
             mmd_loss = torch.stack([self.compute_mmd(z[:, i, :], None if prior is None else prior[:, i, :])
                                     for i in range(z.shape[1])]).mean()
-        kld_loss = torch.distributions.kl_divergence(q_z, torch.distributions.Normal(0, 1.)).sum(-1).mean()
+        kld_sum = getattr(q_z, "kld_sum", None)              # carried from the encoder's launch (mlgnn.latent)
+        if kld_sum is not None:
+            kld_loss = kld_sum.sum() / (q_z.loc.shape[0] * q_z.loc.shape[1])
+        else:
+            kld_loss = torch.distributions.kl_divergence(q_z, torch.distributions.Normal(0, 1.)).sum(-1).mean()
         loss = a.mmd_beta * recons_loss + (1. - a.mmd_alpha) * a.kld_weight * kld_loss + \
             (a.mmd_alpha + a.mmd_reg_weight - 1.) / (n * (n - 1)) * mmd_loss
         return {'loss': loss, 'Reconstruction_Loss': recons_loss, 'MMD': mmd_loss, 'KLD': -kld_loss}
