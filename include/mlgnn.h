@@ -1104,6 +1104,42 @@ int mlgnn_vae_latent_bwd(const float* x, const float* w_mu, const float* w_ls, c
                          void* stream);
 
 /*
+ * The training criterion of the supervised models (csrc/criterion.hip), fp32: BCELoss on the [B, 2] softmax output in one
+ * of four weightings plus the pca feature loss, two launches forward (one without a feature term), one backward.
+ *   pred, y [B, 2] (probabilities, float labels), c_b = (y[b, 1] == 1).
+ *   bce[b, j] = -(y max(log p, -100) + (1 - y) max(log(1 - p), -100));  loss_bce = sum W[b, j] bce[b, j] / (2 B), mode:
+ *     MLGNN_CRIT_PLAIN  W = 1                      MLGNN_CRIT_CLASS  W[b, j] = cw[b, j]  (BCELoss(weight = cw))
+ *     MLGNN_CRIT_SAMPLE W[b, j] = cw[b, c_b]       MLGNN_CRIT_BATCH  W = mean_b cw[b, c_b], one scalar
+ *     anything else MLGNN_E_MODE.  class_weight is [cw_rows, 2] with cw_rows >= B (rows b < B are read), or [2] when
+ *     cw_rows == 0; required by the three weighted modes only.
+ *   feat [B, M] (contiguous; ignored when M == 0: no feature term), coef: the term -coef log(mean_m std_m), std_m the
+ *     unbiased (B - 1) standard deviation of column m over the batch, its variance formed from deviations about the mean.
+ *   mlgnn_criterion_fwd: loss [1] = loss_bce + feature term; terms [3] = (loss_bce, mean_std, feature term) or NULL (the
+ *     last two are 0 when M == 0); colstats [2, M] = (mean_m, inv_m = 1 / ((B - 1) std_m), 0 where std_m == 0) or NULL
+ *     (not wanted: no backward follows).  workspace: mlgnn_criterion_workspace(B, M) floats (one partial sum of std per
+ *     workgroup), required when M > 0 (MLGNN_E_WORKSPACE otherwise).
+ *   mlgnn_criterion_bwd: grad_loss [1], the upstream cotangent g, and terms (mean_std) are read on the device.
+ *     grad_pred [B, 2] = g W (p - y) / max((1 - p) p, 1e-12) / (2 B);  grad_feat [B, M] = g (-coef) / (M mean_std)
+ *     (x - mean_m) inv_m, exactly 0 where std_m == 0 (a select).  Either may be NULL (not wanted; both: nothing is
+ *     launched); grad_feat needs feat, colstats and terms.  Every element of a wanted output is written exactly once.
+ * No atomics, every sum in a fixed order: bitwise reproducible.  Shapes (mlgnn_criterion_supported): 0 <= B <= 65536, and
+ * M == 0, or M >= 1 with B >= 2 and feat below 4 GiB (B == 0 is a no-op: nothing is read or written); MLGNN_E_SHAPE for
+ * anything else (shape errors are reported before an unknown mode, that before NULL operands).
+ */
+#define MLGNN_CRIT_PLAIN 0
+#define MLGNN_CRIT_CLASS 1
+#define MLGNN_CRIT_SAMPLE 2
+#define MLGNN_CRIT_BATCH 3
+int mlgnn_criterion_supported(int64_t B, int64_t M);
+int64_t mlgnn_criterion_workspace(int64_t B, int64_t M);
+int mlgnn_criterion_fwd(const float* pred, const float* y, const float* class_weight, int64_t cw_rows, const float* feat,
+                        float coef, int mode, float* workspace, int64_t workspace_floats, float* colstats, float* loss,
+                        float* terms, int64_t B, int64_t M, void* stream);
+int mlgnn_criterion_bwd(const float* pred, const float* y, const float* class_weight, int64_t cw_rows, const float* feat,
+                        const float* colstats, const float* terms, const float* grad_loss, float coef, int mode,
+                        float* grad_pred, float* grad_feat, int64_t B, int64_t M, void* stream);
+
+/*
  * Measurement aid (bench.py: the box's streaming ceiling next to the 8 TB/s spec peak): dst = src, 16 bytes per lane,
  * non_temporal != 0: non-temporal loads and stores.  bytes a multiple of 16, 16-byte aligned pointers.
  */

@@ -129,6 +129,10 @@ SIGNATURES = {
     "mlgnn_vae_latent_supported": (_INT, [_I64] * 3),
     "mlgnn_vae_latent_fwd": (_INT, [_P] * 10 + [_I64] * 3 + [_P]),
     "mlgnn_vae_latent_bwd": (_INT, [_P] * 16 + [_I64] * 4 + [_P]),
+    "mlgnn_criterion_supported": (_INT, [_I64] * 2),
+    "mlgnn_criterion_workspace": (_I64, [_I64] * 2),
+    "mlgnn_criterion_fwd": (_INT, [_P, _P, _P, _I64, _P, _F, _INT, _P, _I64, _P, _P, _P, _I64, _I64, _P]),
+    "mlgnn_criterion_bwd": (_INT, [_P, _P, _P, _I64, _P, _P, _P, _P, _F, _INT, _P, _P, _I64, _I64, _P]),
     "mlgnn_stream_copy": (_INT, [_P, _P, _I64, _INT, _P]),
     "mlgnn_gemm_bf16_nt_workgroups": (_INT, [_I64, _I64, _INT]),
     "mlgnn_gemm_bf16_nt": (_INT, [_c.POINTER(_P), _c.POINTER(_P), _c.POINTER(_I64), _c.POINTER(_I64), _c.POINTER(_I64),

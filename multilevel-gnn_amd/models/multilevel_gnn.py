@@ -268,10 +268,20 @@ class MultilevelGNN(nn.Module):
         """``pca_loss``: -coef * log(mean(std over batch)); ``pca_indep_loss``: mean |cos| between
         projection columns per pathway, evaluated on detached weights (value only, no gradient),
         accumulated once per outer index exactly as the reference does (:336-346)."""
+        loss = self.get_pca_loss(pca_feature)
+        indep = self.get_indep_loss()
+        return loss + indep if torch.is_tensor(indep) else loss
+
+    def get_pca_loss(self, pca_feature):
+        """The ``pca_loss`` term of :meth:`get_feature_loss` (0 when the flag is off)."""
         loss = 0
         if self.pca_loss:
             flat = pca_feature.reshape(pca_feature.shape[0], -1)
             loss = loss - self.pca_loss_coef * torch.log(torch.mean(torch.std(flat, dim=0)))
+        return loss
+
+    def get_indep_loss(self):
+        """The ``pca_indep_loss`` term of :meth:`get_feature_loss`: a value on detached weights, or 0."""
         if self.pca_indep_loss:
             w = (self.learnable_pca_params * self.info_mask).detach()
             seg = self.pathway_indexs.to(w.device)
@@ -286,8 +296,8 @@ class MultilevelGNN(nn.Module):
                 sums = torch.zeros(n_seg, cols.shape[1], dtype=w.dtype, device=w.device).index_add_(0, seg, cols)
                 length = torch.sqrt(sums[:, :k - 1] * sums[:, k - 1:k])
                 indep = torch.abs(sums[:, k:] / (length + 1e-7)).mean(0).sum()
-                loss = loss + indep / count
-        return loss
+                return indep / count
+        return 0
 
     def generate_mutual_mask(self, x, y, mutual_classif=True, fold=0, tf_token=None):
         """CPU preprocessing (sklearn mutual information), same contract as the reference (:353-381)."""

@@ -153,10 +153,20 @@ class PathCNN(nn.Module):
         between projection columns per pathway on the unmasked, detached weights, added once per outer index after its
         inner loop exactly as the reference does (:173-182: only the pair (i, k - 1) of every i enters the sum, while
         ``count`` counts all pairs) and with no epsilon in the denominator."""
+        loss = self.get_pca_loss(pca_feature)
+        indep = self.get_indep_loss()
+        return loss + indep if torch.is_tensor(indep) else loss
+
+    def get_pca_loss(self, pca_feature):
+        """The ``pca_loss`` term of :meth:`get_feature_loss` (0 when the flag is off)."""
         loss = 0
         if self.pca_loss:
             flat = pca_feature.reshape(pca_feature.shape[0], -1)
             loss = loss - self.pca_loss_coef * torch.log(torch.mean(torch.std(flat, dim=0)))
+        return loss
+
+    def get_indep_loss(self):
+        """The ``pca_indep_loss`` term of :meth:`get_feature_loss`: a value on detached weights, or 0."""
         if self.pca_indep_loss and self.args.learnable_pca:
             w = self.learnable_pca_params.detach()
             seg = self.pathway_indexs.to(w.device)
@@ -169,8 +179,8 @@ class PathCNN(nn.Module):
                 sums = torch.zeros(n_seg, cols.shape[1], dtype=w.dtype, device=w.device).index_add_(0, seg, cols)
                 length = torch.sqrt(sums[:, :k - 1] * sums[:, k - 1:k])
                 indep = torch.abs(sums[:, k:] / length).mean(0).sum()
-                loss = loss + indep / count
-        return loss
+                return indep / count
+        return 0
 
     def generate_mutual_mask(self, x, y, mutual_classif=None):
         """CPU preprocessing (sklearn mutual information), same contract as the reference (:189-200)."""
