@@ -1140,6 +1140,28 @@ int mlgnn_criterion_bwd(const float* pred, const float* y, const float* class_we
                         float* grad_pred, float* grad_feat, int64_t B, int64_t M, void* stream);
 
 /*
+ * Mutual information between continuous features and a discrete target (csrc/mutual_info.hip), fp64: the estimator of
+ * Ross 2014 as scikit-learn's mutual_info_classif evaluates it, one workgroup per feature, one launch.
+ *   x [F, N] feature-major (row f = the prepared column of feature f: scaled, noise added), labels [N] dense class ids in
+ *   [0, n_labels) (anything else is read as 0).  Every label is expected to occur at least twice (the caller has dropped
+ *   the samples whose label occurs once); k = n_neighbors.
+ *     k_i = min(k, count(d_i) - 1)
+ *     r_i = the k_i-th smallest of fl|c_j - c_i| over j != i with d_j = d_i (one IEEE subtraction, no expanded form)
+ *     m_i = #{ j : fl|c_j - c_i| <= nextafter(r_i, 0) } over all N samples, self included
+ *     mi [F] = max(0, base - (1 / N) sum_i psi[m_i])
+ *   psi [N + 1]: psi[j] = digamma(j) for j = 1 .. N (entry 0 is not used), base = digamma(N) + mean_i digamma(k_i)
+ *   - mean_i digamma(count(d_i)): both from the host, neither depends on the feature.  counts [F, N] int32 = m_i in the
+ *   input's sample order, or NULL (not wanted).
+ * No atomics, every sum in a fixed order: bitwise reproducible.  Shapes (mlgnn_mutual_info_supported): 2 <= N <= 2048,
+ * F >= 0 with F * N * 8 below 4 GiB, k >= 1, 1 <= n_labels <= N.  MLGNN_E_NULL for a NULL x, labels, psi or mi, then
+ * MLGNN_E_SHAPE for anything else (here NULL operands are reported before shape errors); both before anything is launched.
+ * F = 0 is a no-op (nothing is read or written).  No workspace.
+ */
+int mlgnn_mutual_info_supported(int64_t n, int64_t n_features, int k, int n_labels);
+int mlgnn_mutual_info_cd(const double* x, const int32_t* labels, const double* psi, double base, double* mi,
+                         int32_t* counts, int64_t n, int64_t n_features, int k, int n_labels, void* stream);
+
+/*
  * Measurement aid (bench.py: the box's streaming ceiling next to the 8 TB/s spec peak): dst = src, 16 bytes per lane,
  * non_temporal != 0: non-temporal loads and stores.  bytes a multiple of 16, 16-byte aligned pointers.
  */

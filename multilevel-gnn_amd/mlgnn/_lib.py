@@ -133,6 +133,8 @@ SIGNATURES = {
     "mlgnn_criterion_workspace": (_I64, [_I64] * 2),
     "mlgnn_criterion_fwd": (_INT, [_P, _P, _P, _I64, _P, _F, _INT, _P, _I64, _P, _P, _P, _I64, _I64, _P]),
     "mlgnn_criterion_bwd": (_INT, [_P, _P, _P, _I64, _P, _P, _P, _P, _F, _INT, _P, _P, _I64, _I64, _P]),
+    "mlgnn_mutual_info_supported": (_INT, [_I64, _I64, _INT, _INT]),
+    "mlgnn_mutual_info_cd": (_INT, [_P, _P, _P, _c.c_double, _P, _P, _I64, _I64, _INT, _INT, _P]),
     "mlgnn_stream_copy": (_INT, [_P, _P, _I64, _INT, _P]),
     "mlgnn_gemm_bf16_nt_workgroups": (_INT, [_I64, _I64, _INT]),
     "mlgnn_gemm_bf16_nt": (_INT, [_c.POINTER(_P), _c.POINTER(_P), _c.POINTER(_I64), _c.POINTER(_I64), _c.POINTER(_I64),

@@ -1,0 +1,138 @@
+"""The mutual-information gene mask on the kernel of csrc/mutual_info.hip: scikit-learn's ``mutual_info_classif`` for dense
+continuous features (the estimator of Ross 2014, ``_compute_mi_cd``) with all features in one launch, one workgroup per
+feature, instead of two KD-trees per column one column after another.
+
+The host prepares the array with the calls scikit-learn makes -- ``check_X_y``, ``scale(with_mean=False)``, noise of
+``1e-10 * max(1, mean|x|)`` drawn from ``check_random_state(random_state)`` -- so the kernel sees bit for bit the columns
+``_compute_mi_cd`` sees and a fixed ``random_state`` gives the values it gives.  The preparation stays on the host on
+purpose: it has to draw from numpy's generator.  The drop of samples whose label occurs once, the feature-independent
+part of the estimate and the digamma table are host work too; the transpose to feature-major and everything per feature
+run on the device.  fp64, no CPU path for the op; the models call scikit-learn where the op does not apply."""
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from .ops import _stream
+
+# MLGNN_MI_FUSED=0: generate_mutual_mask of the models always calls scikit-learn (same-box A/B runs).  On by default: end
+# to end the op beats the scikit-learn call by far more than that call's spread at the gbm, lgg and kirc shapes
+# (profiles/mutual_info.json).
+DEFAULT_ENABLED = True
+ENABLED = os.environ.get("MLGNN_MI_FUSED", "1" if DEFAULT_ENABLED else "0") != "0"
+
+# how often model_mutual_info took each path (development / tests: which path a mask was computed on)
+MI_STATS = {"hip": 0, "sklearn": 0}
+
+if os.environ.get("MLGNN_PRINT_STATS", "0") == "1":
+    import atexit
+    import sys
+    atexit.register(lambda: print("mlgnn stats: mutual_info %r" % (MI_STATS,), file=sys.stderr))
+
+MAX_SAMPLES = 2048
+
+
+def tree_path(k, counts_per_label):
+    """Whether scikit-learn searches every label's neighbours with its tree, where its distances are ``|x - y|`` and the
+    op returns its values: ``min(k, count - 1) < count // 2`` for every label that occurs more than once, the rule of
+    ``NearestNeighbors(algorithm='auto')``.  Otherwise some label goes through the brute-force search, whose
+    expanded-form distances the op does not imitate."""
+    return all(min(int(k), int(c) - 1) < int(c) // 2 for c in counts_per_label if int(c) > 1)
+
+
+def mutual_info_supported(n, n_features, k, counts_per_label):
+    """Whether the op applies: ``n`` samples, of which those with a label occurring once are dropped (``counts_per_label``:
+    how often each label occurs); at least 2 and at most 2048 must remain, ``k >= 1``, the array below 4 GiB."""
+    kept = [int(c) for c in counts_per_label if int(c) > 1]
+    if sum(int(c) for c in counts_per_label) != int(n) or not kept or int(k) < 1 or int(k) >= 1 << 31:
+        return False
+    return bool(_lib.lib.mlgnn_mutual_info_supported(sum(kept), int(n_features), int(k), len(kept)))
+
+
+def prepare(x, y, random_state=None):
+    """``mutual_info_classif``'s preparation of dense continuous features, call for call -> ``(X [n, F] fp64, y [n])``."""
+    from sklearn.preprocessing import scale
+    from sklearn.utils import check_random_state
+    from sklearn.utils.validation import check_X_y
+    X, y = check_X_y(x, y, accept_sparse="csc", y_numeric=False)
+    n_samples, n_features = X.shape
+    rng = check_random_state(random_state)
+    continuous_mask = np.ones(n_features, dtype=bool)          # dense input: every feature is continuous
+    X = X.astype(np.float64, copy=True)
+    X[:, continuous_mask] = scale(X[:, continuous_mask], with_mean=False, copy=False)
+    means = np.maximum(1, np.mean(np.abs(X[:, continuous_mask]), axis=0))
+    X[:, continuous_mask] += 1e-10 * means * rng.standard_normal(size=(n_samples, np.sum(continuous_mask)))
+    return X, y
+
+
+def mutual_info_cd(prepared, y, n_neighbors=3, return_counts=False):
+    """The estimator on an already prepared fp64 array ``[n, F]`` (tests; :func:`mutual_info_classif` is this after
+    :func:`prepare`).  ``return_counts``: also ``m_i`` as int32 ``[F, n_kept]`` in the order of the kept samples, and the
+    boolean mask ``[n]`` of the kept samples."""
+    from scipy.special import digamma
+    X = np.ascontiguousarray(prepared, dtype=np.float64)
+    y = np.asarray(y)
+    if X.ndim != 2 or y.shape != (X.shape[0],):
+        raise ValueError("mutual_info_cd: prepared %s, y %s" % (X.shape, y.shape))
+    n_features = X.shape[1]
+    k = int(n_neighbors)
+    _, dense, count = np.unique(y, return_inverse=True, return_counts=True)
+    keep = count[dense] > 1                                    # scikit-learn: "ignore points with unique labels"
+    n = int(keep.sum())
+    if n == 0 or n_features == 0:
+        mi = np.zeros(n_features, dtype=np.float64)
+        return (mi, np.zeros((n_features, 0), dtype=np.int32), keep) if return_counts else mi
+    if not torch.cuda.is_available():
+        raise RuntimeError("mlgnn.mutual_info has no CPU path (the kernel is HIP only)")
+    _, d, c = np.unique(y[keep], return_inverse=True, return_counts=True)
+    if not _lib.lib.mlgnn_mutual_info_supported(n, n_features, k, len(c)):
+        raise ValueError("mutual_info_cd: unsupported shape (%d samples after the drop, %d features, k = %d; 2 <= n <= %d, "
+                         "k >= 1, below 4 GiB)" % (n, n_features, k, MAX_SAMPLES))
+    count_i = c[d]
+    k_i = np.minimum(k, count_i - 1)
+    base = float(digamma(n) + np.mean(digamma(k_i)) - np.mean(digamma(count_i)))
+    psi = np.zeros(n + 1, dtype=np.float64)
+    psi[1:] = digamma(np.arange(1, n + 1))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rows = X if n == X.shape[0] else X[keep]
+    xt = torch.from_numpy(rows).to(dev).t().contiguous()       # [F, n]: the transpose runs on the device
+    labels = torch.from_numpy(d.astype(np.int32)).to(dev)
+    psi_d = torch.from_numpy(psi).to(dev)
+    mi = torch.empty(n_features, dtype=torch.float64, device=dev)
+    counts = torch.empty((n_features, n), dtype=torch.int32, device=dev) if return_counts else None
+    rc = _lib.lib.mlgnn_mutual_info_cd(xt.data_ptr(), labels.data_ptr(), psi_d.data_ptr(), base, mi.data_ptr(),
+                                       _lib.ptr(counts), n, n_features, k, len(c), _stream())
+    _lib.check(rc, "mlgnn_mutual_info_cd")
+    out = mi.cpu().numpy()
+    return (out, counts.cpu().numpy(), keep) if return_counts else out
+
+
+def mutual_info_classif(x, y, n_neighbors=3, random_state=None, return_counts=False):
+    """``sklearn.feature_selection.mutual_info_classif(x, y, n_neighbors=..., random_state=...)`` for dense continuous
+    features -> fp64 numpy ``[F]`` (with ``return_counts`` also the ``m_i`` and the kept-sample mask of
+    :func:`mutual_info_cd`).  The values are scikit-learn's where :func:`tree_path` holds; the caller checks that and
+    :func:`mutual_info_supported` first."""
+    X, y = prepare(x, y, random_state)
+    return mutual_info_cd(X, y, n_neighbors, return_counts)
+
+
+def label_counts(y):
+    """How often each label of ``y`` occurs (the ``counts_per_label`` of :func:`tree_path`, :func:`mutual_info_supported`)."""
+    y = y.detach().cpu().numpy() if torch.is_tensor(y) else np.asarray(y)
+    return np.unique(y, return_counts=True)[1]
+
+
+def model_mutual_info(x, y, n_neighbors, random_state, mutual_classif):
+    """The mutual information ``generate_mutual_mask`` of the models thresholds: the kernel when ``mutual_classif`` is
+    true, the switch is on, a GPU is present, the shape is supported and :func:`tree_path` holds; otherwise the
+    scikit-learn call (``mutual_info_regression``, small classes, CPU-only hosts, more than 2048 samples)."""
+    if mutual_classif and ENABLED and torch.cuda.is_available() and getattr(x, "ndim", 0) == 2 and getattr(y, "ndim", 0) == 1:
+        counts = label_counts(y)
+        if mutual_info_supported(x.shape[0], x.shape[1], n_neighbors, counts) and tree_path(n_neighbors, counts):
+            MI_STATS["hip"] += 1
+            return mutual_info_classif(x, y, n_neighbors=n_neighbors, random_state=random_state)
+    import sklearn.feature_selection as fs
+    fn = fs.mutual_info_classif if mutual_classif else fs.mutual_info_regression
+    MI_STATS["sklearn"] += 1
+    return fn(x, y, n_neighbors=n_neighbors, random_state=random_state)

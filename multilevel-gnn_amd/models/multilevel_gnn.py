@@ -16,6 +16,7 @@ import torch.nn as nn
 
 from mlgnn.conv import module_conv2d
 from mlgnn.dense import linear as dense_linear
+from mlgnn.mutual_info import model_mutual_info
 from mlgnn.pool_flatten import module_pool_flatten
 from mlgnn.project import segment_project
 from mlgnn.sage import linear_act, linear_act_supported, node_embed, node_embed_supported
@@ -300,12 +301,12 @@ class MultilevelGNN(nn.Module):
         return 0
 
     def generate_mutual_mask(self, x, y, mutual_classif=True, fold=0, tf_token=None):
-        """CPU preprocessing (sklearn mutual information), same contract as the reference (:353-381)."""
-        from sklearn.feature_selection import mutual_info_classif, mutual_info_regression
+        """Preprocessing (mutual information of every gene with the label: the kernel of csrc/mutual_info.hip where
+        :func:`mlgnn.mutual_info.model_mutual_info` finds it applies, else scikit-learn), same contract as the reference
+        (:353-381)."""
         x, y = torch.tensor(x), torch.tensor(y)
         random_state = self.args.random_state if self.args.freeze_mutual_select_init else None
-        fn = mutual_info_classif if mutual_classif else mutual_info_regression
-        mutual_info = fn(x, y, n_neighbors=self.mutual_neighbors, random_state=random_state)
+        mutual_info = model_mutual_info(x, y, self.mutual_neighbors, random_state, mutual_classif)
         if fold in self.mutual_info_mask_cache:
             res = self.mutual_info_mask_cache[fold]
         else:

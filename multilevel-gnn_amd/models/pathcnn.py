@@ -16,6 +16,7 @@ import torch.nn as nn
 
 from mlgnn.conv import PathConv2d
 from mlgnn.dense import linear as dense_linear
+from mlgnn.mutual_info import model_mutual_info
 from mlgnn.pool_flatten import module_pool_flatten
 from mlgnn.project import segment_project
 
@@ -183,11 +184,11 @@ class PathCNN(nn.Module):
         return 0
 
     def generate_mutual_mask(self, x, y, mutual_classif=None):
-        """CPU preprocessing (sklearn mutual information), same contract as the reference (:189-200)."""
-        from sklearn.feature_selection import mutual_info_classif, mutual_info_regression
+        """Preprocessing (mutual information of every gene with the label: the kernel of csrc/mutual_info.hip where
+        :func:`mlgnn.mutual_info.model_mutual_info` finds it applies, else scikit-learn), same contract as the reference
+        (:189-200)."""
         x, y = torch.tensor(x), torch.tensor(y)
-        fn = mutual_info_classif if mutual_classif else mutual_info_regression
-        mutual_info = fn(x, y, n_neighbors=self.mutual_neighbors)
+        mutual_info = model_mutual_info(x, y, self.mutual_neighbors, None, mutual_classif)
         thr = np.mean(mutual_info) if self.mutual_info_threshold is None else self.mutual_info_threshold
         mi = torch.tensor(mutual_info)
         return torch.where(mi < thr, torch.zeros(mi.shape), torch.ones(mi.shape))[:, None], mutual_info

@@ -1,0 +1,152 @@
+#!/usr/bin/env python3
+"""The mutual-information gene mask (``generate_mutual_mask`` of the models: ``mutual_info_classif`` over every gene
+column) at the shapes of the shipped configurations,
+
+  (N, F, k) = (200, 15405, 7)    gbm
+              (200, 15405, 15)   lgg
+              (300, 25015, 15)   kirc
+
+on synthetic fp32 data with a planted signal (column f shifted by ``label * 2 f / F``), two labels at 70 % / 30 %.
+Times ``mlgnn.mutual_info_classif`` (csrc/mutual_info.hip) against the scikit-learn call as the models make it (one job):
+the two legs alternate over three repeats, so the scikit-learn leg's own spread is on record.  Reported per shape:
+
+  * end to end, wall clock: host preparation + upload + transpose + kernel + download;
+  * the kernel alone, by device events (mean of ``--iters`` launches after ``--warmup``);
+  * the host preparation alone (``check_X_y``, ``scale``, the noise draw), wall clock;
+  * the scikit-learn call, wall clock;
+  * that both legs agree (max |difference|; both use the same ``random_state``).
+
+The first shape is run once untimed on the op's leg before the sweep (the first launch of a process carries the load of
+its code object).  Results are written after every shape.  Writes profiles/mutual_info.json.  Development tool; run it
+under a time limit of its own (``timeout -k 10 900 python tools/bench_mutual_info.py``)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
+from mlgnn import _lib  # noqa: E402
+from mlgnn import mutual_info as MI  # noqa: E402
+
+SHAPES = [("gbm", 200, 15405, 7), ("lgg", 200, 15405, 15), ("kirc", 300, 25015, 15)]
+REPEATS = 3
+SEED = 12345
+
+
+def make_data(n, F, seed):
+    rng = np.random.RandomState(seed)
+    y = (np.arange(n) < int(0.3 * n)).astype(np.int64)
+    rng.shuffle(y)
+    x = rng.standard_normal((n, F)) + y[:, None] * (2.0 * np.arange(F) / F)[None, :]
+    return x.astype(np.float32), y
+
+
+def wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, out
+
+
+def kernel_ms(prepared, y, k, warmup, iters):
+    """The launch of mlgnn_mutual_info_cd alone, operands resident on the device."""
+    from scipy.special import digamma
+    n, F = prepared.shape
+    dev = torch.device("cuda:0")
+    _, d, c = np.unique(y, return_inverse=True, return_counts=True)
+    psi = np.zeros(n + 1)
+    psi[1:] = digamma(np.arange(1, n + 1))
+    base = float(digamma(n) + np.mean(digamma(np.minimum(k, c[d] - 1))) - np.mean(digamma(c[d])))
+    xt = torch.from_numpy(prepared).to(dev).t().contiguous()
+    labels, psi_d = torch.from_numpy(d.astype(np.int32)).to(dev), torch.from_numpy(psi).to(dev)
+    mi = torch.empty(F, dtype=torch.float64, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def launch():
+        _lib.check(_lib.lib.mlgnn_mutual_info_cd(xt.data_ptr(), labels.data_ptr(), psi_d.data_ptr(), base, mi.data_ptr(), None,
+                                                 n, F, k, len(c), stream), "mlgnn_mutual_info_cd")
+
+    for _ in range(warmup):
+        launch()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    s.record()
+    for _ in range(iters):
+        launch()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / iters
+
+
+def bench_shape(name, n, F, k, warmup, iters, repeats):
+    from sklearn.feature_selection import mutual_info_classif as sk_classif
+    x, y = make_data(n, F, 7)
+    counts = MI.label_counts(y)
+    assert MI.mutual_info_supported(n, F, k, counts) and MI.tree_path(k, counts), (n, F, k, counts)
+    entry = {"shape": name, "N": n, "F": F, "k": k, "label_counts": [int(c) for c in counts],
+             "hip_end_to_end_ms": [], "sklearn_ms": [], "prepare_ms": [], "kernel_ms": []}
+    got = want = None
+    for _ in range(repeats):                                                  # the legs alternate
+        ms, got = wall(lambda: MI.mutual_info_classif(x, y, n_neighbors=k, random_state=SEED))
+        entry["hip_end_to_end_ms"].append(ms)
+        ms, want = wall(lambda: sk_classif(x, y, n_neighbors=k, random_state=SEED))
+        entry["sklearn_ms"].append(ms)
+        ms, (prepared, _) = wall(lambda: MI.prepare(x, y, SEED))
+        entry["prepare_ms"].append(ms)
+        entry["kernel_ms"].append(kernel_ms(prepared, y, k, warmup, iters))
+    entry["max_abs_diff_to_sklearn"] = float(np.abs(got - want).max())
+    entry["masks_equal_at_the_mean_threshold"] = bool(np.array_equal(got < got.mean(), want < want.mean()))
+    hip, ref = entry["hip_end_to_end_ms"], entry["sklearn_ms"]
+    entry["summary"] = {"hip_end_to_end_mean_ms": sum(hip) / repeats, "hip_spread_ms": max(hip) - min(hip),
+                        "sklearn_mean_ms": sum(ref) / repeats, "sklearn_spread_ms": max(ref) - min(ref),
+                        "prepare_mean_ms": sum(entry["prepare_ms"]) / repeats,
+                        "kernel_mean_ms": sum(entry["kernel_ms"]) / repeats,
+                        "speedup_over_sklearn": sum(ref) / sum(hip),
+                        "beats_sklearn_by_more_than_its_spread": sum(ref) / repeats - sum(hip) / repeats > max(ref) - min(ref)}
+    return entry
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=REPEATS)
+    ap.add_argument("--shapes", default=",".join(s[0] for s in SHAPES))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mutual_info.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_mutual_info.py needs the GPU: there is no CPU path of the op to time")
+    import scipy
+    import sklearn
+    result = {"workload": "mutual_info_classif over every gene column (generate_mutual_mask), fp64: the op of "
+                          "csrc/mutual_info.hip against the scikit-learn call (MLGNN_MI_FUSED=0), same input and random_state",
+              "timing": "wall clock around each call with a device synchronise, the two legs alternating over %d repeats, "
+                        "one process; the kernel alone by device events, mean of %d launches after %d" % (a.repeats, a.iters,
+                                                                                                        a.warmup),
+              "device": torch.cuda.get_device_name(0), "host_threads": torch.get_num_threads(),
+              "versions": {"sklearn": sklearn.__version__, "numpy": np.__version__, "scipy": scipy.__version__},
+              "shapes": []}
+    x, y = make_data(SHAPES[0][1], 512, 1)
+    MI.mutual_info_classif(x, y, n_neighbors=SHAPES[0][3], random_state=SEED)      # discarded: the code object loads
+    for name, n, F, k in SHAPES:
+        if name not in a.shapes.split(","):
+            continue
+        entry = bench_shape(name, n, F, k, a.warmup, a.iters, a.repeats)
+        result["shapes"].append(entry)
+        print(json.dumps(entry), flush=True)
+        result["ships_enabled"] = all(e["summary"]["beats_sklearn_by_more_than_its_spread"] for e in result["shapes"]) \
+            and len(result["shapes"]) == len(SHAPES)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            json.dump(result, fh, indent=1)
+            fh.write("\n")
+
+
+if __name__ == "__main__":
+    main()
