@@ -1162,6 +1162,41 @@ int mlgnn_mutual_info_cd(const double* x, const int32_t* labels, const double* p
                          int32_t* counts, int64_t n, int64_t n_features, int k, int n_labels, void* stream);
 
 /*
+ * PathwayConv's message + aggregation (csrc/pathway_conv.hip; the reference's torch_vertex.py:107-178): the second
+ * message-passing step over the gene -> pathway-node membership edges, for MLGNN_AGGR_MAX and MLGNN_AGGR_SOFTMAX (add and
+ * mean are two weighted sums of the existing aggregation by linearity; MLGNN_E_MODE here).  fp32, no atomics, every
+ * output element written exactly once, bitwise reproducible.  Edge j -> i with attributes a_e [2]:
+ *     msg_e[c] = a_e0 * Y[j, c] + a_e1 * Y[j, d + c]        Y [N, 2d] = x [W[:, 0::2] | W[:, 1::2]]^T
+ *     max:      m[i, c] = max_e msg_e[c] (the first maximal edge of the by-destination order wins)
+ *     softmax:  m[i, c] = sum_e w_e msg_e[c],  w = softmax_e(t * msg_e[c])      t = *t_ptr when t_ptr is given
+ *   mlgnn_pathway_conv_fwd   rowptr [N+1] / col [E] / attr [E, 2]: the CSR by destination and the attributes in that
+ *                            order; rows [R]: the destination rows that have edges (ascending or not, each once);
+ *                            out [R, d] = m[rows] + bias (bias [d] or NULL); winner [R, d] int32 (max: the by-destination
+ *                            position of the winning edge) or lse [R, d] (softmax: log2 of sum_e 2^(t log2(e) msg_e)).
+ *   mlgnn_pathway_conv_bwd   grad_out [R, d] -> grad_Y [N, 2d] (EVERY row written, zeros for sources without edges) by
+ *                            source row over the transposed CSR (rowptr_t, col_t, pos_t; attr_t [E, 2] in that order),
+ *                            row_of [N]: position of a node in rows[] (-1: none); grad_bias [d] or NULL; learn_t != 0
+ *                            (softmax only): the gradient also runs through w, and grad_t [1] is written; `out` and
+ *                            `bias` are those of the forward (read under learn_t only).  workspace:
+ *                            mlgnn_pathway_conv_bwd_workspace_floats(N, E, R, d, learn_t) floats, 16-byte aligned.
+ * Shapes (mlgnn_pathway_conv_supported): 1 <= d <= 256 (any d; 16-byte loads and 16-byte aligned operands when
+ * d % 4 == 0: MLGNN_E_ALIGN otherwise), Y below 4 GiB, E < 2^31, 0 <= R <= N.  MLGNN_E_SHAPE for anything else (shape
+ * errors are reported before the aggregator, that before NULL operands); R = 0 (forward) and N = 0 (backward) are no-ops.
+ */
+int mlgnn_pathway_conv_supported(int64_t N, int64_t E, int64_t d);
+int mlgnn_pathway_conv_fwd(const float* Y, const int32_t* rowptr, const int32_t* col, const float* attr,
+                           const int32_t* rows, const float* bias, float* out, int32_t* winner, float* lse,
+                           int64_t N, int64_t E, int64_t R, int64_t d, int aggr, float t, const float* t_ptr,
+                           void* stream);
+int64_t mlgnn_pathway_conv_bwd_workspace_floats(int64_t N, int64_t E, int64_t R, int64_t d, int learn_t);
+int mlgnn_pathway_conv_bwd(const float* grad_out, const float* Y, const float* out, const float* bias,
+                           const int32_t* winner, const float* lse, const int32_t* rowptr_t,
+                           const int32_t* col_t, const int32_t* pos_t, const float* attr_t,
+                           const int32_t* row_of, float* grad_Y, float* grad_bias, float* grad_t,
+                           float* workspace, int64_t workspace_floats, int64_t N, int64_t E, int64_t R,
+                           int64_t d, int aggr, float t, const float* t_ptr, int learn_t, void* stream);
+
+/*
  * Measurement aid (bench.py: the box's streaming ceiling next to the 8 TB/s spec peak): dst = src, 16 bytes per lane,
  * non_temporal != 0: non-temporal loads and stores.  bytes a multiple of 16, 16-byte aligned pointers.
  */

@@ -14,6 +14,7 @@ from .decoder import decoder_supported, pathway_decoders  # noqa: F401
 from .vq import vector_quantize, vq_supported  # noqa: F401
 from .latent import vae_latent, vae_latent_supported  # noqa: F401
 from .criterion import TrainCriterion, criterion_supported, train_criterion  # noqa: F401
+from .pathway_conv import PathwayTopology, pathway_aggregate, pathway_conv_supported  # noqa: F401
 from .mutual_info import mutual_info_classif, mutual_info_supported, tree_path  # noqa: F401
 from .ops import (LowRankEdge, RankOneEdge, TableEdge, edge_type_embedding, gen_aggregate, share_edge_gradient,  # noqa: F401
                   weighted_mean_aggregate)

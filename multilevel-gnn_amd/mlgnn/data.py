@@ -186,3 +186,53 @@ class SyntheticTCGA(torch.utils.data.Dataset):
         """``MyData.get_weight_balance`` (multiloader.py:321-326): per-class weights repeated per batch row."""
         counts = torch.bincount(self.labels[torch.as_tensor(indexs)], minlength=2).float()
         return torch.repeat_interleave(((counts.max() / counts) ** weight_power).unsqueeze(0), batch_size, dim=0)
+
+
+class SyntheticMultiOmix(torch.utils.data.Dataset):
+    """Patients with the batch fields the multi-omics model reads (``models/deepergcn_virtual_node.py``; no loader of the
+    reference produces them): ``node_num`` gene nodes plus ``pathway_num`` pathway nodes at the END of every graph,
+    ``x [n, 3]`` (one value per omics), ONE gene topology shared by all patients with ``edge_attr [E, 1]``, and per
+    omics ``o`` in mrna / cnv / mt the gene -> pathway-node membership: ``pathway_{o}_edges [E_p, 2]`` (graph-local
+    ``(src, dst)``, destinations among the pathway rows, segment sizes drawn as :class:`SyntheticTCGA` draws
+    ``raw_indice``), ``pathway_{o}_edges_num`` (a Python int: one entry per graph after the collate),
+    ``pathway_{o}_edge_attr [E_p, 2]`` and ``pathway_{o}_node_attr [P, 2]``.  None of the names contains "index": the
+    collate concatenates them along dim 0 WITHOUT an offset (the model offsets the edges itself)."""
+
+    OMICS = ("mrna", "cnv", "mt")
+
+    def __init__(self, n_patients, node_num=5135, pathway_num=146, n_edges=60000, n_members=8338, seed=0):
+        gen = torch.Generator().manual_seed(seed)
+        self.node_num, self.pathway_num, self.n = node_num, pathway_num, node_num + pathway_num
+        self.n_members = n_members
+        src = torch.randint(0, node_num, (n_edges,), generator=gen)
+        dst = torch.randint(0, node_num, (n_edges,), generator=gen)
+        self.edge_index, self.edge_attr = torch.stack([src, dst]), torch.rand(n_edges, 1, generator=gen)
+        self.x = torch.rand(n_patients, self.n, 3, generator=gen)
+        self.x[:, node_num:] = 0.0                                  # (the model overwrites the pathway rows)
+        self.edges, self.edge_values, self.node_values = {}, {}, {}
+        for o in self.OMICS:
+            seg = torch.sort(torch.randint(0, pathway_num, (n_members,), generator=gen))[0]
+            genes = torch.randint(0, node_num, (n_members,), generator=gen)
+            self.edges[o] = torch.stack([genes, node_num + seg], dim=1)
+            self.edge_values[o] = torch.rand(n_patients, n_members, 2, generator=gen) * 2 - 1
+            self.node_values[o] = torch.randn(n_patients, pathway_num, 2, generator=gen)
+        first = self.edges["mrna"][: min(200, n_members), 0]
+        signal = self.x[:, first, 0].mean(1)
+        self.labels = (signal > signal.median()).long()
+        self.age = torch.rand(n_patients, generator=gen)
+
+    def __len__(self):
+        return self.x.shape[0]
+
+    def __getitem__(self, i):
+        y = torch.tensor([1.0 - float(self.labels[i]), float(self.labels[i])])
+        d = Data(x=self.x[i], edge_index=self.edge_index, edge_attr=self.edge_attr, y=y, age=float(self.age[i]),
+                 node_size=self.n)
+        for o in self.OMICS:
+            setattr(d, "pathway_%s_edges" % o, self.edges[o])
+            setattr(d, "pathway_%s_edges_num" % o, int(self.n_members))
+            setattr(d, "pathway_%s_edge_attr" % o, self.edge_values[o][i])
+            setattr(d, "pathway_%s_node_attr" % o, self.node_values[o][i])
+        return d
+
+    get_weight_balance = SyntheticTCGA.get_weight_balance

@@ -490,6 +490,8 @@ def _release_at_exit():
         _SHARED_SAGE_CACHE[:] = []
         from . import project
         project._MEMBERSHIP_CACHE[:] = []
+        from . import pathway_conv
+        pathway_conv.PathwayTopology.clear_cache()
         if torch.cuda.is_available() and torch.cuda.is_initialized():
             torch.cuda.synchronize()
     except Exception:                                  # noqa: BLE001 -- never turn a clean exit into an error

@@ -1,7 +1,9 @@
 """Model registry with the reference's surface: ``from models import get_model`` (reference
-``models/__init__.py:11-24``).  Only the model families on the accelerated hot path are registered
-(SURVEY.md section 8a, 8f): the stale DeeperGCN copies ('multiomix') are out of scope for this library."""
+``models/__init__.py:11-24``): all nine names the reference registers.  'multiomix' is the multi-omics model
+(``deepergcn_virtual_node.py``: three DeeperGCN_Vnode encoders with a PathwayConv behind every gene convolution past the
+first)."""
 from .deepergcn import DeeperGCN
+from .deepergcn_virtual_node import DeeperGCN_Vnode, MultiOmixGCN  # noqa: F401
 from .multilevel_gnn import MultilevelGNN
 from .pathcnn import PathCNN
 from .multilevel_gnn_seq import MultilevelGNNSeq, PathwayHeadSeq  # noqa: F401
@@ -17,6 +19,7 @@ MODELS = {
     'vq_vae': VQ_VAE,
     'autoencoder': AutoEncoder,
     'pathcnn': PathCNN,
+    'multiomix': MultiOmixGCN,
 }
 
 

@@ -1,8 +1,9 @@
 """Sparse graph convolutions on the HIP CSR kernels (interface of the reference's
 ``models/gcn_lib/sparse/torch_vertex.py``: ``GENConv`` :12-104, ``SAGEConv`` :226-294,
-``RSAGEConv`` :297-304, ``GATConv`` :207-223, ``GraphConv`` :338-363).
+``RSAGEConv`` :297-304, ``GATConv`` :207-223, ``GraphConv`` :338-363, ``PathwayConv`` :107-178).
 
-Provided: ``gen``, ``sage``, ``rsage`` (the shipped configs) and ``gat`` (the reference's default ``gnn_name``); the other
+Provided: ``gen``, ``sage``, ``rsage`` (the shipped configs), ``gat`` (the reference's default ``gnn_name``) and the
+multi-omics model's ``PathwayConv`` (the membership step; ``MLGNN_PATHWAY_CONV=0``: its torch lines); the other
 PyG-wrapper types (edge/mr/gcn/gin) raise ``NotImplementedError`` -- the reference's ``GraphConv.forward`` cannot call
 them either.
 """
@@ -18,7 +19,7 @@ from mlgnn import gat as mlgnn_gat
 from mlgnn.dense import linear
 from mlgnn.graph import sage_graph
 from mlgnn.norm import msg_norm_add
-from .torch_message import GenMessagePassing, MsgNorm
+from .torch_message import GenMessagePassing, MsgNorm, PathwayMessagePassing
 from .torch_nn import MLP, act_layer, norm_layer
 
 _SAGE_FUSED = os.environ.get("MLGNN_SAGE_FUSED", "1") == "1"      # (0: the separate aggregate / lin_r / cat / Linear / act ops, for A/B runs)
@@ -77,6 +78,73 @@ class GENConv(GenMessagePassing):
         if isinstance(self.feature_encoder, MLP) and (residual is not None or post_norm is not None):
             return self.feature_encoder(h, residual=residual, post_norm=post_norm)
         out = self.feature_encoder(h)
+        return out if residual is None else out + residual
+
+
+class PathwayConv(PathwayMessagePassing):
+    """Second message-passing step over the gene -> pathway-node membership edges (torch_vertex.py:107-178):
+    ``relu(MLP(x + aggregate(msg_encoder(flatten(x_j (x) a_e))))) * mask``, ``a_e`` the edge's two attributes.
+
+    ``msg_norm.msg_scale`` and ``edge_encoder`` exist for ``state_dict`` parity; the reference's forward uses neither.
+    With ``mask=True`` (the destination mask: 1 exactly where a node has an incoming membership edge) only those ``R``
+    rows are non-zero, and the MLP runs on them alone -- exact whenever the MLP's norm is per row.  A BatchNorm in
+    training mode takes its statistics over all ``N`` rows in the reference: the layer then runs all rows."""
+
+    def __init__(self, in_dim, emb_dim, aggr='softmax', t=1.0, learn_t=False, p=1.0, learn_p=False,
+                 y=0.0, learn_y=False, msg_norm=False, learn_msg_scale=True, encode_edge=False, bond_encoder=False,
+                 edge_feat_dim=None, norm='batch', mlp_layers=2, eps=1e-7):
+        super().__init__(aggr=aggr, t=t, learn_t=learn_t, p=p, learn_p=learn_p, y=y, learn_y=learn_y)
+        if bond_encoder:
+            raise NotImplementedError("OGB bond encoder is outside the accelerated path")
+        self.mlp = MLP([in_dim] + [in_dim * 2] * (mlp_layers - 1) + [emb_dim], norm=norm, last_lin=True)
+        self.msg_encoder = nn.Linear(2 * in_dim, in_dim)
+        self.eps = eps
+        self.encode_edge = encode_edge
+        self.bond_encoder = bond_encoder
+        self.msg_norm = MsgNorm(learn_msg_scale=learn_msg_scale) if msg_norm else None
+        if encode_edge:
+            self.edge_encoder = nn.Linear(edge_feat_dim, in_dim)
+        self.all_rows = False           # (True: the MLP over all N rows even where the compact form is exact; for A/B runs)
+
+    def _batch_statistics(self):
+        return self.training and any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in self.mlp)
+
+    def forward(self, x, edge_index, edge_attr=None, mask=None, residual=None):
+        """``edge_index``: COO ``[2, E_p]`` (global node ids) or a prebuilt :class:`mlgnn.pathway_conv.PathwayTopology`
+        (then ``edge_attr`` may be omitted: the topology holds it).  ``mask``: None, a ``[N, 1]`` tensor, or True for
+        the destination mask.  ``residual``: added to the result (the caller's ``conv(...) + h``)."""
+        from mlgnn import pathway_conv as pc
+        topo = edge_index if isinstance(edge_index, pc.PathwayTopology) else None
+        if topo is not None and edge_attr is None:
+            edge_attr = topo.edge_attr
+        if edge_attr is None:
+            raise ValueError("PathwayConv needs the [E, 2] edge attributes (its message encoder is Linear(2 * in_dim, in_dim))")
+        W, b = self.msg_encoder.weight, self.msg_encoder.bias
+        if not pc.PATHWAY_CONV:
+            ei = topo.edge_index if topo is not None else edge_index
+            pc.STATS["torch_layers"] += 1
+            out = F.relu(self.mlp(x + self.reduce_pathway_messages_torch(x, ei, edge_attr, W, b)))
+            if mask is True:
+                mask = torch.zeros((x.shape[0], 1), dtype=x.dtype, device=x.device).index_fill_(0, ei[1], 1.0)
+            if mask is not None:
+                out = out * mask
+            return out if residual is None else out + residual
+        if topo is None:
+            topo = pc.PathwayTopology.from_cache((edge_index, edge_attr), x.shape[0],
+                                                 lambda: pc.PathwayTopology(edge_index, edge_attr, x.shape[0]))
+        m = self.reduce_pathway_messages(x, topo, W, b)                          # [R, d]
+        rows = topo.rows_long
+        if mask is True and not self.all_rows and not self._batch_statistics():
+            pc.STATS["compact_layers"] += 1
+            out = F.relu(self.mlp(x.index_select(0, rows) + m))
+            base = residual if residual is not None else torch.zeros_like(x)
+            return base.index_add(0, rows, out)
+        pc.STATS["all_rows_layers"] += 1
+        out = F.relu(self.mlp(x.index_add(0, rows, m)))
+        if mask is True:
+            mask = (topo.row_of >= 0).to(out.dtype).unsqueeze(1)
+        if mask is not None:
+            out = out * mask
         return out if residual is None else out + residual
 
 

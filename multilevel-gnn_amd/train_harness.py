@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Training harness with the step semantics of the reference's ``train.py`` (``train`` :38-69,
 ``eval`` :71-109, ``run`` :111-213) on the synthetic TCGA-shaped dataset -- the reference's own
-script needs torch_geometric's DataLoader and the (absent) TCGA files.
+script needs torch_geometric's DataLoader and the (absent) TCGA files.  ``--model multiomix`` trains the multi-omics
+model on :class:`mlgnn.data.SyntheticMultiOmix` (its criterion is the BCE term alone).
 
   python multilevel-gnn_amd/train_harness.py --config /path/to/config/gbm.yaml --epochs 2 --patients 96
 
@@ -22,7 +23,7 @@ import yaml
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
-from mlgnn.data import DataLoader, SyntheticTCGA  # noqa: E402
+from mlgnn.data import DataLoader, SyntheticMultiOmix, SyntheticTCGA  # noqa: E402
 from mlgnn.dist import broadcast_parameters  # noqa: E402
 from mlgnn.optim import FlatAdam, StepLR  # noqa: E402
 from models import get_model  # noqa: E402
@@ -76,6 +77,15 @@ def parse_opts(argv=None):
     return args
 
 
+def _predict(model, batch):
+    """``(pred, feature loss)``: the models with a projection return ``(pred, pca_feature)``; 'multiomix' returns the
+    probabilities alone, and its criterion is the BCE term alone."""
+    out = model(batch)
+    if isinstance(out, tuple):
+        return out[0], model.get_feature_loss(out[1])
+    return out, 0.0
+
+
 def train_epoch(model, device, loader, optimizer, criterion, criterion_weight, args, bucket):
     """``train.py:38-69``: BCE on the probabilities + feature loss, optional clip, one optimizer step per batch."""
     losses = []
@@ -83,8 +93,7 @@ def train_epoch(model, device, loader, optimizer, criterion, criterion_weight, a
     for step, batch in enumerate(loader):
         batch = batch.to(device)
         model.step = step
-        pred, pca_feature = model(batch)
-        loss_feature = model.get_feature_loss(pca_feature)
+        pred, loss_feature = _predict(model, batch)
         bucket.release()
         target = batch.y.reshape(-1, 2).to(torch.float32)
         if args.weighted_loss or args.batch_weighted_loss:
@@ -110,7 +119,7 @@ def evaluate(model, device, loader, criterion):
     ys, ps, losses = [], [], []
     for batch in loader:
         batch = batch.to(device)
-        pred, _ = model(batch)
+        pred, _ = _predict(model, batch)
         target = batch.y.reshape(-1, 2).to(torch.float32)
         losses.append(criterion(pred.to(torch.float32), target))
         ys.append(target)
@@ -135,7 +144,15 @@ def run(args):
     torch.manual_seed(args.seed)
 
     small = dict(node_num=60, n_edges=500, n_members=900) if args.small else {}
-    data = SyntheticTCGA(args.patients, pca_dim=args.pca_dim, seed=args.seed, with_raw_data=(args.model == "pathcnn"), **small)
+    if args.model == "multiomix":
+        # the multi-omics cohort: gene + pathway nodes, per-omics membership edges; one scalar weight per gene edge
+        small = dict(node_num=40, pathway_num=8, n_edges=160, n_members=60) if args.small else {}
+        data = SyntheticMultiOmix(args.patients, seed=args.seed, **small)
+        args.pathway_num = data.pathway_num
+        if args.use_column is None:
+            args.use_column = "weight"
+    else:
+        data = SyntheticTCGA(args.patients, pca_dim=args.pca_dim, seed=args.seed, with_raw_data=(args.model == "pathcnn"), **small)
     n_train = int(0.7 * len(data)) // (args.batch_size * world) * (args.batch_size * world)
     idx = torch.randperm(len(data), generator=torch.Generator().manual_seed(args.seed)).tolist()
     train_idx, valid_idx = idx[:n_train][rank::world], idx[n_train:]
