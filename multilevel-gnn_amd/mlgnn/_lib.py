@@ -1,6 +1,10 @@
 """ctypes binding of the C ABI in include/mlgnn.h.  Fails loudly when the library is missing."""
+import atexit
 import ctypes
 import os
+import sys
+
+import torch
 
 # (MLGNN_LIB: a development override for same-box A/B runs of kernel variants, tools/build_variant.py)
 LIB = os.environ.get("MLGNN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libmlgnn.so")
@@ -11,7 +15,7 @@ _I64 = _c.c_int64
 _INT = _c.c_int
 _F = _c.c_float
 
-# name -> (restype, argtypes); mirrors include/mlgnn.h one to one (tests check the export list)
+# name -> (restype, argtypes); mirrors include/mlgnn.h one to one (tests/test_abi.py compares names and types)
 SIGNATURES = {
     "mlgnn_version": (_INT, []),
     "mlgnn_csr_aggregate_bwd_workspace_floats": (_I64, [_I64, _I64, _INT, _INT, _INT, _INT]),
@@ -253,7 +257,6 @@ class _CanaryLib:
 
 
 def _install_canary():
-    import torch
     alloc = torch.cuda.memory.CUDAPluggableAllocator(LIB, "mlgnn_canary_malloc", "mlgnn_canary_free")
     torch.cuda.memory.change_current_allocator(alloc)       # raises if the process has allocated device memory already
     return alloc
@@ -275,3 +278,42 @@ def check(code, what):
 def ptr(t):
     """Device address of a tensor (None -> NULL)."""
     return None if t is None else t.data_ptr()
+
+
+def stream():
+    """Raw handle of torch's current stream."""
+    return torch.cuda.current_stream().cuda_stream
+
+
+def call(name, *args):
+    """Launch the status-returning entry point ``name``: every tensor goes in as its address (``None`` as NULL), anything
+    else unchanged; a non-zero status raises :class:`MlgnnError`.  A tensor a kernel cannot read (neither on the device nor
+    in pinned host memory) is refused here, before its host address reaches a kernel.  ``name`` is looked up on ``lib`` at
+    call time (MLGNN_CANARY and the tests replace attributes of it)."""
+    argv = list(args)
+    for i, a in enumerate(argv):
+        if isinstance(a, torch.Tensor):
+            if not a.is_cuda and not a.is_pinned():
+                raise TypeError("%s: argument %d is a %s tensor in pageable host memory; the kernels read device (or "
+                                "pinned) memory only" % (name, i, a.device))
+            argv[i] = a.data_ptr()
+    check(getattr(lib, name)(*argv), name)
+
+
+def require_gpu(t, who):
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise RuntimeError("%s has no CPU path (the kernels are HIP only); move the tensors to the GPU" % who)
+
+
+_STATS = []      # (name, counters, suffix) of every stats() dict, in import order
+
+
+def stats(name, suffix="", **counters):
+    """The counters dict of one op (which path its calls took; models and tests read and bump it), registered for the
+    MLGNN_PRINT_STATS=1 report at exit."""
+    _STATS.append((name, counters, suffix))
+    return counters
+
+
+if os.environ.get("MLGNN_PRINT_STATS", "0") == "1":          # development: which paths a run took
+    atexit.register(lambda: print("".join("mlgnn stats: %s %r%s\n" % s for s in _STATS), end="", file=sys.stderr))

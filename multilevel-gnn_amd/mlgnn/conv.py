@@ -13,18 +13,12 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .ops import _stream
 
 # MLGNN_PATH_CONV=0: PathConv2d and HeadConv2d always take the convolution library (same-box A/B runs)
 ENABLED = os.environ.get("MLGNN_PATH_CONV", "1") != "0"
 
 # how often each path was taken (development / tests: which path a model ran on)
-CONV_STATS = {"hip": 0, "library": 0}
-
-if os.environ.get("MLGNN_PRINT_STATS", "0") == "1":
-    import atexit
-    import sys
-    atexit.register(lambda: print("mlgnn stats: conv2d %r" % (CONV_STATS,), file=sys.stderr))
+CONV_STATS = _lib.stats("conv2d", hip=0, library=0)
 
 
 def conv2d_supported(x, weight):
@@ -50,9 +44,7 @@ class _Conv2d(torch.autograd.Function):
         B, H, W, Cin = xr.shape
         Cout, k = weight.shape[0], weight.shape[2]
         y = torch.empty((B, H, W, Cout), dtype=torch.float32, device=xr.device)
-        rc = _lib.lib.mlgnn_conv2d_fwd(xr.data_ptr(), weight.data_ptr(), _lib.ptr(bias), y.data_ptr(), int(bool(relu)),
-                                       B, H, W, Cin, Cout, k, _stream())
-        _lib.check(rc, "mlgnn_conv2d_fwd")
+        _lib.call("mlgnn_conv2d_fwd", xr, weight, bias, y, int(bool(relu)), B, H, W, Cin, Cout, k, _lib.stream())
         CONV_STATS["hip"] += 1
         ctx.save_for_backward(xr, weight, y if relu else None)
         ctx.cfg = (B, H, W, Cin, Cout, k, bool(relu), bias is not None)
@@ -75,10 +67,8 @@ class _Conv2d(torch.autograd.Function):
         if need_w or need_b:
             floats = int(_lib.lib.mlgnn_conv2d_bwd_workspace_floats(B, H, W, Cin, Cout, k))
             ws = torch.empty(max(floats, 1), **f32)
-        rc = _lib.lib.mlgnn_conv2d_bwd(gy.data_ptr(), xr.data_ptr(), weight.data_ptr(), _lib.ptr(y), int(relu),
-                                       _lib.ptr(gx), _lib.ptr(gw), _lib.ptr(gb), _lib.ptr(ws), floats,
-                                       B, H, W, Cin, Cout, k, _stream())
-        _lib.check(rc, "mlgnn_conv2d_bwd")
+        _lib.call("mlgnn_conv2d_bwd", gy, xr, weight, y, int(relu), gx, gw, gb, ws, floats, B, H, W, Cin, Cout, k,
+                  _lib.stream())
         if B == 0:
             gw = torch.zeros_like(weight) if need_w else None
             gb = torch.zeros((Cout,), **f32) if need_b else None
@@ -89,8 +79,7 @@ def conv2d(x, weight, bias=None, relu=False):
     """``F.conv2d(x, weight, bias, padding=k // 2)`` (``relu``: followed by ReLU) for ``x`` [B, Cin, H, W], contiguous or
     channel-last; the result is ``[B, Cout, H, W]``, channel-last in memory.  The caller checks
     :func:`conv2d_supported` first."""
-    if not (torch.is_tensor(x) and x.is_cuda):
-        raise RuntimeError("mlgnn.conv has no CPU path (the kernels are HIP only); move the tensors to the GPU")
+    _lib.require_gpu(x, "mlgnn.conv")
     if not conv2d_supported(x, weight):
         raise ValueError("conv2d: unsupported input %s %s with weight %s (fp32, k in {3, 5}, <= 128 channels, W <= 32, "
                          "< 4 GiB)" % (tuple(x.shape), x.dtype, tuple(weight.shape)))

@@ -15,7 +15,6 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .ops import _stream
 
 # MLGNN_CRITERION_FUSED=0: TrainCriterion always takes the torch lines (same-box A/B runs).  On by default: forward +
 # backward beats the torch lines by more than their spread at the gbm and kirc shapes (profiles/criterion.json).
@@ -23,12 +22,7 @@ DEFAULT_ENABLED = True
 ENABLED = os.environ.get("MLGNN_CRITERION_FUSED", "1" if DEFAULT_ENABLED else "0") != "0"
 
 # how often each path was taken (development / tests: which path a step ran on)
-CRITERION_STATS = {"hip": 0, "torch": 0}
-
-if os.environ.get("MLGNN_PRINT_STATS", "0") == "1":
-    import atexit
-    import sys
-    atexit.register(lambda: print("mlgnn stats: criterion %r" % (CRITERION_STATS,), file=sys.stderr))
+CRITERION_STATS = _lib.stats("criterion", hip=0, torch=0)
 
 MODES = {"plain": 0, "class": 1, "sample": 2, "batch": 3}
 
@@ -65,10 +59,8 @@ class _Criterion(torch.autograd.Function):
         ws = torch.empty(n_ws, dtype=torch.float32, device=dev) if n_ws else None
         stats = torch.empty((2, M), dtype=torch.float32, device=dev) if (M and want[1]) else None
         cw_rows = 0 if (cw is None or cw.dim() == 1) else cw.shape[0]
-        rc = _lib.lib.mlgnn_criterion_fwd(pred.data_ptr(), y.data_ptr(), _lib.ptr(cw), cw_rows, _lib.ptr(feat), coef, mode,
-                                          _lib.ptr(ws), n_ws, _lib.ptr(stats), loss.data_ptr(), terms.data_ptr(), B, M,
-                                          _stream())
-        _lib.check(rc, "mlgnn_criterion_fwd")
+        _lib.call("mlgnn_criterion_fwd", pred, y, cw, cw_rows, feat, coef, mode, ws, n_ws, stats, loss, terms, B, M,
+                  _lib.stream())
         CRITERION_STATS["hip"] += 1
         if want[0] or want[1]:
             ctx.save_for_backward(pred, y, cw, feat if want[1] else None, stats, terms)
@@ -88,10 +80,8 @@ class _Criterion(torch.autograd.Function):
         grad_loss = grad_loss.to(torch.float32).contiguous()
         grad_pred = torch.empty_like(pred) if want_pred else None
         grad_feat = torch.empty_like(feat) if want_feat else None
-        rc = _lib.lib.mlgnn_criterion_bwd(pred.data_ptr(), y.data_ptr(), _lib.ptr(cw), cw_rows, _lib.ptr(feat),
-                                          _lib.ptr(stats), terms.data_ptr(), grad_loss.data_ptr(), coef, mode,
-                                          _lib.ptr(grad_pred), _lib.ptr(grad_feat), B, M, _stream())
-        _lib.check(rc, "mlgnn_criterion_bwd")
+        _lib.call("mlgnn_criterion_bwd", pred, y, cw, cw_rows, feat, stats, terms, grad_loss, coef, mode, grad_pred,
+                  grad_feat, B, M, _lib.stream())
         return grad_pred, None, None, grad_feat, None, None, None
 
 
@@ -101,8 +91,7 @@ def train_criterion(pred, y, feat=None, pca_loss_coef=0.0, mode="plain", class_w
     ``[B, 2]`` probabilities, ``y`` the labels (``B * 2`` values), ``feat`` anything with ``B`` rows (made contiguous and
     seen as ``[B, M]``), ``class_weight`` ``[2]``, ``[B, 2]`` or, for ``'sample'`` / ``'batch'``, ``[R >= B, 2]``.
     Gradients flow to ``pred`` and ``feat`` only.  The caller checks :func:`criterion_supported` first."""
-    if not (torch.is_tensor(pred) and pred.is_cuda):
-        raise RuntimeError("mlgnn.train_criterion has no CPU path (the kernels are HIP only); move the tensors to the GPU")
+    _lib.require_gpu(pred, "mlgnn.train_criterion")
     if mode not in MODES:
         raise ValueError("train_criterion: unknown mode %r (one of %s)" % (mode, ", ".join(MODES)))
     if not criterion_supported(pred, feat):

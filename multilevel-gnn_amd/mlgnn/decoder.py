@@ -12,18 +12,12 @@ import os
 import torch
 
 from . import _lib
-from .ops import _stream
 
 # MLGNN_DECODER_FUSED=0: foreach_decoder always takes the torch paths (same-box A/B runs)
 ENABLED = os.environ.get("MLGNN_DECODER_FUSED", "1") != "0"
 
 # how often each path was taken (development / tests: which path a model ran on)
-DECODER_STATS = {"hip": 0, "torch": 0}
-
-if os.environ.get("MLGNN_PRINT_STATS", "0") == "1":
-    import atexit
-    import sys
-    atexit.register(lambda: print("mlgnn stats: decoder %r" % (DECODER_STATS,), file=sys.stderr))
+DECODER_STATS = _lib.stats("decoder", hip=0, torch=0)
 
 RULE = ("fp32, contiguous [B, P, H], B <= 256, 1 <= H <= 128, 1 <= hid <= 256, "
         "B * (max(H4, 16) + hid4) + max(B * hid4, 2112) <= 40960 with H4, hid4 = H, max hid rounded up to 4, "
@@ -75,10 +69,8 @@ class _Decoder(torch.autograd.Function):
     def forward(ctx, h, w1, b1, w2, b2, hid_off, out_off, w2_off, limits):
         B, P, H = h.shape
         out = torch.empty((B, limits[2]), dtype=torch.float32, device=h.device)
-        rc = _lib.lib.mlgnn_pathway_decoder_fwd(h.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
-                                                hid_off.data_ptr(), out_off.data_ptr(), w2_off.data_ptr(), out.data_ptr(),
-                                                B, P, H, *limits, _stream())
-        _lib.check(rc, "mlgnn_pathway_decoder_fwd")
+        _lib.call("mlgnn_pathway_decoder_fwd", h, w1, b1, w2, b2, hid_off, out_off, w2_off, out, B, P, H, *limits,
+                  _lib.stream())
         DECODER_STATS["hip"] += 1
         if any(ctx.needs_input_grad[:5]):
             ctx.save_for_backward(h, w1, b1, w2, hid_off, out_off, w2_off)
@@ -98,10 +90,8 @@ class _Decoder(torch.autograd.Function):
         like = (h, w1, b1, w2)
         grads = [torch.empty_like(like[i]) if needs[i] else None for i in range(4)]
         grads.append(torch.empty(ctx.b2_shape, dtype=torch.float32, device=h.device) if needs[4] else None)
-        rc = _lib.lib.mlgnn_pathway_decoder_bwd(h.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), g.data_ptr(),
-                                                hid_off.data_ptr(), out_off.data_ptr(), w2_off.data_ptr(),
-                                                *[_lib.ptr(t) for t in grads], B, P, H, *ctx.limits, _stream())
-        _lib.check(rc, "mlgnn_pathway_decoder_bwd")
+        _lib.call("mlgnn_pathway_decoder_bwd", h, w1, b1, w2, g, hid_off, out_off, w2_off, *grads, B, P, H,
+                  *ctx.limits, _lib.stream())
         return (*grads, None, None, None, None)
 
 
@@ -110,8 +100,7 @@ def pathway_decoders(h, w1, b1, w2, b2, hid_off, out_off, w2_off, limits=None):
     ``[B, N]``.  ``w1, b1, w2, b2``: the packed parameters (1-D), ``hid_off, out_off, w2_off``: :func:`offset_tables`
     on ``h``'s device.  ``limits``: ``(max_hid, max_out, total_out)`` when the caller knows them (a module computes
     them once); without it the tables are read back and checked, which synchronises."""
-    if not (torch.is_tensor(h) and h.is_cuda):
-        raise RuntimeError("mlgnn.pathway_decoders has no CPU path (the kernels are HIP only); move the tensors to the GPU")
+    _lib.require_gpu(h, "mlgnn.pathway_decoders")
     tables = (hid_off, out_off, w2_off)
     if any(not (torch.is_tensor(t) and t.device == h.device and t.dtype == torch.int64 and t.dim() == 1) for t in tables):
         raise ValueError("pathway_decoders: hid_off, out_off, w2_off must be int64 vectors on h's device")

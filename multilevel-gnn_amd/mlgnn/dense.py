@@ -7,7 +7,7 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .norm import ln_backward_normalised, ln_backward_saved
-from .ops import _DTYPE_IDS, _stream
+from .ops import _DTYPE_IDS
 from .tags import PostLN, backward_of, f32_cached, row_max_of, softmax_lse_of, tag_post_ln, tag_row_max, tag_shifted
 
 DIFFPOOL_EPS = 1e-15
@@ -52,10 +52,8 @@ def tall_matmul_nt(a, bt, bias=None, residual=None, row_max=None, ln=None, bt_tr
             eps = float(ln[3])
             rstd = torch.empty(N, dtype=torch.float32, device=a.device)
             rmax = torch.empty(N, dtype=torch.float32, device=a.device)
-    rc = _lib.lib.mlgnn_tallgemm_nt(a.data_ptr(), bt.data_ptr(), int(bt_transposed), _lib.ptr(bias), _lib.ptr(residual),
-                                    _lib.ptr(row_max), mode, _lib.ptr(gamma), _lib.ptr(beta), eps, _lib.ptr(rstd),
-                                    _lib.ptr(rmax), out.data_ptr(), ws.data_ptr(), nbytes, N, R, J, dt, _stream())
-    _lib.check(rc, "mlgnn_tallgemm_nt")
+    _lib.call("mlgnn_tallgemm_nt", a, bt, int(bt_transposed), bias, residual, row_max, mode, gamma, beta, eps, rstd,
+              rmax, out, ws, nbytes, N, R, J, dt, _lib.stream())
     return (out, rstd, rmax) if mode == 1 else out
 
 
@@ -77,13 +75,9 @@ def tall_matmul_lnin_postln(xhat, w, bias, residual, row_max, gamma, beta, post)
         bias = f32_cached(bias)
     ROW_MAX_STATS["given" if row_max is not None else "computed"] += 1
     g2, b2, eps2, relu = post
-    rc = _lib.lib.mlgnn_tallgemm_lnin_postln(xhat.data_ptr(), w.data_ptr(), _lib.ptr(bias), _lib.ptr(residual),
-                                             _lib.ptr(row_max), gamma.contiguous().data_ptr(),
-                                             beta.contiguous().data_ptr(), g2.contiguous().data_ptr(),
-                                             b2.contiguous().data_ptr(), float(eps2), int(bool(relu)), out.data_ptr(),
-                                             y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(), nbytes,
-                                             N, R, J, _stream())
-    _lib.check(rc, "mlgnn_tallgemm_lnin_postln")
+    _lib.call("mlgnn_tallgemm_lnin_postln", xhat, w, bias, residual, row_max, gamma.contiguous(), beta.contiguous(),
+              g2.contiguous(), b2.contiguous(), float(eps2), int(bool(relu)), out, y, mean, rstd, ws, nbytes, N, R, J,
+              _lib.stream())
     return out, y, mean, rstd
 
 
@@ -100,10 +94,8 @@ def tall_matmul_nt_shift(a, w, row_max, lse, rowptr):
     nbytes = int(_lib.lib.mlgnn_tallgemm_workspace_bytes(R, J, 0))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
     ROW_MAX_STATS["given" if row_max is not None else "computed"] += 1
-    rc = _lib.lib.mlgnn_tallgemm_nt_shift(a.data_ptr(), w.data_ptr(), 1, _lib.ptr(row_max), lse.data_ptr(),
-                                          rowptr.data_ptr(), gx.data_ptr(), gt.data_ptr(), flag.data_ptr(),
-                                          ws.data_ptr(), nbytes, N, R, J, _stream())
-    _lib.check(rc, "mlgnn_tallgemm_nt_shift")
+    _lib.call("mlgnn_tallgemm_nt_shift", a, w, 1, row_max, lse, rowptr, gx, gt, flag, ws, nbytes, N, R, J,
+              _lib.stream())
     return gx, gt, flag
 
 
@@ -119,9 +111,7 @@ def tall_matmul_bf16_shift(go, weight, lse):
     flag = torch.empty(4, dtype=torch.int32, device=go.device)
     nbytes = int(_lib.lib.mlgnn_tallgemm_workspace_bytes(M, K, 1))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=go.device)
-    rc = _lib.lib.mlgnn_tallgemm_bf16_shift(go.data_ptr(), bt.data_ptr(), lse.data_ptr(), gx.data_ptr(), gt.data_ptr(),
-                                            flag.data_ptr(), ws.data_ptr(), nbytes, N, M, K, _stream())
-    _lib.check(rc, "mlgnn_tallgemm_bf16_shift")
+    _lib.call("mlgnn_tallgemm_bf16_shift", go, bt, lse, gx, gt, flag, ws, nbytes, N, M, K, _lib.stream())
     return gx, gt, flag
 
 
@@ -138,10 +128,8 @@ def tall_matmul_ln_backward(go, w, xhat, rstd, gamma, beta, row_max=None):
     nbytes = int(_lib.lib.mlgnn_tallgemm_lnbwd_workspace_bytes(R, J))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=go.device)
     ROW_MAX_STATS["given" if row_max is not None else "computed"] += 1
-    rc = _lib.lib.mlgnn_tallgemm_lnbwd(go.data_ptr(), w.data_ptr(), 1, _lib.ptr(row_max), xhat.data_ptr(), rstd.data_ptr(),
-                                       gamma.contiguous().data_ptr(), beta.contiguous().data_ptr(), gh.data_ptr(),
-                                       rmax.data_ptr(), ggb.data_ptr(), ws.data_ptr(), nbytes, N, R, J, _stream())
-    _lib.check(rc, "mlgnn_tallgemm_lnbwd")
+    _lib.call("mlgnn_tallgemm_lnbwd", go, w, 1, row_max, xhat, rstd, gamma.contiguous(), beta.contiguous(), gh, rmax,
+              ggb, ws, nbytes, N, R, J, _lib.stream())
     return gh, ggb[0], ggb[1], rmax
 
 
@@ -182,11 +170,8 @@ def linear_backward(go, w, x, go_max, x_max, epilogue, rstd=None, gamma=None, be
     ws = torch.empty(n, **f32)
     if gamma is not None:
         gamma, beta = gamma.contiguous(), beta.contiguous()
-    rc = _lib.lib.mlgnn_linear_bwd(go.data_ptr(), w.data_ptr(), x.data_ptr(), go_max.data_ptr(), int(go_max_is_parts),
-                                   x_max.data_ptr(), epilogue, _lib.ptr(rstd), _lib.ptr(gamma), _lib.ptr(beta),
-                                   _lib.ptr(lse), dx.data_ptr(), _lib.ptr(gt), _lib.ptr(flag), gwb.data_ptr(),
-                                   parts.data_ptr(), ws.data_ptr(), n, N, M, K, _stream())
-    _lib.check(rc, "mlgnn_linear_bwd")
+    _lib.call("mlgnn_linear_bwd", go, w, x, go_max, int(go_max_is_parts), x_max, epilogue, rstd, gamma, beta, lse, dx,
+              gt, flag, gwb, parts, ws, n, N, M, K, _lib.stream())
     out = dict(dx=dx, gw=gwb[:M * K].view(M, K), gb=gwb[M * K:M * K + M], parts=parts, gt=gt, flag=flag)
     if epilogue == LB_LN:
         out["ggamma"], out["gbeta"] = gwb[M * K + M:M * K + M + K], gwb[M * K + M + K:]
@@ -218,9 +203,7 @@ def _wgrad(go, x, x_gamma=None, x_beta=None, go_max=None, x_max=None, out_dtype=
     if (x.dtype != torch.float32 or go_max is None or x_max is None or _WGRAD_EXACT
             or go_max.shape[0] != N or x_max.shape[0] != N):
         go_max = x_max = None
-    rc = _lib.lib.mlgnn_linear_wgrad(go.data_ptr(), x.data_ptr(), _lib.ptr(x_gamma), _lib.ptr(x_beta), _lib.ptr(go_max),
-                                     _lib.ptr(x_max), out.data_ptr(), ws.data_ptr(), n, N, M, K, dt, _stream())
-    _lib.check(rc, "mlgnn_linear_wgrad")
+    _lib.call("mlgnn_linear_wgrad", go, x, x_gamma, x_beta, go_max, x_max, out, ws, n, N, M, K, dt, _lib.stream())
     if out_dtype is not None and out_dtype != torch.float32:
         out = out.to(out_dtype)                      # weight and bias gradient of a bf16 model: ONE converting copy
     return out[:M * K].view(M, K), out[M * K:]
@@ -460,9 +443,7 @@ class _WideLinearF32(torch.autograd.Function):
         y = torch.empty((Np, J), dtype=torch.float32, device=x.device)
         ws = torch.empty(int(_lib.lib.mlgnn_linear_f32x3_fwd_workspace_bytes(N, R, J)), dtype=torch.uint8, device=x.device)
         b = bias.contiguous() if bias is not None else None
-        rc = _lib.lib.mlgnn_linear_f32x3_fwd(x.data_ptr(), weight.data_ptr(), _lib.ptr(b), y.data_ptr(), ws.data_ptr(),
-                                             ws.numel(), N, R, J, _stream())
-        _lib.check(rc, "mlgnn_linear_f32x3_fwd")
+        _lib.call("mlgnn_linear_f32x3_fwd", x, weight, b, y, ws, ws.numel(), N, R, J, _lib.stream())
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         return y[:N]
@@ -478,9 +459,7 @@ class _WideLinearF32(torch.autograd.Function):
         gw = torch.empty((J, R), dtype=torch.float32, device=x.device)
         ws = torch.empty(int(_lib.lib.mlgnn_linear_f32x3_bwd_workspace_bytes(N, R, J)), dtype=torch.uint8, device=x.device)
         gb = torch.empty(J, dtype=torch.float32, device=x.device) if ctx.has_bias else None
-        rc = _lib.lib.mlgnn_linear_f32x3_bwd(go.data_ptr(), x.data_ptr(), weight.data_ptr(), _lib.ptr(gx), gw.data_ptr(),
-                                             _lib.ptr(gb), ws.data_ptr(), ws.numel(), N, R, J, _stream())
-        _lib.check(rc, "mlgnn_linear_f32x3_bwd")
+        _lib.call("mlgnn_linear_f32x3_bwd", go, x, weight, gx, gw, gb, ws, ws.numel(), N, R, J, _lib.stream())
         return (gx[:N] if gx is not None else None), gw, gb
 
 
@@ -519,9 +498,7 @@ class _SkinnyLinear(torch.autograd.Function):
         n = int(_lib.lib.mlgnn_skinny_linear_fwd_workspace_floats(M, J, K))
         ws = torch.empty(n, dtype=torch.float32, device=x.device)
         b = bias.contiguous() if bias is not None else None
-        rc = _lib.lib.mlgnn_skinny_linear_fwd(x.data_ptr(), w.data_ptr(), _lib.ptr(b), y.data_ptr(), ws.data_ptr(), n, M, J, K,
-                                              _stream())
-        _lib.check(rc, "mlgnn_skinny_linear_fwd")
+        _lib.call("mlgnn_skinny_linear_fwd", x, w, b, y, ws, n, M, J, K, _lib.stream())
         ctx.save_for_backward(x, w)
         ctx.has_bias = bias is not None
         ctx.slot, ctx.param = getattr(weight, "_mlgnn_grad_slot", None), weight
@@ -545,9 +522,7 @@ class _SkinnyLinear(torch.autograd.Function):
             else:
                 gw = torch.empty((J, K), dtype=torch.float32, device=x.device)
         gb = torch.empty(J, dtype=torch.float32, device=x.device) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-        rc = _lib.lib.mlgnn_skinny_linear_bwd(go.data_ptr(), x.data_ptr(), w.data_ptr(), _lib.ptr(gx), _lib.ptr(gw),
-                                              _lib.ptr(gb), M, J, K, _stream())
-        _lib.check(rc, "mlgnn_skinny_linear_bwd")
+        _lib.call("mlgnn_skinny_linear_bwd", go, x, w, gx, gw, gb, M, J, K, _lib.stream())
         return gx, gw, gb
 
 
@@ -564,8 +539,7 @@ class _NarrowLinear(torch.autograd.Function):
         J = w.shape[0]
         y = torch.empty((N, J), dtype=torch.float32, device=x.device)
         b = bias.contiguous() if bias is not None else None
-        rc = _lib.lib.mlgnn_narrow_linear_fwd(x.data_ptr(), w.data_ptr(), _lib.ptr(b), y.data_ptr(), N, R, J, _stream())
-        _lib.check(rc, "mlgnn_narrow_linear_fwd")
+        _lib.call("mlgnn_narrow_linear_fwd", x, w, b, y, N, R, J, _lib.stream())
         ctx.save_for_backward(x, w)
         ctx.has_bias = bias is not None
         return y
@@ -581,9 +555,7 @@ class _NarrowLinear(torch.autograd.Function):
             n = int(_lib.lib.mlgnn_narrow_linear_bwd_workspace_floats(R, J))
             ws = torch.empty(n, dtype=torch.float32, device=x.device)
             out = torch.empty(J * R + J, dtype=torch.float32, device=x.device)
-            rc = _lib.lib.mlgnn_narrow_linear_bwd(go.data_ptr(), x.data_ptr(), out.data_ptr(), ws.data_ptr(), n, N, R, J,
-                                                  _stream())
-            _lib.check(rc, "mlgnn_narrow_linear_bwd")
+            _lib.call("mlgnn_narrow_linear_bwd", go, x, out, ws, n, N, R, J, _lib.stream())
             gw, gb = out[:J * R].view(J, R), (out[J * R:] if ctx.has_bias else None)
         gx = go.matmul(w) if ctx.needs_input_grad[0] else None
         return gx, gw, gb
@@ -636,10 +608,8 @@ class _DenseSageFused(torch.autograd.Function):
         rinv = torch.empty((B, n), dtype=torch.float32, device=x.device)
         ctx.bias_dtype = bias.dtype if bias is not None else None
         bias32 = f32_cached(bias) if bias is not None else None           # the kernels add the bias in fp32
-        rc = _lib.lib.mlgnn_dense_sage_fwd(x.data_ptr(), adj.data_ptr(), w_rel.data_ptr(), w_root.data_ptr(),
-                                           _lib.ptr(bias32), y.data_ptr(), rinv.data_ptr(), B, n, C, O, int(batched),
-                                           int(normalize), _DTYPE_IDS[x.dtype], _stream())
-        _lib.check(rc, "mlgnn_dense_sage_fwd")
+        _lib.call("mlgnn_dense_sage_fwd", x, adj, w_rel, w_root, bias32, y, rinv, B, n, C, O, int(batched),
+                  int(normalize), _DTYPE_IDS[x.dtype], _lib.stream())
         ctx.save_for_backward(x, adj, w_rel, w_root, y, rinv)
         ctx.cfg = (batched, bool(normalize), bias is not None)
         return y
@@ -657,11 +627,8 @@ class _DenseSageFused(torch.autograd.Function):
         gw = torch.empty(2 * O * C + O, dtype=torch.float32, device=x.device)
         ws_n = int(_lib.lib.mlgnn_dense_sage_bwd_workspace_floats(B, C, O))
         ws = torch.empty(ws_n, dtype=torch.float32, device=x.device)
-        rc = _lib.lib.mlgnn_dense_sage_bwd(gy.data_ptr(), y.data_ptr(), rinv.data_ptr(), x.data_ptr(), adj.data_ptr(),
-                                           w_rel.data_ptr(), w_root.data_ptr(), gx.data_ptr(), _lib.ptr(gadj),
-                                           gw.data_ptr(), ws.data_ptr(), ws_n, B, n, C, O, int(batched),
-                                           int(normalize), _DTYPE_IDS[x.dtype], _stream())
-        _lib.check(rc, "mlgnn_dense_sage_bwd")
+        _lib.call("mlgnn_dense_sage_bwd", gy, y, rinv, x, adj, w_rel, w_root, gx, gadj, gw, ws, ws_n, B, n, C, O,
+                  int(batched), int(normalize), _DTYPE_IDS[x.dtype], _lib.stream())
         if need_adj and not batched:
             gadj = gadj.float().sum(0, keepdim=True).to(adj.dtype).reshape(adj.shape)          # shared adjacency
         elif need_adj:
@@ -710,10 +677,8 @@ class _DiffPoolFused(torch.autograd.Function):
         x_out = torch.empty((B, K, C), dtype=z.dtype, device=z.device)
         a_out = torch.empty((B, K, K), dtype=z.dtype, device=z.device)
         partial = torch.empty((B, 2), dtype=torch.float32, device=z.device)
-        rc = _lib.lib.mlgnn_diffpool_fwd(z.data_ptr(), adj_k.data_ptr(), s.data_ptr(), S.data_ptr(),
-                                         x_out.data_ptr(), a_out.data_ptr(), partial.data_ptr(), B, N, K, C,
-                                         int(batched), _DTYPE_IDS[z.dtype], _stream())
-        _lib.check(rc, "mlgnn_diffpool_fwd")
+        _lib.call("mlgnn_diffpool_fwd", z, adj_k, s, S, x_out, a_out, partial, B, N, K, C, int(batched),
+                  _DTYPE_IDS[z.dtype], _lib.stream())
         tot = partial.sum(0)
         norm = torch.sqrt(tot[0])
         link = norm / adj.numel()
@@ -735,10 +700,8 @@ class _DiffPoolFused(torch.autograd.Function):
         need_adj = ctx.needs_input_grad[1]
         gadj = torch.empty((B, N, N), dtype=z.dtype, device=z.device) if need_adj else None
         gx, ga = gx.to(z.dtype).contiguous(), ga.to(z.dtype).contiguous()
-        rc = _lib.lib.mlgnn_diffpool_bwd(z.data_ptr(), adj.data_ptr(), S.data_ptr(), gx.data_ptr(), ga.data_ptr(),
-                                         coef.data_ptr(), gz.data_ptr(), gs.data_ptr(), _lib.ptr(gadj), B, N, K, C,
-                                         int(batched), _DTYPE_IDS[z.dtype], _stream())
-        _lib.check(rc, "mlgnn_diffpool_bwd")
+        _lib.call("mlgnn_diffpool_bwd", z, adj, S, gx, ga, coef, gz, gs, gadj, B, N, K, C, int(batched),
+                  _DTYPE_IDS[z.dtype], _lib.stream())
         if need_adj and not batched:
             gadj = gadj.float().sum(0, keepdim=True).to(adj.dtype).reshape(adj.shape)          # shared adjacency
         return gz, gadj, gs
@@ -765,11 +728,8 @@ class _DiffPoolLarge(torch.autograd.Function):
         stats = torch.empty(3, dtype=torch.float32, device=dev)
         scal = torch.empty(2, dtype=out_dtype, device=dev)
         ws = torch.empty(B * int(_lib.lib.mlgnn_diffpool_large_workspace_bytes(N, K, C)), dtype=torch.uint8, device=dev)
-        rc = _lib.lib.mlgnn_diffpool_large_fwd(
-            zb.data_ptr(), ab.data_ptr(), s.data_ptr(), _DTYPE_IDS[s.dtype], S.data_ptr(), x_out.data_ptr(), a_out.data_ptr(),
-            scal.data_ptr(), _DTYPE_IDS[out_dtype], stats.data_ptr(), ws.data_ptr(), ws.numel(), N, K, C, B, adj_batched,
-            _stream())
-        _lib.check(rc, "mlgnn_diffpool_large_fwd")
+        _lib.call("mlgnn_diffpool_large_fwd", zb, ab, s, _DTYPE_IDS[s.dtype], S, x_out, a_out, scal,
+                  _DTYPE_IDS[out_dtype], stats, ws, ws.numel(), N, K, C, B, adj_batched, _lib.stream())
         ctx.save_for_backward(zb, ab, s, S, ws, stats)
         ctx.cfg = (bool(adj_symmetric), z.dtype, adj_batched)
         ctx.adj_dtype, ctx.adj_shape = adj.dtype, adj.shape
@@ -793,11 +753,9 @@ class _DiffPoolLarge(torch.autograd.Function):
         gadj = torch.empty((B, N, N), dtype=s.dtype, device=dev) if ctx.needs_input_grad[1] else None
         wb = torch.empty(B * int(_lib.lib.mlgnn_diffpool_large_bwd_workspace_bytes(N, K, C, int(sym))), dtype=torch.uint8,
                          device=dev)
-        rc = _lib.lib.mlgnn_diffpool_large_bwd(
-            zb.data_ptr(), ab.data_ptr(), s.data_ptr(), _DTYPE_IDS[s.dtype], S.data_ptr(), ws.data_ptr(), gx.data_ptr(),
-            ga.data_ptr(), _DTYPE_IDS[gdt], g_link.data_ptr(), g_ent.data_ptr(), _DTYPE_IDS[g_link.dtype], stats.data_ptr(),
-            gz.data_ptr(), gs.data_ptr(), _lib.ptr(gadj), int(sym), wb.data_ptr(), wb.numel(), N, K, C, B, adj_batched, _stream())
-        _lib.check(rc, "mlgnn_diffpool_large_bwd")
+        _lib.call("mlgnn_diffpool_large_bwd", zb, ab, s, _DTYPE_IDS[s.dtype], S, ws, gx, ga, _DTYPE_IDS[gdt], g_link,
+                  g_ent, _DTYPE_IDS[g_link.dtype], stats, gz, gs, gadj, int(sym), wb, wb.numel(), N, K, C, B,
+                  adj_batched, _lib.stream())
         if gadj is not None:
             if not adj_batched and B > 1:
                 gadj = gadj.float().sum(0, keepdim=True)         # shared adjacency: the sum over the graphs that read it
@@ -824,10 +782,8 @@ class _DiffPoolLargeFP32(torch.autograd.Function):
         stats = torch.empty(3, dtype=torch.float32, device=dev)
         scal = torch.empty(2, dtype=torch.float32, device=dev)
         ws = torch.empty(B * int(_lib.lib.mlgnn_diffpool_large_f32_workspace_bytes(N, K, C)), dtype=torch.uint8, device=dev)
-        rc = _lib.lib.mlgnn_diffpool_large_f32_fwd(z.data_ptr(), adj.data_ptr(), s.data_ptr(), S.data_ptr(), x_out.data_ptr(),
-                                                   a_out.data_ptr(), scal.data_ptr(), stats.data_ptr(), ws.data_ptr(),
-                                                   ws.numel(), N, K, C, B, adj_batched, _stream())
-        _lib.check(rc, "mlgnn_diffpool_large_f32_fwd")
+        _lib.call("mlgnn_diffpool_large_f32_fwd", z, adj, s, S, x_out, a_out, scal, stats, ws, ws.numel(), N, K, C, B,
+                  adj_batched, _lib.stream())
         ctx.save_for_backward(adj, s, ws, stats)
         ctx.cfg = (bool(adj_symmetric), adj_batched, (B, N, K, C))
         ctx.adj_shape = adj.shape
@@ -846,11 +802,8 @@ class _DiffPoolLargeFP32(torch.autograd.Function):
         gadj = torch.empty((B, N, N), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
         wb = torch.empty(B * int(_lib.lib.mlgnn_diffpool_large_f32_bwd_workspace_bytes(N, K, C, int(sym))), dtype=torch.uint8,
                          device=dev)
-        rc = _lib.lib.mlgnn_diffpool_large_f32_bwd(adj.data_ptr(), s.data_ptr(), ws.data_ptr(), gx.data_ptr(), ga.data_ptr(),
-                                                   g_link.data_ptr(), g_ent.data_ptr(), stats.data_ptr(), gz.data_ptr(),
-                                                   gs.data_ptr(), _lib.ptr(gadj), int(sym), wb.data_ptr(), wb.numel(),
-                                                   N, K, C, B, adj_batched, _stream())
-        _lib.check(rc, "mlgnn_diffpool_large_f32_bwd")
+        _lib.call("mlgnn_diffpool_large_f32_bwd", adj, s, ws, gx, ga, g_link, g_ent, stats, gz, gs, gadj, int(sym), wb,
+                  wb.numel(), N, K, C, B, adj_batched, _lib.stream())
         if gadj is not None:
             if not adj_batched and B > 1:
                 gadj = gadj.sum(0, keepdim=True)                 # shared adjacency: the sum over the graphs that read it

@@ -14,7 +14,6 @@ import torch
 
 from . import _lib
 from .dense import _aligned
-from .ops import _stream
 from .tags import tag_row_max
 
 
@@ -43,13 +42,9 @@ class _GatAggregate(torch.autograd.Function):
         E = int(graph.col.numel())                  # (a SAGE-rewritten graph: the parked loops of its spare row included)
         a_src, a_dst = torch.empty((N, H), **f32), torch.empty((N, H), **f32)
         y, lse, y_max = torch.empty((N, d), **f32), torch.empty((N, H), **f32), torch.empty(N, **f32)
-        rc = _lib.lib.mlgnn_gat_scores(z.data_ptr(), att_s.data_ptr(), att_d.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(),
-                                       N, H, C, _stream())
-        _lib.check(rc, "mlgnn_gat_scores")
-        rc = _lib.lib.mlgnn_gat_aggregate_fwd(z.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(), _lib.ptr(b),
-                                              graph.rowptr.data_ptr(), _lib.ptr(graph.col), y.data_ptr(), lse.data_ptr(),
-                                              y_max.data_ptr(), N, E, H, C, float(negative_slope), float(act_slope), _stream())
-        _lib.check(rc, "mlgnn_gat_aggregate_fwd")
+        _lib.call("mlgnn_gat_scores", z, att_s, att_d, a_src, a_dst, N, H, C, _lib.stream())
+        _lib.call("mlgnn_gat_aggregate_fwd", z, a_src, a_dst, b, graph.rowptr, graph.col, y, lse, y_max, N, E, H, C,
+                  float(negative_slope), float(act_slope), _lib.stream())
         ctx.save_for_backward(z, att_s, att_d, b, y, a_src, a_dst, lse)
         ctx.graph = graph
         ctx.cfg = (H, C, E, float(negative_slope), float(act_slope), att_src.shape, att_dst.shape,
@@ -78,12 +73,8 @@ class _GatAggregate(torch.autograd.Function):
             gy = _aligned(gy)
             floats = int(_lib.lib.mlgnn_gat_bwd_workspace_floats(N, E, H, C))
             ws = torch.empty(max(floats, 1), **f32)
-            rc = _lib.lib.mlgnn_gat_aggregate_bwd(gy.data_ptr(), y.data_ptr(), z.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(),
-                                                  lse.data_ptr(), att_s.data_ptr(), att_d.data_ptr(), _lib.ptr(b),
-                                                  g.rowptr.data_ptr(), g.rowptr_t.data_ptr(), _lib.ptr(g.col_t),
-                                                  _lib.ptr(g.pos_t), _lib.ptr(gz), _lib.ptr(gs), _lib.ptr(gd), _lib.ptr(gb),
-                                                  ws.data_ptr(), floats, N, E, H, C, neg, act, _stream())
-            _lib.check(rc, "mlgnn_gat_aggregate_bwd")
+            _lib.call("mlgnn_gat_aggregate_bwd", gy, y, z, a_src, a_dst, lse, att_s, att_d, b, g.rowptr, g.rowptr_t,
+                      g.col_t, g.pos_t, gz, gs, gd, gb, ws, floats, N, E, H, C, neg, act, _lib.stream())
         return (gz, gs.reshape(shape_s) if need_s else None, gd.reshape(shape_d) if need_d else None,
                 gb.reshape(shape_b) if need_b else None, None, None, None, None)
 
@@ -93,8 +84,7 @@ def gat_aggregate(z, att_src, att_dst, bias, graph, heads, negative_slope=0.2, a
     ``bias`` [H * C] or None, ``graph`` a device :class:`mlgnn.CSRGraph` that already holds the self loops -> ``y``
     [N, H * C], tagged with its row maxima.  ``act_slope``: the activation after the bias as a leaky-relu slope
     (1.0: none, 0.0: relu)."""
-    if not (torch.is_tensor(z) and z.is_cuda):
-        raise RuntimeError("mlgnn.gat has no CPU path (the kernels are HIP only); move the tensors to the GPU")
+    _lib.require_gpu(z, "mlgnn.gat")
     H = int(heads)
     if not gat_supported(z, H):
         raise ValueError("gat_aggregate: unsupported input %s %s with heads=%d (fp32 [N, H*C], 1 <= H <= 16, H*C <= 256, "

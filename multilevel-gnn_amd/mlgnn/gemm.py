@@ -51,13 +51,10 @@ def gemm_bf16_nt(segments, splits=1, out_dtype=torch.bfloat16, want_c=True, want
             ct = out["ct"] = torch.empty((N, M), dtype=torch.bfloat16, device=dev)
         if dot is not None:
             partial = torch.empty(int(_lib.lib.mlgnn_gemm_bf16_nt_workgroups(M, N, 1)), dtype=torch.float32, device=dev)
-    rc = _lib.lib.mlgnn_gemm_bf16_nt(
-        pa, pb, la, lb, ks, n, M, N, splits, _lib.ptr(slab if splits > 1 else None),
-        _lib.ptr(c), N, _dtype_id(c) if c is not None else 1, _lib.ptr(ct), M,
-        _lib.ptr(aux), aux.stride(0) if aux is not None else 0, _dtype_id(aux) if aux is not None else 0, float(alpha),
-        _lib.ptr(dot), dot.stride(0) if dot is not None else 0, _lib.ptr(partial),
-        torch.cuda.current_stream().cuda_stream)
-    _lib.check(rc, "mlgnn_gemm_bf16_nt")
+    _lib.call("mlgnn_gemm_bf16_nt", pa, pb, la, lb, ks, n, M, N, splits, slab if splits > 1 else None, c, N,
+              _dtype_id(c) if c is not None else 1, ct, M, aux, aux.stride(0) if aux is not None else 0,
+              _dtype_id(aux) if aux is not None else 0, float(alpha), dot, dot.stride(0) if dot is not None else 0,
+              partial, _lib.stream())
     if partial is not None:
         out["dot"] = partial.sum()
     return out

@@ -115,12 +115,9 @@ class CSRGraph:
         g.rowptr, g.rowptr_t = torch.empty(n * B + 1, **i32), torch.empty(n * B + 1, **i32)
         g.col, g.eid = torch.empty(e * B, **i32), torch.empty(e * B, **i32)
         g.col_t, g.pos_t, g.eid_t = torch.empty(e * B, **i32), torch.empty(e * B, **i32), torch.empty(e * B, **i32)
-        rc = _lib.lib.mlgnn_csr_replicate(single.rowptr.data_ptr(), _lib.ptr(single.col), _lib.ptr(single.eid),
-                                          single.rowptr_t.data_ptr(), _lib.ptr(single.col_t), _lib.ptr(single.pos_t),
-                                          _lib.ptr(single.eid_t), g.rowptr.data_ptr(), _lib.ptr(g.col), _lib.ptr(g.eid),
-                                          g.rowptr_t.data_ptr(), _lib.ptr(g.col_t), _lib.ptr(g.pos_t), _lib.ptr(g.eid_t),
-                                          n, e, B, torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "mlgnn_csr_replicate")
+        _lib.call("mlgnn_csr_replicate", single.rowptr, single.col, single.eid, single.rowptr_t, single.col_t,
+                  single.pos_t, single.eid_t, g.rowptr, g.col, g.eid, g.rowptr_t, g.col_t, g.pos_t, g.eid_t, n, e, B,
+                  _lib.stream())
         g._deg, g._scalar_cache, g._table_cache, g._hub = None, None, None, {}
         ev = torch.cuda.Event()
         ev.record()
@@ -155,9 +152,7 @@ class CSRGraph:
             i32 = dict(dtype=torch.int32, device=self.device)
             vrows, hubs, counts = torch.empty((cap_rows, 3), **i32), torch.empty((cap_rows, 3), **i32), torch.empty(2, **i32)
             rowptr = self.rowptr if direction == "dst" else self.rowptr_t
-            rc = _lib.lib.mlgnn_hub_rows(rowptr.data_ptr(), self.num_nodes, cap, cap_rows, vrows.data_ptr(),
-                                         hubs.data_ptr(), counts.data_ptr(), torch.cuda.current_stream().cuda_stream)
-            _lib.check(rc, "mlgnn_hub_rows")
+            _lib.call("mlgnn_hub_rows", rowptr, self.num_nodes, cap, cap_rows, vrows, hubs, counts, _lib.stream())
             # the counts also travel to pinned host memory, asynchronously: once that copy is known to have finished
             # (event.query(), never a wait) a graph without long rows skips the two empty launches per aggregation
             host = torch.empty(2, dtype=torch.int32, pin_memory=True)
@@ -210,11 +205,8 @@ class CSRGraph:
         nbytes = int(_lib.lib.mlgnn_coo_to_csr_workspace_bytes(N, E))
         ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
         self._bad_ids = torch.empty(1, **i32)               # cleared by the build itself
-        rc = _lib.lib.mlgnn_coo_to_csr(ei.data_ptr(), E, N, self.rowptr.data_ptr(), _lib.ptr(self.col),
-                                       _lib.ptr(self.eid), self.rowptr_t.data_ptr(), _lib.ptr(self.col_t),
-                                       _lib.ptr(self.pos_t), _lib.ptr(self.eid_t), self._bad_ids.data_ptr(),
-                                       ws.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "mlgnn_coo_to_csr")
+        _lib.call("mlgnn_coo_to_csr", ei, E, N, self.rowptr, self.col, self.eid, self.rowptr_t, self.col_t, self.pos_t,
+                  self.eid_t, self._bad_ids, ws, nbytes, _lib.stream())
 
     def validate(self):
         """Raise if the edge list named a node outside ``[0, num_nodes)`` (the device build clamps such
@@ -319,11 +311,8 @@ class CSRGraph:
                     rows = rows.contiguous()
                 by_dst = torch.empty((self.num_edges, width), dtype=torch.float32, device=a.device)
                 by_src = torch.empty_like(by_dst)
-                rc = _lib.lib.mlgnn_edge_table_to_csr(rows.data_ptr(), rows.stride(0), rows.shape[1], width,
-                                                      self.eid.data_ptr(), self.eid_t.data_ptr(), by_dst.data_ptr(),
-                                                      by_src.data_ptr(), self.num_edges,
-                                                      torch.cuda.current_stream().cuda_stream)
-                _lib.check(rc, "mlgnn_edge_table_to_csr")
+                _lib.call("mlgnn_edge_table_to_csr", rows, rows.stride(0), rows.shape[1], width, self.eid, self.eid_t,
+                          by_dst, by_src, self.num_edges, _lib.stream())
                 hit = (by_dst, by_src)
             else:
                 rows = a.to(torch.float32)
@@ -383,9 +372,7 @@ def _sage_graph_device(edge_index, edge_attr, num_nodes):
         stride = attr.stride(0) if E > 0 else 1
     out = torch.empty((2, E + N), dtype=torch.int64, device=ei.device)
     weight = torch.empty(E + N, dtype=torch.float32, device=ei.device) if attr is not None else None
-    rc = _lib.lib.mlgnn_sage_rewrite(ei.data_ptr(), _lib.ptr(attr), stride, E, N, out.data_ptr(), _lib.ptr(weight),
-                                     torch.cuda.current_stream().cuda_stream)
-    _lib.check(rc, "mlgnn_sage_rewrite")
+    _lib.call("mlgnn_sage_rewrite", ei, attr, stride, E, N, out, weight, _lib.stream())
     graph = CSRGraph(out, N + 1)
     graph.hub_cap = SAGE_HUB_CAP
     graph.num_nodes = N                      # rowptr / rowptr_t carry one more (unused) row: the parked self loops

@@ -11,18 +11,12 @@ import os
 import torch
 
 from . import _lib
-from .ops import _stream
 
 # MLGNN_VAE_LATENT_FUSED=0: VAE.encoder always takes the torch lines (same-box A/B runs)
 ENABLED = os.environ.get("MLGNN_VAE_LATENT_FUSED", "1") != "0"
 
 # how often each path was taken (development / tests: which path a model ran on)
-LATENT_STATS = {"hip": 0, "torch": 0}
-
-if os.environ.get("MLGNN_PRINT_STATS", "0") == "1":
-    import atexit
-    import sys
-    atexit.register(lambda: print("mlgnn stats: vae_latent %r" % (LATENT_STATS,), file=sys.stderr))
+LATENT_STATS = _lib.stats("vae_latent", hip=0, torch=0)
 
 EPS = 1e-7          # q_z's scale is sigma + EPS; the KL sum uses the same
 
@@ -36,10 +30,6 @@ def vae_latent_supported(x):
     return bool(_lib.lib.mlgnn_vae_latent_supported(B, P, H))
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 class _VaeLatent(torch.autograd.Function):
     """``x`` [B, P, H], ``w_mu``, ``w_ls`` [H, H], ``b_mu``, ``b_ls`` [H], all fp32 and contiguous ->
     ``(mu, sigma [B, P, H], std_sum, corr_sum, kld_sum [P])``."""
@@ -49,10 +39,7 @@ class _VaeLatent(torch.autograd.Function):
         B, P, H = x.shape
         mu, sigma = torch.empty_like(x), torch.empty_like(x)
         sums = [torch.empty((P,), dtype=torch.float32, device=x.device) for _ in range(3)]
-        rc = _lib.lib.mlgnn_vae_latent_fwd(x.data_ptr(), w_mu.data_ptr(), b_mu.data_ptr(), w_ls.data_ptr(), b_ls.data_ptr(),
-                                           mu.data_ptr(), sigma.data_ptr(), *[t.data_ptr() for t in sums], B, P, H,
-                                           _stream())
-        _lib.check(rc, "mlgnn_vae_latent_fwd")
+        _lib.call("mlgnn_vae_latent_fwd", x, w_mu, b_mu, w_ls, b_ls, mu, sigma, *sums, B, P, H, _lib.stream())
         LATENT_STATS["hip"] += 1
         if any(ctx.needs_input_grad):
             ctx.save_for_backward(x, w_mu, w_ls, mu, sigma)
@@ -74,10 +61,8 @@ class _VaeLatent(torch.autograd.Function):
         ws = None
         if any(need[1:]):
             ws = torch.empty((P * (2 * H * H + 2 * H),), dtype=torch.float32, device=x.device)
-        rc = _lib.lib.mlgnn_vae_latent_bwd(x.data_ptr(), w_mu.data_ptr(), w_ls.data_ptr(), mu.data_ptr(), sigma.data_ptr(),
-                                           *[_ptr(g) for g in cots], _ptr(grad_x), *[_ptr(g) for g in grads],
-                                           _ptr(ws), 0 if ws is None else ws.numel(), B, P, H, _stream())
-        _lib.check(rc, "mlgnn_vae_latent_bwd")
+        _lib.call("mlgnn_vae_latent_bwd", x, w_mu, w_ls, mu, sigma, *cots, grad_x, *grads, ws,
+                  0 if ws is None else ws.numel(), B, P, H, _lib.stream())
         return (grad_x, *grads)
 
 
@@ -88,8 +73,7 @@ def vae_latent(x, w_mu, b_mu, w_ls, b_ls):
     the sum over ``b, h`` of ``kl_divergence(Normal(mu, sigma + 1e-7), Normal(0, 1))``.  So
     ``loss_std = -std_sum.sum() / (P H)``, ``loss_corr = corr_sum.sum() / (P H H)`` and the KL term is
     ``kld_sum.sum() / (B P)``.  The caller checks :func:`vae_latent_supported` first."""
-    if not (torch.is_tensor(x) and x.is_cuda):
-        raise RuntimeError("mlgnn.vae_latent has no CPU path (the kernels are HIP only); move the tensors to the GPU")
+    _lib.require_gpu(x, "mlgnn.vae_latent")
     if not vae_latent_supported(x):
         raise ValueError("vae_latent: unsupported input %s %s (strides %s) (fp32, contiguous [B, P, H], 2 <= B <= 256, "
                          "1 <= H <= 128, B * H <= 8192, < 4 GiB)" % (tuple(x.shape), x.dtype, x.stride()))

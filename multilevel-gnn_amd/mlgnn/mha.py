@@ -16,7 +16,6 @@ import torch
 
 from . import _lib
 from .dense import _aligned
-from .ops import _stream
 
 
 def mha_supported(qkv, batch, heads):
@@ -38,9 +37,7 @@ class _MhaAttention(torch.autograd.Function):
         P, D = qkv.shape[0] // B, qkv.shape[1] // (3 * H)
         f32 = dict(dtype=torch.float32, device=qkv.device)
         out, lse = torch.empty((B * P, H * D), **f32), torch.empty((B, H, P), **f32)
-        rc = _lib.lib.mlgnn_mha_fwd(qkv.data_ptr(), _lib.ptr(keep), float(keep_scale), out.data_ptr(), lse.data_ptr(),
-                                    B, P, H, D, _stream())
-        _lib.check(rc, "mlgnn_mha_fwd")
+        _lib.call("mlgnn_mha_fwd", qkv, keep, float(keep_scale), out, lse, B, P, H, D, _lib.stream())
         ctx.save_for_backward(qkv, out, lse)
         ctx.keep = keep
         ctx.cfg = (B, P, H, D, float(keep_scale))
@@ -56,9 +53,7 @@ class _MhaAttention(torch.autograd.Function):
         gqkv = torch.empty_like(qkv)
         floats = int(_lib.lib.mlgnn_mha_bwd_workspace_floats(B, P, H, D))
         ws = torch.empty(floats, dtype=torch.float32, device=qkv.device) if floats > 0 else None
-        rc = _lib.lib.mlgnn_mha_bwd(go.data_ptr(), qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), _lib.ptr(ctx.keep),
-                                    keep_scale, gqkv.data_ptr(), _lib.ptr(ws), floats, B, P, H, D, _stream())
-        _lib.check(rc, "mlgnn_mha_bwd")
+        _lib.call("mlgnn_mha_bwd", go, qkv, out, lse, ctx.keep, keep_scale, gqkv, ws, floats, B, P, H, D, _lib.stream())
         return gqkv, None, None, None, None
 
 
@@ -66,8 +61,7 @@ def mha_attention(qkv, batch, heads, keep=None, keep_scale=1.0):
     """``qkv`` [B * P, 3 * H * D] (the in-projection's output), ``batch`` = B, ``heads`` = H, ``keep`` a contiguous uint8
     tensor [B, H, P, P] of dropout keep flags or None, ``keep_scale`` what a kept probability is multiplied by
     (``1 / (1 - p)``) -> ``out`` [B * P, H * D]."""
-    if not (torch.is_tensor(qkv) and qkv.is_cuda):
-        raise RuntimeError("mlgnn.mha has no CPU path (the kernels are HIP only); move the tensors to the GPU")
+    _lib.require_gpu(qkv, "mlgnn.mha")
     B, H = int(batch), int(heads)
     if not mha_supported(qkv, B, H):
         raise ValueError("mha_attention: unsupported input %s %s with batch=%d, heads=%d (fp32 [B*P, 3*H*D], 1 <= H <= 16, "

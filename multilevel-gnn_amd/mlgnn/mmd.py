@@ -11,18 +11,12 @@ import os
 import torch
 
 from . import _lib
-from .ops import _stream
 
 # MLGNN_MMD_FUSED=0: VAE.vae_loss always takes the per-pathway loop (same-box A/B runs)
 ENABLED = os.environ.get("MLGNN_MMD_FUSED", "1") != "0"
 
 # how often each path was taken (development / tests: which path a model ran on)
-MMD_STATS = {"hip": 0, "torch": 0}
-
-if os.environ.get("MLGNN_PRINT_STATS", "0") == "1":
-    import atexit
-    import sys
-    atexit.register(lambda: print("mlgnn stats: mmd %r" % (MMD_STATS,), file=sys.stderr))
+MMD_STATS = _lib.stats("mmd", hip=0, torch=0)
 
 KINDS = {"imq": 0, "rbf": 1}
 EPS = 1e-7
@@ -45,9 +39,7 @@ class _Mmd(torch.autograd.Function):
         B, P, H = z.shape
         terms = torch.empty((P, 3), dtype=torch.float32, device=z.device)
         mmd = torch.empty((P,), dtype=torch.float32, device=z.device)
-        rc = _lib.lib.mlgnn_mmd_fwd(z.data_ptr(), prior.data_ptr(), terms.data_ptr(), mmd.data_ptr(), kind, c_eps, c,
-                                    B, P, H, _stream())
-        _lib.check(rc, "mlgnn_mmd_fwd")
+        _lib.call("mlgnn_mmd_fwd", z, prior, terms, mmd, kind, c_eps, c, B, P, H, _lib.stream())
         MMD_STATS["hip"] += 1
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(z, prior)
@@ -64,9 +56,7 @@ class _Mmd(torch.autograd.Function):
         B, P, H = z.shape
         grad_mmd = grad_mmd.to(torch.float32).contiguous()
         grad_z = torch.empty_like(z)
-        rc = _lib.lib.mlgnn_mmd_bwd(z.data_ptr(), prior.data_ptr(), grad_mmd.data_ptr(), grad_z.data_ptr(), kind, c_eps,
-                                    c, B, P, H, _stream())
-        _lib.check(rc, "mlgnn_mmd_bwd")
+        _lib.call("mlgnn_mmd_bwd", z, prior, grad_mmd, grad_z, kind, c_eps, c, B, P, H, _lib.stream())
         return grad_z, None, None, None, None
 
 
@@ -75,8 +65,7 @@ def mmd_per_pathway(z, prior, kind="imq", z_var=2.0, return_terms=False):
     every pathway: ``[P]``, and with ``return_terms`` also ``terms [P, 3] = (T_pp, T_zz, T_pz)``.  ``kind``: ``'imq'``
     (off-diagonal sums of ``c / (eps + c + |a - b|^2)``) or ``'rbf'`` (means over all pairs of
     ``exp(-(|a - b|^2 / H) / c)``), ``c = 2 H z_var``.  The caller checks :func:`mmd_supported` first."""
-    if not (torch.is_tensor(z) and z.is_cuda):
-        raise RuntimeError("mlgnn.mmd_per_pathway has no CPU path (the kernels are HIP only); move the tensors to the GPU")
+    _lib.require_gpu(z, "mlgnn.mmd_per_pathway")
     if kind not in KINDS:
         raise ValueError("Undefined kernel type.")
     if not mmd_supported(z):

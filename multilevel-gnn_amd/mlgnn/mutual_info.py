@@ -14,7 +14,6 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ops import _stream
 
 # MLGNN_MI_FUSED=0: generate_mutual_mask of the models always calls scikit-learn (same-box A/B runs).  On by default: end
 # to end the op beats the scikit-learn call by far more than that call's spread at the gbm, lgg and kirc shapes
@@ -23,12 +22,7 @@ DEFAULT_ENABLED = True
 ENABLED = os.environ.get("MLGNN_MI_FUSED", "1" if DEFAULT_ENABLED else "0") != "0"
 
 # how often model_mutual_info took each path (development / tests: which path a mask was computed on)
-MI_STATS = {"hip": 0, "sklearn": 0}
-
-if os.environ.get("MLGNN_PRINT_STATS", "0") == "1":
-    import atexit
-    import sys
-    atexit.register(lambda: print("mlgnn stats: mutual_info %r" % (MI_STATS,), file=sys.stderr))
+MI_STATS = _lib.stats("mutual_info", hip=0, sklearn=0)
 
 MAX_SAMPLES = 2048
 
@@ -101,9 +95,7 @@ def mutual_info_cd(prepared, y, n_neighbors=3, return_counts=False):
     psi_d = torch.from_numpy(psi).to(dev)
     mi = torch.empty(n_features, dtype=torch.float64, device=dev)
     counts = torch.empty((n_features, n), dtype=torch.int32, device=dev) if return_counts else None
-    rc = _lib.lib.mlgnn_mutual_info_cd(xt.data_ptr(), labels.data_ptr(), psi_d.data_ptr(), base, mi.data_ptr(),
-                                       _lib.ptr(counts), n, n_features, k, len(c), _stream())
-    _lib.check(rc, "mlgnn_mutual_info_cd")
+    _lib.call("mlgnn_mutual_info_cd", xt, labels, psi_d, base, mi, counts, n, n_features, k, len(c), _lib.stream())
     out = mi.cpu().numpy()
     return (out, counts.cpu().numpy(), keep) if return_counts else out
 

@@ -5,7 +5,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .ops import _DTYPE_IDS, _stream
+from .ops import _DTYPE_IDS
 from .tags import f32_cached, tag_row_max
 
 
@@ -43,11 +43,8 @@ class _LayerNormAct(torch.autograd.Function):
         ctx.row_max = torch.empty(rows, dtype=torch.float32, device=x.device) if x.dtype == torch.float32 else None
         if keep is not None and (keep.shape != x.shape or keep.dtype != torch.uint8 or not keep.is_contiguous()):
             raise ValueError("dropout keep mask must be a contiguous uint8 tensor of the input's shape")
-        rc = _lib.lib.mlgnn_layernorm_act_fwd(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), out.data_ptr(),
-                                              mean.data_ptr(), rstd.data_ptr(), _lib.ptr(ctx.row_max), _lib.ptr(keep),
-                                              float(keep_scale), rows, d,
-                                              float(eps), int(relu), _DTYPE_IDS[x.dtype], _stream())
-        _lib.check(rc, "mlgnn_layernorm_act_fwd")
+        _lib.call("mlgnn_layernorm_act_fwd", x, weight, bias, out, mean, rstd, ctx.row_max, keep, float(keep_scale),
+                  rows, d, float(eps), int(relu), _DTYPE_IDS[x.dtype], _lib.stream())
         ctx.relu = bool(relu)
         ctx.keep, ctx.keep_scale = keep, float(keep_scale)
         ctx.save_for_backward(x, weight, bias, mean, rstd)
@@ -72,10 +69,8 @@ def _ln_bwd(go, x, weight, bias, mean, rstd, relu, extra=None, keep=None, keep_s
     n = int(_lib.lib.mlgnn_layernorm_bwd_workspace_floats(rows, d, dt))
     ws = torch.empty(n, dtype=torch.float32, device=x.device)
     row_max = torch.empty(rows, dtype=torch.float32, device=x.device) if x.dtype == torch.float32 else None
-    rc = _lib.lib.mlgnn_layernorm_act_bwd(go.data_ptr(), x.data_ptr(), weight.data_ptr(), bias.data_ptr(), _lib.ptr(mean),
-                                          rstd.data_ptr(), _lib.ptr(extra), gx.data_ptr(), _lib.ptr(row_max), ggb.data_ptr(),
-                                          ws.data_ptr(), n, _lib.ptr(keep), keep_scale, rows, d, int(relu), dt, _stream())
-    _lib.check(rc, "mlgnn_layernorm_act_bwd")
+    _lib.call("mlgnn_layernorm_act_bwd", go, x, weight, bias, mean, rstd, extra, gx, row_max, ggb, ws, n, keep,
+              keep_scale, rows, d, int(relu), dt, _lib.stream())
     return gx, ggb, row_max
 
 
@@ -157,9 +152,7 @@ class _MsgNormAdd(torch.autograd.Function):
         rows, d = x.shape
         h = torch.empty_like(x)
         scale32 = scale if scale.dtype == torch.float32 else scale.float()       # the learnable scalar stays fp32
-        rc = _lib.lib.mlgnn_msgnorm_add_fwd(x.data_ptr(), m.data_ptr(), scale32.data_ptr(), h.data_ptr(), rows, d,
-                                            _DTYPE_IDS[x.dtype], _stream())
-        _lib.check(rc, "mlgnn_msgnorm_add_fwd")
+        _lib.call("mlgnn_msgnorm_add_fwd", x, m, scale32, h, rows, d, _DTYPE_IDS[x.dtype], _lib.stream())
         ctx.save_for_backward(x, m, scale32)
         ctx.scale_dtype = scale.dtype
         return h
@@ -173,10 +166,8 @@ class _MsgNormAdd(torch.autograd.Function):
         gs = torch.empty(1, dtype=torch.float32, device=x.device)
         n = int(_lib.lib.mlgnn_msgnorm_bwd_workspace_floats(rows, d))
         ws = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
-        rc = _lib.lib.mlgnn_msgnorm_add_bwd(gh.data_ptr(), x.data_ptr(), m.data_ptr(), scale.data_ptr(),
-                                            gx.data_ptr(), gm.data_ptr(), gs.data_ptr(), ws.data_ptr(), n, rows, d,
-                                            _DTYPE_IDS[x.dtype], _stream())
-        _lib.check(rc, "mlgnn_msgnorm_add_bwd")
+        _lib.call("mlgnn_msgnorm_add_bwd", gh, x, m, scale, gx, gm, gs, ws, n, rows, d, _DTYPE_IDS[x.dtype],
+                  _lib.stream())
         return gx, gm, (gs.to(ctx.scale_dtype) if ctx.needs_input_grad[2] else None)
 
 

@@ -27,10 +27,6 @@ AGGR_IDS = {"add": AGGR_SUM, "sum": AGGR_SUM, "mean": AGGR_MEAN, "max": AGGR_MAX
             "power": AGGR_POWER, "power_sum": AGGR_POWER}
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 class KernelTimer:
     """HIP-event stopwatch around individual C-ABI launches (events are recorded on the stream the
     kernel is launched on -- torch's current stream).  ``bench.py`` installs one to report the
@@ -125,14 +121,8 @@ def _dev_act(t, what, like=None):
 # 0.21 ms LayerNorm-backward launch it removes -- that kernel is bound by instruction issue and by the L2 hit rate of
 # its gather, and the epilogue adds to both; the step moved by -0.1 ... +0.1 ms.  MLGNN_LN_FOLD=1 turns it on.
 LN_FOLD = os.environ.get("MLGNN_LN_FOLD", "0") == "1"
-LN_FOLD_STATS = {"folded": 0, "separate": 0}
+LN_FOLD_STATS = _lib.stats("ln_fold", folded=0, separate=0)
 SHIFT_STATS = {"given": 0, "computed": 0}     # softmax backwards whose rescaled cotangent came from the producer / a pre-pass
-
-
-if os.environ.get("MLGNN_PRINT_STATS", "0") == "1":          # development: which paths a run took
-    import atexit
-    import sys
-    atexit.register(lambda: print("mlgnn stats: ln_fold %r" % (LN_FOLD_STATS,), file=sys.stderr))
 
 
 class LowRankEdge:
@@ -201,9 +191,7 @@ def _sum_rows_by_table_row(ge, order, rowptr, T):
     gathers and sums its cotangent rows in a fixed order (``csrc/embedding.hip``)."""
     d = ge.shape[1]
     out = torch.empty((T, d), dtype=torch.float32, device=ge.device)
-    rc = _lib.lib.mlgnn_embedding_bwd(ge.data_ptr(), order.data_ptr(), rowptr.data_ptr(), out.data_ptr(), T, d,
-                                      DTYPE_F32, _stream())
-    _lib.check(rc, "mlgnn_embedding_bwd")
+    _lib.call("mlgnn_embedding_bwd", ge, order, rowptr, out, T, d, DTYPE_F32, _lib.stream())
     return out
 
 
@@ -432,12 +420,9 @@ def _aggregate_fwd(x, graph, out, msg, aggr_id, hub, ew_pair=None, eu=None, ev=N
     ``ew_pair``: per-edge scalars in (by-destination, by-source) order -- the forward reads the first, the backward the second."""
     N, d = x.shape
     ew = ew_pair[0] if ew_pair is not None else None
-    rc = _lib.lib.mlgnn_csr_aggregate_fwd(
-        x.data_ptr(), graph.rowptr.data_ptr(), graph.col.data_ptr(), _lib.ptr(ew), _lib.ptr(eu), _lib.ptr(ev),
-        _lib.ptr(efull), _lib.ptr(eid), out.data_ptr(), _lib.ptr(aux), _lib.ptr(aux2), _lib.ptr(argmax),
-        _lib.ptr(rowmax), N, d, _DTYPE_IDS[x.dtype], msg, edge_mode, rank, aggr_id, float(t), float(p),
-        _lib.ptr(t_dev), _lib.ptr(p_dev), float(eps), int(add_root), hub, _stream())
-    _lib.check(rc, "mlgnn_csr_aggregate_fwd")
+    _lib.call("mlgnn_csr_aggregate_fwd", x, graph.rowptr, graph.col, ew, eu, ev, efull, eid, out, aux, aux2, argmax,
+              rowmax, N, d, _DTYPE_IDS[x.dtype], msg, edge_mode, rank, aggr_id, float(t), float(p), t_dev, p_dev,
+              float(eps), int(add_root), hub, _lib.stream())
 
 
 def _aggregate_bwd(go, graph, gx, msg, aggr_id, hub, x=None, out=None, aux=None, argmax=None, ew_pair=None, eu=None, ev=None,
@@ -449,17 +434,15 @@ def _aggregate_bwd(go, graph, gx, msg, aggr_id, hub, x=None, out=None, aux=None,
     no hub table): ``mlgnn_csr_aggregate_bwd_ln`` -- the LayerNorm backward in the row epilogue, the struct behind the arguments."""
     N, d = go.shape
     ew_t = ew_pair[1] if ew_pair is not None else None
-    args = (go.data_ptr(), _lib.ptr(x), _lib.ptr(out), _lib.ptr(aux), _lib.ptr(argmax),
-            graph.rowptr_t.data_ptr(), graph.col_t.data_ptr(), graph.pos_t.data_ptr(), graph.rowptr.data_ptr(),
-            _lib.ptr(ew_t), _lib.ptr(eu), _lib.ptr(ev), _lib.ptr(efull), _lib.ptr(eid_t), _lib.ptr(geid_t),
-            gx.data_ptr(), _lib.ptr(ge), _lib.ptr(guv), _lib.ptr(ws), ws_n,
+    args = (go, x, out, aux, argmax, graph.rowptr_t, graph.col_t, graph.pos_t, graph.rowptr,
+            ew_t, eu, ev, efull, eid_t, geid_t, gx, ge, guv, ws, ws_n,
             N, d, _DTYPE_IDS[go.dtype], msg, edge_mode, rank, aggr_id, int(learn_t), t, p,
-            _lib.ptr(t_dev), _lib.ptr(p_dev), eps, int(add_root), ge_accumulate, hub,
-            _lib.ptr(shifted[0]) if shifted else None, _lib.ptr(shifted[1]) if shifted else None)
+            t_dev, p_dev, eps, int(add_root), ge_accumulate, hub,
+            shifted[0] if shifted else None, shifted[1] if shifted else None)
     if ln is None:
-        _lib.check(_lib.lib.mlgnn_csr_aggregate_bwd(*args, _stream()), "mlgnn_csr_aggregate_bwd")
+        _lib.call("mlgnn_csr_aggregate_bwd", *args, _lib.stream())
     else:
-        _lib.check(_lib.lib.mlgnn_csr_aggregate_bwd_ln(*args, ctypes.byref(ln), _stream()), "mlgnn_csr_aggregate_bwd_ln")
+        _lib.call("mlgnn_csr_aggregate_bwd_ln", *args, ctypes.byref(ln), _lib.stream())
 
 
 class _GenAggregate(torch.autograd.Function):
@@ -552,10 +535,9 @@ class _GenAggregate(torch.autograd.Function):
             gp = torch.empty(1, dtype=torch.float32, device=x.device) if learn_p else None
             pw_n = int(_lib.lib.mlgnn_power_bwd_prologue_workspace_floats())
             pw_ws = torch.empty(pw_n, dtype=torch.float32, device=x.device) if learn_p else None
-            rc = _lib.lib.mlgnn_power_bwd_prologue(go.data_ptr(), aux.data_ptr(), g.rowptr.data_ptr(), _lib.ptr(out if learn_p else None),
-                                                   _lib.ptr(aux2 if learn_p else None), float(p), _lib.ptr(p_dev), go_k.data_ptr(),
-                                                   _lib.ptr(gp), _lib.ptr(pw_ws), pw_n, N, d, _DTYPE_IDS[x.dtype], _stream())
-            _lib.check(rc, "mlgnn_power_bwd_prologue")
+            _lib.call("mlgnn_power_bwd_prologue", go, aux, g.rowptr, out if learn_p else None,
+                      aux2 if learn_p else None, float(p), p_dev, go_k, gp, pw_ws, pw_n, N, d, _DTYPE_IDS[x.dtype],
+                      _lib.stream())
             if learn_p:
                 grad_p = gp.to(p_dev.dtype)
         if aggr_id == AGGR_SOFTMAX and learn_t:
@@ -622,9 +604,7 @@ def _streamed_table_grad(go_k, argmax, g, te, sink):
     rows_dst = te.rows_for(g)[0]
     mt_n = int(_lib.lib.mlgnn_max_table_grad_workspace_floats(N, d, T))
     mt_ws = torch.empty(mt_n, dtype=torch.float32, device=go_k.device)
-    rc = _lib.lib.mlgnn_max_table_grad(go_k.data_ptr(), argmax.data_ptr(), rows_dst.data_ptr(), total.data_ptr(),
-                                       mt_ws.data_ptr(), mt_n, N, d, T, accumulate, _stream())
-    _lib.check(rc, "mlgnn_max_table_grad")
+    _lib.call("mlgnn_max_table_grad", go_k, argmax, rows_dst, total, mt_ws, mt_n, N, d, T, accumulate, _lib.stream())
     TABLE_DEST_STATS["streamed"] += 1
 
 
@@ -634,12 +614,9 @@ def _max_winners_backward(go_k, argmax, g, gx, add_root, te, sink):
     (N, d), dev = go_k.shape, go_k.device
     recs = torch.empty((int(_lib.lib.mlgnn_max_sparse_records(N, d, g.num_edges)), 2), dtype=torch.int32, device=dev)
     meta = torch.empty((g.num_edges, 2), dtype=torch.int32, device=dev)
-    rc = _lib.lib.mlgnn_max_winners(go_k.data_ptr(), argmax.data_ptr(), g.rowptr.data_ptr(), recs.data_ptr(),
-                                    meta.data_ptr(), N, d, _stream())
-    _lib.check(rc, "mlgnn_max_winners")
-    rc = _lib.lib.mlgnn_max_sparse_bwd(recs.data_ptr(), meta.data_ptr(), g.rowptr_t.data_ptr(), g.pos_t.data_ptr(),
-                                       go_k.data_ptr() if add_root else None, gx.data_ptr(), N, d, _stream())
-    _lib.check(rc, "mlgnn_max_sparse_bwd")
+    _lib.call("mlgnn_max_winners", go_k, argmax, g.rowptr, recs, meta, N, d, _lib.stream())
+    _lib.call("mlgnn_max_sparse_bwd", recs, meta, g.rowptr_t, g.pos_t, go_k if add_root else None, gx, N, d,
+              _lib.stream())
     SPARSE_MAX_STATS["calls"] += 1
     if te is None or sink is None:
         return
@@ -649,9 +626,7 @@ def _max_winners_backward(go_k, argmax, g, gx, add_root, te, sink):
     else:
         total, accumulate = sink.table_total(T, d, dev)
         pos_s, _, rp_s, _ = te.winners_by_type(g)
-        rc = _lib.lib.mlgnn_max_sparse_table_grad(recs.data_ptr(), meta.data_ptr(), pos_s.data_ptr(), rp_s.data_ptr(),
-                                                  total.data_ptr(), N, d, T, accumulate, _stream())
-        _lib.check(rc, "mlgnn_max_sparse_table_grad")
+        _lib.call("mlgnn_max_sparse_table_grad", recs, meta, pos_s, rp_s, total, N, d, T, accumulate, _lib.stream())
         SPARSE_MAX_STATS["table"] += 1
     TABLE_DEST_STATS["calls"] += 1
 
@@ -662,7 +637,7 @@ def _fixed_point_begin(go_k, te, sink):
     nbytes = int(_lib.lib.mlgnn_table_grad_bytes(te.table_rows, d))
     if sink.fix is None or sink.fix.numel() != nbytes:
         sink.fix = torch.zeros(nbytes, dtype=torch.uint8, device=go_k.device)
-    _lib.check(_lib.lib.mlgnn_table_grad_begin(go_k.data_ptr(), N, d, sink.fix.data_ptr(), _stream()), "mlgnn_table_grad_begin")
+    _lib.call("mlgnn_table_grad_begin", go_k, N, d, sink.fix, _lib.stream())
     return sink.fix
 
 
@@ -674,10 +649,8 @@ def _by_type_table_grad(go_k, argmax, g, te, sink, ws, rank):
     pos_s, dst_s, rp_s, rel_s = te.winners_by_type(g)
     off = int(_lib.lib.mlgnn_csr_aggregate_bwd_slots_offset_floats(N, d, rank))
     slots = ws.data_ptr() + 4 * off if (ws is not None and off >= 0 and TABLE_SLOTS) else None
-    rc = _lib.lib.mlgnn_max_table_grad_by_type(go_k.data_ptr(), argmax.data_ptr(), dst_s.data_ptr(), pos_s.data_ptr(),
-                                               rel_s.data_ptr(), rp_s.data_ptr(), slots, total.data_ptr(), N, d,
-                                               te.table_rows, accumulate, _stream())
-    _lib.check(rc, "mlgnn_max_table_grad_by_type")
+    _lib.call("mlgnn_max_table_grad_by_type", go_k, argmax, dst_s, pos_s, rel_s, rp_s, slots, total, N, d,
+              te.table_rows, accumulate, _lib.stream())
     TABLE_DEST_STATS["by_type"] += 1
 
 
@@ -728,8 +701,7 @@ def _gather_backward(ctx, saved, route, go_k, gx, shifted):
             sink.buf = ge
     ws_n = int(_lib.lib.mlgnn_csr_aggregate_bwd_workspace_floats(
         N, d, _DTYPE_IDS[x.dtype], rank, AGGR_SUM if shifted is not None else aggr_id, int(learn_t)))
-    if ws_n < 0:
-        _lib.check(ws_n, "mlgnn_csr_aggregate_bwd_workspace_floats")
+    _lib.check(min(ws_n, 0), "mlgnn_csr_aggregate_bwd_workspace_floats")
     ws = torch.empty(ws_n, dtype=torch.float32, device=x.device) if ws_n > 0 else None
     guv = torch.empty((rank + 1, d), dtype=torch.float32, device=x.device) if edge_mode == EDGE_RANK1 else None
     timer = KERNEL_TIMER
@@ -751,8 +723,7 @@ def _gather_backward(ctx, saved, route, go_k, gx, shifted):
         _by_type_table_grad(go_k, argmax, g, te, sink, ws, rank)
     if route == ROUTE_TABLE_FIXED:
         total, accumulate = sink.table_total(te.table_rows, d, x.device)
-        _lib.check(_lib.lib.mlgnn_table_grad_finish(sink.fix.data_ptr(), total.data_ptr(), te.table_rows, d, accumulate,
-                                                    _stream()), "mlgnn_table_grad_finish")
+        _lib.call("mlgnn_table_grad_finish", sink.fix, total, te.table_rows, d, accumulate, _lib.stream())
     SHIFT_STATS["given" if shifted else "computed"] += int(aggr_id == AGGR_SOFTMAX and not learn_t)
     if sink is not None or te is not None:
         ge = None                                        # reported once, by the fan-out node of the shared term

@@ -68,12 +68,9 @@ class FlatAdam:
         t = self.step_count
         step_size = g["lr"] / (1.0 - b1 ** t)
         bias2_sqrt = math.sqrt(1.0 - b2 ** t)
-        rc = _lib.lib.mlgnn_adam_step(self.flat_p.data_ptr(), self.bucket.flat.data_ptr(), self.exp_avg.data_ptr(),
-                                      self.exp_avg_sq.data_ptr(), self.flat_p.numel(), self._offsets.data_ptr(),
-                                      self.bucket.live.data_ptr(), len(self.sizes), self.clip, b1, b2, g["eps"],
-                                      g["weight_decay"], step_size, bias2_sqrt, self._ws.data_ptr(),
-                                      torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "mlgnn_adam_step")
+        _lib.call("mlgnn_adam_step", self.flat_p, self.bucket.flat, self.exp_avg, self.exp_avg_sq, self.flat_p.numel(),
+                  self._offsets, self.bucket.live, len(self.sizes), self.clip, b1, b2, g["eps"], g["weight_decay"],
+                  step_size, bias2_sqrt, self._ws, _lib.stream())
         # the kernel wrote parameters, moments and (when clipping) gradients behind torch's back: bump the version
         # counters (shared by every view of the flat buffers) so that version-keyed caches and autograd's
         # saved-tensor checks see the update

@@ -19,18 +19,13 @@ import torch
 from . import _lib
 from .dense import _aligned
 from .graph import CSRGraph, _same_view
-from .ops import _stream, weighted_mean_aggregate
+from .ops import weighted_mean_aggregate
 
 AGGR_MAX, AGGR_SOFTMAX = 2, 3
 # (0: PathwayConv as torch lines -- index_select, the outer-product GEMM, scatter_reduce / the softmax steps; for A/B runs)
 PATHWAY_CONV = os.environ.get("MLGNN_PATHWAY_CONV", "1") == "1"
-STATS = {"fwd": 0, "bwd": 0, "topology_build": 0, "topology_hit": 0, "compact_layers": 0, "all_rows_layers": 0,
-         "torch_layers": 0}
-if os.environ.get("MLGNN_PRINT_STATS", "0") == "1":
-    import atexit
-    import sys
-    atexit.register(lambda: print("mlgnn stats: pathway_conv %r (MLGNN_PATHWAY_CONV=%d)" % (STATS, PATHWAY_CONV),
-                                  file=sys.stderr))
+STATS = _lib.stats("pathway_conv", suffix=" (MLGNN_PATHWAY_CONV=%d)" % PATHWAY_CONV, fwd=0, bwd=0, topology_build=0,
+                   topology_hit=0, compact_layers=0, all_rows_layers=0, torch_layers=0)
 
 
 class PathwayTopology:
@@ -105,10 +100,8 @@ class _PathwayAggregate(torch.autograd.Function):
         winner = torch.empty((R, d), dtype=torch.int32, device=dev) if aggr_id == AGGR_MAX else None
         lse = torch.empty((R, d), dtype=torch.float32, device=dev) if aggr_id == AGGR_SOFTMAX else None
         g = topo.graph
-        rc = _lib.lib.mlgnn_pathway_conv_fwd(y.data_ptr(), g.rowptr.data_ptr(), _lib.ptr(g.col), topo.attr_dst.data_ptr(),
-                                             topo.rows.data_ptr(), _lib.ptr(b), out.data_ptr(), _lib.ptr(winner),
-                                             _lib.ptr(lse), N, E, R, d, aggr_id, t_imm, _lib.ptr(t_dev), _stream())
-        _lib.check(rc, "mlgnn_pathway_conv_fwd")
+        _lib.call("mlgnn_pathway_conv_fwd", y, g.rowptr, g.col, topo.attr_dst, topo.rows, b, out, winner, lse, N, E, R,
+                  d, aggr_id, t_imm, t_dev, _lib.stream())
         STATS["fwd"] += 1
         ctx.save_for_backward(y, b, t_dev, out, winner, lse)
         ctx.topo = topo
@@ -132,12 +125,8 @@ class _PathwayAggregate(torch.autograd.Function):
         gt = torch.empty(1, **f32) if learn_t else None
         floats = int(_lib.lib.mlgnn_pathway_conv_bwd_workspace_floats(N, E, R, d, int(learn_t)))
         ws = torch.empty(max(floats, 1), **f32)
-        rc = _lib.lib.mlgnn_pathway_conv_bwd(go.data_ptr(), y.data_ptr(), out.data_ptr(), _lib.ptr(b), _lib.ptr(winner),
-                                             _lib.ptr(lse), g.rowptr_t.data_ptr(), _lib.ptr(g.col_t), _lib.ptr(g.pos_t),
-                                             topo.attr_src.data_ptr(), topo.row_of.data_ptr(), gy.data_ptr(), _lib.ptr(gb),
-                                             _lib.ptr(gt), ws.data_ptr(), floats, N, E, R, d, aggr_id, t_imm,
-                                             _lib.ptr(t_dev), int(learn_t), _stream())
-        _lib.check(rc, "mlgnn_pathway_conv_bwd")
+        _lib.call("mlgnn_pathway_conv_bwd", go, y, out, b, winner, lse, g.rowptr_t, g.col_t, g.pos_t, topo.attr_src,
+                  topo.row_of, gy, gb, gt, ws, floats, N, E, R, d, aggr_id, t_imm, t_dev, int(learn_t), _lib.stream())
         STATS["bwd"] += 1
         return (gy, gb.reshape(shape_b) if need_b else None, gt.reshape(shape_t) if need_t else None, None, None, None)
 
@@ -146,8 +135,7 @@ def pathway_aggregate(y, bias, topology, aggr="max", t=1.0, learn_t=False):
     """``Y`` [N, 2d] (``Y0 | Y1`` side by side), ``bias`` [d] or None, ``topology`` a :class:`PathwayTopology` ->
     ``m[rows] + bias`` [R, d] for ``aggr`` in ``max`` / ``softmax`` (``t``: a float, or a one-element device tensor;
     ``learn_t``: the gradient also runs through the softmax weights and to ``t``)."""
-    if not (torch.is_tensor(y) and y.is_cuda):
-        raise RuntimeError("mlgnn.pathway_conv has no CPU path (the kernels are HIP only); move the tensors to the GPU")
+    _lib.require_gpu(y, "mlgnn.pathway_conv")
     if aggr not in ("max", "softmax"):
         raise ValueError("pathway_aggregate: aggr must be 'max' or 'softmax' (add / mean: pathway_linear_aggregate)")
     if not pathway_conv_supported(y, topology):
@@ -169,8 +157,7 @@ def pathway_aggregate(y, bias, topology, aggr="max", t=1.0, learn_t=False):
 def pathway_linear_aggregate(x, weight, bias, topology, mean=False):
     """``add`` / ``mean`` of the messages, [R, d]: by linearity ``sum_e msg_e = [S0 | S1][rows] [W0 | W1]^T + deg b`` with
     ``S_k = sum_e a_ek x_j`` -- two calls of the weighted CSR aggregation and one product on the destination rows."""
-    if not (torch.is_tensor(x) and x.is_cuda):
-        raise RuntimeError("mlgnn.pathway_conv has no CPU path (the kernels are HIP only); move the tensors to the GPU")
+    _lib.require_gpu(x, "mlgnn.pathway_conv")
     a = topology.edge_attr
     s0 = weighted_mean_aggregate(x, topology.graph, a[:, 0], mean=mean)
     s1 = weighted_mean_aggregate(x, topology.graph, a[:, 1], mean=mean)

@@ -5,7 +5,7 @@ the first maximal row).  Forward: two deterministic HIP stages (``csrc/pool.hip`
 import torch
 
 from . import _lib
-from .ops import DTYPE_F32, _stream
+from .ops import DTYPE_F32
 
 _KINDS = {"sum": 0, "add": 0, "mean": 1, "max": 2}
 
@@ -20,9 +20,7 @@ class _SegmentPool(torch.autograd.Function):
         argmax = torch.empty((B, d), dtype=torch.int32, device=x.device) if kind == 2 else None
         nbytes = int(_lib.lib.mlgnn_segment_pool_workspace_bytes(B, d))
         ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
-        rc = _lib.lib.mlgnn_segment_pool_fwd(x.data_ptr(), ptr.data_ptr(), out.data_ptr(), _lib.ptr(argmax),
-                                             ws.data_ptr(), nbytes, B, d, kind, DTYPE_F32, _stream())
-        _lib.check(rc, "mlgnn_segment_pool_fwd")
+        _lib.call("mlgnn_segment_pool_fwd", x, ptr, out, argmax, ws, nbytes, B, d, kind, DTYPE_F32, _lib.stream())
         ctx.kind, ctx.shape = kind, (N, d)
         ctx.save_for_backward(ptr, batch, argmax)
         return out

@@ -15,19 +15,13 @@ import torch.nn.functional as F
 
 from . import _lib
 from .norm import _keep_mask
-from .ops import _stream
 from .sage import flatten_channel_last
 
 # MLGNN_POOL_FLATTEN=0: module_pool_flatten always takes the torch lines (same-box A/B runs)
 ENABLED = os.environ.get("MLGNN_POOL_FLATTEN", "1") != "0"
 
 # how often each path was taken (development / tests: which path a model ran on)
-POOL_STATS = {"hip": 0, "torch": 0}
-
-if os.environ.get("MLGNN_PRINT_STATS", "0") == "1":
-    import atexit
-    import sys
-    atexit.register(lambda: print("mlgnn stats: pool_flatten %r" % (POOL_STATS,), file=sys.stderr))
+POOL_STATS = _lib.stats("pool_flatten", hip=0, torch=0)
 
 
 def _window(window):
@@ -60,9 +54,7 @@ class _PoolFlatten(torch.autograd.Function):
         winner = None
         if need_x and ph * pw > 1:
             winner = torch.empty((B, n), dtype=torch.uint8, device=xr.device)
-        rc = _lib.lib.mlgnn_pool_flatten_fwd(xr.data_ptr(), _lib.ptr(keep), keep_scale, _lib.ptr(age), out.data_ptr(),
-                                             _lib.ptr(winner), B, H, W, C, ph, pw, _stream())
-        _lib.check(rc, "mlgnn_pool_flatten_fwd")
+        _lib.call("mlgnn_pool_flatten_fwd", xr, keep, keep_scale, age, out, winner, B, H, W, C, ph, pw, _lib.stream())
         POOL_STATS["hip"] += 1
         ctx.save_for_backward(keep, winner)
         ctx.cfg = (B, H, W, C, ph, pw, float(keep_scale), age is not None)
@@ -76,9 +68,8 @@ class _PoolFlatten(torch.autograd.Function):
         B, H, W, C, ph, pw, keep_scale, has_age = ctx.cfg
         go = go.contiguous()
         gx = torch.empty((B, H, W, C), dtype=torch.float32, device=go.device)
-        rc = _lib.lib.mlgnn_pool_flatten_bwd(go.data_ptr(), _lib.ptr(keep), keep_scale, _lib.ptr(winner), gx.data_ptr(),
-                                             int(has_age), B, H, W, C, ph, pw, _stream())
-        _lib.check(rc, "mlgnn_pool_flatten_bwd")
+        _lib.call("mlgnn_pool_flatten_bwd", go, keep, keep_scale, winner, gx, int(has_age), B, H, W, C, ph, pw,
+                  _lib.stream())
         return gx, None, None, None, None, None
 
 
@@ -87,8 +78,7 @@ def pool_flatten(x, window, dropout_p=0.0, training=False, age=None, dropout_mas
     ``x`` [B, C, H, W]; without ``age`` no column is appended.  ``dropout_mask`` (one flag per pooled element, in
     output order ``[B, C * Ho * Wo]``) replaces the draw: the result is ``pooled * mask / (1 - dropout_p)``.  ``age`` is
     data (no gradient).  The caller checks :func:`pool_flatten_supported` first."""
-    if not (torch.is_tensor(x) and x.is_cuda):
-        raise RuntimeError("mlgnn.pool_flatten has no CPU path (the kernels are HIP only); move the tensors to the GPU")
+    _lib.require_gpu(x, "mlgnn.pool_flatten")
     ph, pw = _window(window)
     if not pool_flatten_supported(x, (ph, pw)):
         raise ValueError("pool_flatten: unsupported input %s %s (strides %s) with window %s (fp32, channel-last, "

@@ -10,7 +10,7 @@ and weight gradient (``csrc/project.hip``).
 import torch
 
 from . import _lib
-from .ops import DTYPE_BF16, DTYPE_F32, _dev_f32, _stream
+from .ops import DTYPE_BF16, DTYPE_F32, _dev_f32
 
 
 class Membership:
@@ -85,11 +85,8 @@ class _SegmentProject(torch.autograd.Function):
         if G != tables.G or R != tables.R:
             raise ValueError("membership table does not match the inputs")
         out_t = torch.empty((tables.B * tables.S, K, C), dtype=x.dtype, device=x.device)
-        rc = _lib.lib.mlgnn_segment_project_fwd(
-            x.data_ptr(), w.data_ptr(), tables.seg_ptr.data_ptr(), _lib.ptr(tables.seg_mem),
-            tables.mem_row.data_ptr(), out_t.data_ptr(), tables.B * tables.S, C, G, K, tables.S, int(n_groups), dt,
-            _stream())
-        _lib.check(rc, "mlgnn_segment_project_fwd")
+        _lib.call("mlgnn_segment_project_fwd", x, w, tables.seg_ptr, tables.seg_mem, tables.mem_row, out_t,
+                  tables.B * tables.S, C, G, K, tables.S, int(n_groups), dt, _lib.stream())
         ctx.tables = tables
         ctx.n_groups = int(n_groups)
         ctx.dt = dt
@@ -105,11 +102,8 @@ class _SegmentProject(torch.autograd.Function):
         gout_t = gout_t.to(x.dtype).contiguous() if ctx.dt == DTYPE_BF16 else _dev_f32(gout_t, "grad_out")
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         gwp = torch.empty((t.B * G, K), dtype=torch.float32, device=x.device) if ctx.needs_input_grad[1] else None
-        rc = _lib.lib.mlgnn_segment_project_bwd(
-            gout_t.data_ptr(), x.data_ptr(), w.data_ptr(), t.seg_ptr.data_ptr(), _lib.ptr(t.seg_mem),
-            t.mem_row.data_ptr(), t.mem_seg.data_ptr(), t.node_ptr.data_ptr(), _lib.ptr(t.node_mem),
-            _lib.ptr(gx), _lib.ptr(gwp), t.B * t.S, R, C, G, K, t.S, ctx.n_groups, ctx.dt, _stream())
-        _lib.check(rc, "mlgnn_segment_project_bwd")
+        _lib.call("mlgnn_segment_project_bwd", gout_t, x, w, t.seg_ptr, t.seg_mem, t.mem_row, t.mem_seg, t.node_ptr,
+                  t.node_mem, gx, gwp, t.B * t.S, R, C, G, K, t.S, ctx.n_groups, ctx.dt, _lib.stream())
         gw = gwp.reshape(t.B, G, K).sum(0).to(ctx.w_dtype) if gwp is not None else None
         return gx, gw, None, None
 

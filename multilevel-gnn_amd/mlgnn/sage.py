@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from .dense import WGRAD_MIN_ROWS, _aligned, _wgrad, tall_matmul_nt, tall_matmul_supported
-from .ops import AGGR_MEAN, AGGR_SUM, MSG_IDENTITY, MSG_WEIGHTED, _aggregate_bwd, _aggregate_fwd, _stream
+from .ops import AGGR_MEAN, AGGR_SUM, MSG_IDENTITY, MSG_WEIGHTED, _aggregate_bwd, _aggregate_fwd
 from .tags import tag_row_max
 
 STATS = {"fused": 0, "fallback": 0}
@@ -57,9 +57,7 @@ class _SageLayer(torch.autograd.Function):
         w_nn_c, w_r_c = w_nn.contiguous(), w_r.contiguous()
         f32 = dict(dtype=torch.float32, device=dev)
         w_cat, w_x1, w_c = torch.empty((cout, 2 * cin), **f32), torch.empty((cout, cin), **f32), torch.empty((cout, cin), **f32)
-        rc = _lib.lib.mlgnn_sage_fold_fwd(w_nn_c.data_ptr(), w_r_c.data_ptr(), w_cat.data_ptr(), w_x1.data_ptr(), w_c.data_ptr(),
-                                          cin, cout, int(bool(relative)), _stream())
-        _lib.check(rc, "mlgnn_sage_fold_fwd")
+        _lib.call("mlgnn_sage_fold_fwd", w_nn_c, w_r_c, w_cat, w_x1, w_c, cin, cout, int(bool(relative)), _lib.stream())
         y = torch.empty((N, cout), dtype=torch.float32, device=dev)
         y_max = torch.empty(N, dtype=torch.float32, device=dev)
         a_max = torch.empty(N, dtype=torch.float32, device=dev)
@@ -67,10 +65,8 @@ class _SageLayer(torch.autograd.Function):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         bias = b_nn.contiguous() if b_nn is not None else None
         rs = row_scale.reshape(-1).contiguous() if row_scale is not None else None
-        rc = _lib.lib.mlgnn_tallgemm_dual(x.data_ptr(), agg.data_ptr(), w_cat.data_ptr(), _lib.ptr(bias), float(slope),
-                                          _lib.ptr(rs), y.data_ptr(), y_max.data_ptr(), a_max.data_ptr(), ws.data_ptr(),
-                                          nbytes, N, cin, cin, cout, _stream())
-        _lib.check(rc, "mlgnn_tallgemm_dual")
+        _lib.call("mlgnn_tallgemm_dual", x, agg, w_cat, bias, float(slope), rs, y, y_max, a_max, ws, nbytes, N, cin,
+                  cin, cout, _lib.stream())
         ctx.save_for_backward(x, agg, y, w_nn_c, w_r_c, w_x1, w_c, rs, a_max)
         ctx.graph, ctx.ew_pair = graph, ew_pair
         ctx.cfg = (float(slope), bool(relative), b_nn is not None, msg, aggr)
@@ -87,9 +83,7 @@ class _SageLayer(torch.autograd.Function):
         gy = _aligned(gy)
         dz = torch.empty_like(y)
         dz_max = torch.empty(N, dtype=torch.float32, device=x.device)
-        rc = _lib.lib.mlgnn_leaky_relu_bwd(gy.data_ptr(), y.data_ptr(), _lib.ptr(rs), slope, dz.data_ptr(), dz_max.data_ptr(),
-                                           N, cout, _stream())
-        _lib.check(rc, "mlgnn_leaky_relu_bwd")
+        _lib.call("mlgnn_leaky_relu_bwd", gy, y, rs, slope, dz, dz_max, N, cout, _lib.stream())
         gx = None
         if ctx.needs_input_grad[0]:
             # d agg = dz W_c, through the transposed aggregation, then dx = dz W_x' + that (the sum in the GEMM's epilogue)
@@ -105,9 +99,7 @@ class _SageLayer(torch.autograd.Function):
         g_nn = torch.empty_like(w_nn)
         g_r = torch.empty_like(w_r)
         gw_x1, gw_c = gw_x1.contiguous(), gw_c.contiguous()
-        rc = _lib.lib.mlgnn_sage_fold_bwd(gw_x1.data_ptr(), gw_c.data_ptr(), w_nn.data_ptr(), w_r.data_ptr(), g_nn.data_ptr(),
-                                          g_r.data_ptr(), cin, cout, int(relative), _stream())
-        _lib.check(rc, "mlgnn_sage_fold_bwd")
+        _lib.call("mlgnn_sage_fold_bwd", gw_x1, gw_c, w_nn, w_r, g_nn, g_r, cin, cout, int(relative), _lib.stream())
         return gx, g_nn, (gb if has_bias else None), g_r, None, None, None, None, None, None
 
 
@@ -140,9 +132,7 @@ class _NodeEmbed(torch.autograd.Function):
         emb = _aligned(emb)
         h = torch.empty((batch * nodes, C), dtype=torch.float32, device=x.device)
         h_max = torch.empty(batch * nodes, dtype=torch.float32, device=x.device)
-        rc = _lib.lib.mlgnn_node_embed_fwd(x.data_ptr(), emb.data_ptr(), h.data_ptr(), h_max.data_ptr(), batch, nodes, C,
-                                           _stream())
-        _lib.check(rc, "mlgnn_node_embed_fwd")
+        _lib.call("mlgnn_node_embed_fwd", x, emb, h, h_max, batch, nodes, C, _lib.stream())
         ctx.save_for_backward(x)
         ctx.cfg = (batch, nodes, C)
         ctx.mark_non_differentiable(h_max)
@@ -154,8 +144,7 @@ class _NodeEmbed(torch.autograd.Function):
         batch, nodes, C = ctx.cfg
         gh = _aligned(gh)
         ge = torch.empty((nodes, C), dtype=torch.float32, device=gh.device)
-        rc = _lib.lib.mlgnn_node_embed_bwd(x.data_ptr(), gh.data_ptr(), ge.data_ptr(), batch, nodes, C, _stream())
-        _lib.check(rc, "mlgnn_node_embed_bwd")
+        _lib.call("mlgnn_node_embed_bwd", x, gh, ge, batch, nodes, C, _lib.stream())
         return None, ge
 
 
@@ -190,9 +179,8 @@ class _LinearAct(torch.autograd.Function):
         nbytes = int(_lib.lib.mlgnn_tallgemm_workspace_bytes(R, J, 0))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         bias = b.contiguous() if b is not None else None
-        rc = _lib.lib.mlgnn_tallgemm_dual(x.data_ptr(), None, w.data_ptr(), _lib.ptr(bias), float(slope), None, y.data_ptr(),
-                                          y_max.data_ptr(), a_max.data_ptr(), ws.data_ptr(), nbytes, N, R, 0, J, _stream())
-        _lib.check(rc, "mlgnn_tallgemm_dual")
+        _lib.call("mlgnn_tallgemm_dual", x, None, w, bias, float(slope), None, y, y_max, a_max, ws, nbytes, N, R, 0, J,
+                  _lib.stream())
         ctx.save_for_backward(x, w, y, a_max)
         ctx.cfg = (float(slope), b is not None)
         ctx.mark_non_differentiable(y_max)
@@ -206,9 +194,7 @@ class _LinearAct(torch.autograd.Function):
         gy = _aligned(gy)
         dz = torch.empty_like(y)
         dz_max = torch.empty(N, dtype=torch.float32, device=y.device)
-        rc = _lib.lib.mlgnn_leaky_relu_bwd(gy.data_ptr(), y.data_ptr(), None, slope, dz.data_ptr(), dz_max.data_ptr(), N, J,
-                                           _stream())
-        _lib.check(rc, "mlgnn_leaky_relu_bwd")
+        _lib.call("mlgnn_leaky_relu_bwd", gy, y, None, slope, dz, dz_max, N, J, _lib.stream())
         gx = tall_matmul_nt(dz, w, row_max=dz_max, bt_transposed=True) if ctx.needs_input_grad[0] else None
         gw, gb = _wgrad(dz, x, go_max=dz_max, x_max=a_max)
         return gx, gw, (gb if has_bias else None), None
@@ -237,7 +223,7 @@ class _TransposeBatched(torch.autograd.Function):
     def forward(ctx, x):
         B, R, C = x.shape
         y = torch.empty((B, C, R), dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib.mlgnn_transpose_batched(x.data_ptr(), y.data_ptr(), B, R, C, _stream()), "mlgnn_transpose_batched")
+        _lib.call("mlgnn_transpose_batched", x, y, B, R, C, _lib.stream())
         return y
 
     @staticmethod
@@ -245,7 +231,7 @@ class _TransposeBatched(torch.autograd.Function):
         gy = gy.contiguous()
         B, C, R = gy.shape
         gx = torch.empty((B, R, C), dtype=torch.float32, device=gy.device)
-        _lib.check(_lib.lib.mlgnn_transpose_batched(gy.data_ptr(), gx.data_ptr(), B, C, R, _stream()), "mlgnn_transpose_batched")
+        _lib.call("mlgnn_transpose_batched", gy, gx, B, C, R, _lib.stream())
         return gx
 
 

@@ -11,18 +11,12 @@ import os
 import torch
 
 from . import _lib
-from .ops import _stream
 
 # MLGNN_VQ_FUSED=0: VectorQuantizer.forward always takes the torch lines (same-box A/B runs)
 ENABLED = os.environ.get("MLGNN_VQ_FUSED", "1") != "0"
 
 # how often each path was taken (development / tests: which path a model ran on)
-VQ_STATS = {"hip": 0, "torch": 0}
-
-if os.environ.get("MLGNN_PRINT_STATS", "0") == "1":
-    import atexit
-    import sys
-    atexit.register(lambda: print("mlgnn stats: vq %r" % (VQ_STATS,), file=sys.stderr))
+VQ_STATS = _lib.stats("vq", hip=0, torch=0)
 
 ROWS = 64                # MLGNN_VQ_ROWS of include/mlgnn.h: rows per loss partial
 RULE = "fp32 device tensors, latents [..., D] and codebook [K, D] with 1 <= K <= 65536, 1 <= D <= 128, N * D < 2^30"
@@ -57,9 +51,7 @@ class _Vq(torch.autograd.Function):
         else:
             loss = torch.empty((), dtype=torch.float32, device=z.device)
             partials = torch.empty(((N + ROWS - 1) // ROWS,), dtype=torch.float32, device=z.device)
-            rc = _lib.lib.mlgnn_vq_fwd(z.data_ptr(), codebook.data_ptr(), index.data_ptr(), out.data_ptr(),
-                                       partials.data_ptr(), loss.data_ptr(), beta, N, K, D, _stream())
-            _lib.check(rc, "mlgnn_vq_fwd")
+            _lib.call("mlgnn_vq_fwd", z, codebook, index, out, partials, loss, beta, N, K, D, _lib.stream())
         VQ_STATS["hip"] += 1
         if any(ctx.needs_input_grad[:2]):
             ctx.save_for_backward(z, codebook, index)
@@ -86,10 +78,8 @@ class _Vq(torch.autograd.Function):
         if need_cb:
             grad_cb = torch.empty_like(codebook) if (N and g_loss is not None) else torch.zeros_like(codebook)
         if N:
-            rc = _lib.lib.mlgnn_vq_bwd(z.data_ptr(), codebook.data_ptr(), index.data_ptr(), _lib.ptr(g_out),
-                                       _lib.ptr(g_loss), _lib.ptr(grad_z),
-                                       _lib.ptr(grad_cb) if g_loss is not None else None, ctx.beta, N, K, D, _stream())
-            _lib.check(rc, "mlgnn_vq_bwd")
+            _lib.call("mlgnn_vq_bwd", z, codebook, index, g_out, g_loss, grad_z,
+                      grad_cb if g_loss is not None else None, ctx.beta, N, K, D, _lib.stream())
         return grad_z, grad_cb, None
 
 
@@ -100,8 +90,7 @@ def vector_quantize(latents, codebook, beta=0.25, return_indices=False):
     ``(codebook[indices] - latents)^2`` carries the commitment gradient to ``latents`` and the embedding gradient to
     ``codebook``.  ``latents`` is ``[..., D]`` of any leading shape.  No rows: ``vq_loss`` is NaN, as ``mse_loss`` of
     nothing is."""
-    if not (torch.is_tensor(latents) and latents.is_cuda):
-        raise RuntimeError("mlgnn.vector_quantize has no CPU path (the kernels are HIP only); move the tensors to the GPU")
+    _lib.require_gpu(latents, "mlgnn.vector_quantize")
     if not vq_supported(latents, codebook):
         raise ValueError("vector_quantize: unsupported input %s %s with codebook %s %s (%s)" % (
             tuple(latents.shape), latents.dtype, tuple(codebook.shape) if torch.is_tensor(codebook) else None,

@@ -2,6 +2,7 @@
 import ast
 import glob
 import os
+import re
 from types import SimpleNamespace
 
 import numpy as np
@@ -45,6 +46,29 @@ def load_golden(path):
             nested[head] = un
     top.update(nested)
     return top
+
+
+def header_declarations(path):
+    """The function declarations of a C header such as include/mlgnn.h -> ``{name: (return type, [argument types])}``.  A
+    type is ``"ptr"`` for any pointer, otherwise its C spelling without ``const`` (``"int64_t"``, ``"int"``, ``"float"``,
+    ``"double"``, ``"void"``).  Comments, preprocessor lines and struct bodies are dropped first."""
+    text = open(path).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    text = re.sub(r"^\s*#[^\n]*", "", text, flags=re.M)
+    text = re.sub(r"\btypedef\s+struct\b[^{;]*\{[^}]*\}[^;]*;", "", text)
+
+    def kind(decl, named):
+        if "*" in decl or "[" in decl:
+            return "ptr"
+        words = [w for w in decl.split() if w != "const"]
+        return " ".join(words[:-1] if named and len(words) > 1 else words)
+
+    out = {}
+    for ret, name, args in re.findall(r"([\w \t*]+?)\b(\w+)\s*\(([^()]*)\)\s*;", text):
+        args = [a.strip() for a in args.split(",")]
+        out[name] = (kind(ret, False), [] if args in ([""], ["void"]) else [kind(a, True) for a in args])
+    return out
 
 
 def literal(s):

@@ -13,13 +13,28 @@ def _declared():
     return sorted(set(re.findall(r"\b(mlgnn_[a-z0-9_]+)\s*\(", text)))
 
 
+def _c_kind(t):
+    """A ctypes return / argument type of ``SIGNATURES`` in the words of ``_util.header_declarations``."""
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "ptr"
+    return {ctypes.c_int64: "int64_t", ctypes.c_int: "int", ctypes.c_float: "float", ctypes.c_double: "double"}[t]
+
+
 def test_header_and_binding_agree():
+    """Every declaration of include/mlgnn.h is bound, and bound with the header's return and argument types."""
+    from _util import header_declarations
     from mlgnn import _lib
     declared = _declared()
     assert declared, "no declarations parsed"
     assert sorted(_lib.SIGNATURES) == declared
+    typed = header_declarations(os.path.join(ROOT, "include", "mlgnn.h"))
+    assert sorted(typed) == declared                 # the two parsers see the same functions
     for name in declared:
         assert hasattr(_lib.lib, name), name
+        res, args = _lib.SIGNATURES[name]
+        assert (_c_kind(res), [_c_kind(a) for a in args]) == typed[name], name
 
 
 def test_version_and_error_codes():

@@ -118,7 +118,7 @@ def test_leaky_relu_backward_widths(J):
     gradient of ``leaky_relu(z) * row_scale`` from its output, and ``max |row|`` of it.  Bound of
     tests/test_sage_layer_gpu.py (1e-4, elementwise)."""
     from mlgnn import _lib
-    from mlgnn.ops import _stream
+    from mlgnn._lib import stream as _stream
     gen = torch.Generator().manual_seed(J)
     slope = 0.2
     z = torch.randn(ROWS, J, generator=gen)

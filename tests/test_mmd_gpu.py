@@ -109,7 +109,7 @@ def test_autograd_contract():
 @pytest.mark.parametrize("kind", KINDS)
 def test_terms_may_be_absent_at_the_abi(kind):
     from mlgnn import _lib, mmd as M
-    from mlgnn.ops import _stream
+    from mlgnn._lib import stream as _stream
     z, prior = _inputs(6, 4, 8)
     mmd, _ = M.mmd_per_pathway(z, prior, kind, 2.0, return_terms=True)
     out = torch.empty_like(mmd)
