@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const AdamArgs a) {
   __shared__ float wsum[4];
   __shared__ int64_t off_lds[kAdamLdsParams + 1];
   const bool in_lds = a.n_params <= kAdamLdsParams;
-  if (in_lds)
+  if (a.live && in_lds)                                  // live == NULL: the offsets are not read (they may be NULL)
     for (int i = threadIdx.x; i <= a.n_params; i += 256) off_lds[i] = a.offsets[i];
   float clip = 1.f;
   if (a.max_norm > 0.f) {

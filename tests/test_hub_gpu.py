@@ -25,11 +25,24 @@ def _power_law_graph(gen, N=30000, E=400000):
     return torch.stack([src, dst])
 
 
-def _case(aggr, edge_kind, d, learn=False, dtype=torch.float32, seed=0):
+def _many_hubs_graph(gen, N=3000):
+    """300 rows of 257..346 incoming edges (rows 0..299) and 300 of as many outgoing ones (rows 1000..1299): more split
+    rows in either direction than the 256 wavefronts that combine the chunks, so a wavefront combines a second row."""
+    n = 257 + torch.arange(300) % 90
+    total = int(n.sum())
+    dst = [torch.repeat_interleave(torch.arange(300), n), torch.randint(300, N - 3, (total,), generator=gen),
+           torch.randint(300, N - 3, (20000,), generator=gen)]
+    src = [torch.randint(300, N, (total,), generator=gen), torch.repeat_interleave(torch.arange(1000, 1300), n),
+           torch.randint(300, N, (20000,), generator=gen)]
+    return torch.stack([torch.cat(src), torch.cat(dst)])
+
+
+def _case(aggr, edge_kind, d, learn=False, dtype=torch.float32, seed=0, graph=_power_law_graph, N=30000,
+          at_least=(97 + 19 + 1, 3), at_least_src=(0, 0)):
     from mlgnn import CSRGraph, RankOneEdge, gen_aggregate
     gen = torch.Generator().manual_seed(seed)
-    ei = _power_law_graph(gen)
-    N, E = 30000, ei.shape[1]
+    ei = graph(gen)
+    E = ei.shape[1]
     rnd = (lambda t: t.to(dtype).float())
     x = rnd(torch.randn(N, d, generator=gen))
     a = torch.rand(E, generator=gen)
@@ -58,7 +71,9 @@ def _case(aggr, edge_kind, d, learn=False, dtype=torch.float32, seed=0):
     gl = {k: val.detach().to(DEV).to(dtype if k == "x" else torch.float32).requires_grad_(True) for k, val in leaves.items()}
     graph = CSRGraph(ei.to(DEV), N)
     counts = graph.hub_tables("dst")[2].cpu().tolist()
-    assert counts[0] >= 97 + 19 + 1 and counts[1] >= 3, counts          # the planted rows really are split
+    assert counts[0] >= at_least[0] and counts[1] >= at_least[1], counts          # the planted rows really are split
+    counts = graph.hub_tables("src")[2].cpu().tolist()
+    assert counts[0] >= at_least_src[0] and counts[1] >= at_least_src[1], counts
     edge = RankOneEdge(a.to(DEV), gl["u"], gl["v"]) if edge_kind == "rank1" else None
     out = gen_aggregate(gl["x"], graph, edge, aggr=aggr, t=gl.get("t", 0.8), p=2.0, learn_t=learn)
     tol = TOL if dtype == torch.float32 else 2.0 ** -7
@@ -77,6 +92,13 @@ def _case(aggr, edge_kind, d, learn=False, dtype=torch.float32, seed=0):
 @pytest.mark.parametrize("edge_kind", ["rank1", "none"])
 def test_split_rows_match_oracle(aggr, edge_kind):
     _case(aggr, edge_kind, 64)
+
+
+@pytest.mark.parametrize("aggr", ["softmax", "max", "mean"])
+def test_more_split_rows_than_combining_wavefronts(aggr):
+    """The chunks are combined by 64 workgroups of four wavefronts, one split row per wavefront and trip: with 300 split
+    rows by destination (forward) and 300 by source (backward) 44 wavefronts of each launch take a second row."""
+    _case(aggr, "rank1", 64, seed=6, graph=_many_hubs_graph, N=3000, at_least=(300, 300), at_least_src=(300, 300))
 
 
 def test_split_rows_learnable_temperature_and_wide_rows():
@@ -143,3 +165,42 @@ def test_graph_without_long_rows_is_untouched():
     finally:
         graph_mod.HUB_CAP = 256
     assert torch.equal(out, ref)
+
+
+def test_chunk_tables_past_the_grid_cap():
+    """``mlgnn_hub_rows`` on its own, on more rows than the 1024 x 256 threads of its capped grid: 777 rows are seen on a
+    thread's second trip, long ones among them.  The rows arrive in any order (two counters, advanced atomically), so the
+    tables are compared as sets: every long row once, its chunks consecutive and in chunk order, nothing else."""
+    from mlgnn import _lib
+    cap = 256
+    N = 1024 * 256 + 777
+    gen = torch.Generator().manual_seed(12)
+    deg = torch.randint(0, 4, (N,), generator=gen)
+    long_rows = {5: 257, 1000: 25000, 262143: 513, 262144: 512, 262145: 1025, 262500: 256 * 3 + 1, N - 1: 300}
+    for r, n in long_rows.items():
+        deg[r] = n
+    deg[77], deg[N - 2] = cap, cap                                           # exactly the cap: not split
+    rowptr = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(deg, 0)]).to(torch.int32)
+    E = int(rowptr[-1])
+    want_hubs = {r: (n + cap - 1) // cap - 1 for r, n in long_rows.items()}
+    assert all(k >= 1 for k in want_hubs.values()) and int((deg > cap).sum()) == len(long_rows)
+    capacity = int(_lib.lib.mlgnn_hub_capacity(E, cap))
+    assert capacity >= sum(want_hubs.values())
+    i32 = dict(dtype=torch.int32, device=DEV)
+    vrows, hubs = torch.full((capacity, 3), -7, **i32), torch.full((capacity, 3), -7, **i32)
+    counts = torch.full((2,), -7, **i32)
+    _lib.call("mlgnn_hub_rows", rowptr.to(DEV), N, cap, capacity, vrows, hubs, counts, _lib.stream())
+    n_chunks, n_hubs = counts.cpu().tolist()
+    assert (n_chunks, n_hubs) == (sum(want_hubs.values()), len(want_hubs))
+    vrows, hubs = vrows.cpu(), hubs.cpu()
+    assert bool((vrows[n_chunks:] == -7).all()) and bool((hubs[n_hubs:] == -7).all())      # nothing past the counts
+    seen, used = {}, torch.zeros(n_chunks, dtype=torch.bool)
+    for r, v0, k in hubs[:n_hubs].tolist():
+        assert r not in seen and want_hubs.get(r) == k, (r, k)
+        seen[r] = v0
+        assert not bool(used[v0:v0 + k].any())
+        used[v0:v0 + k] = True
+        beg, end = int(rowptr[r]), int(rowptr[r + 1])
+        want = [[r, beg + (c + 1) * cap, min(end, beg + (c + 2) * cap)] for c in range(k)]
+        assert vrows[v0:v0 + k].tolist() == want, r
+    assert sorted(seen) == sorted(want_hubs) and bool(used.all())

@@ -36,9 +36,22 @@ def _ready(graph):
                                                  (64, 3000, False, 2), (100, 700, True, 1), (256, 40000, True, 2), (256, 40000, True, 1),
                                                  (32, 0, True, 2), (36, 90, False, 1), (128, 5000, False, 1)])
 def test_sparse_max_backward_matches_general_and_oracle(d, T, add_root, layers, monkeypatch):
+    _check_backward(2999, 30000, d, T, add_root, layers, monkeypatch)
+
+
+def test_sparse_max_backward_past_the_persistent_grid(monkeypatch):
+    """The three kernels run on persistent grids of at most 2048 workgroups (fewer where the occupancy says so), and the
+    other cases stay below that: one unit of work per workgroup.  Here every kernel has more units than that cap -- 2188
+    units of 32 rows for the winner lists and for the by-source pass (d = 32: eight lanes per row), 2251 units of four
+    table rows -- so workgroups walk their XCD's share with a stride."""
+    N, d, T = 70001, 32, 9001
+    assert -(-N // 32) > 2048 and -(-T // 4) > 2048
+    _check_backward(N, 280000, d, T, True, 1, monkeypatch)
+
+
+def _check_backward(N, E, d, T, add_root, layers, monkeypatch):
     from mlgnn import CSRGraph, TableEdge, gen_aggregate, ops
     gen = torch.Generator().manual_seed(300 + d + T)
-    N, E = 2999, 30000
     ei = _short_graph(gen, N, E, max_deg=256 if d == 128 else 40)
     # inputs on a 2^-12 grid: x_j + e is then exact in fp32 and in fp64, both pick the same winners (first maximal edge on
     # exact ties), and the comparison with the fp64 oracle cannot trip over a near-tie resolved differently

@@ -28,6 +28,7 @@ SHAPES = [
     (2, 1, 1, 1, 1, 1),            # one element
     (1, 16, 16, 3, 16, 16),        # one 256-element window per channel
     (2, 7, 5, 67, 2, 2),           # C past one tile and not a multiple of 4
+    (65537, 2, 2, 3, 2, 1),        # past the 65 535 samples of one launch: the second launch takes the last two samples
 ]
 _IDS = ["x".join(map(str, s)) for s in SHAPES]
 _CACHE = {}

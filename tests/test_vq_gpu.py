@@ -27,9 +27,15 @@ DENORMAL = 1.5e-45
 
 # (N, K, D): the default latent width; at least two LDS slabs whatever the slab size; odd sizes, rows one past a multiple
 # of the wavefront; one code; an odd width; many slabs at a narrow width; every code used with distances tiny against
-# the operands' scale (the codebook is 512 of the latent rows, times 1.05)
+# the operands' scale (the codebook is 512 of the latent rows, times 1.05).
+# Past the launch geometry of one trip: "long_scan" -- the by-code scan of grad_codebook takes the index vector in chunks of
+# 16 * 64 = 1024 rows: two full chunks and a partial one of 65, members on both sides of a chunk boundary; "past_caps" --
+# 258 loss partials (the one-workgroup sum takes a second trip of 256) and N * D = 542 817 > 2048 * 256 elements (grad_z
+# runs on its capped grid and strides a second time), one float per load; "past_caps_vec" -- the same on the 16-byte
+# loads of the forward (N * D = 526 368)
 CASES = {"d2": (300, 512, 2), "slabs": (300, 1024, 64), "odd": (257, 7, 3), "one_code": (129, 1, 5),
-         "odd_width": (700, 96, 33), "narrow_slabs": (500, 2048, 16), "latent_rows": (900, 512, 64)}
+         "odd_width": (700, 96, 33), "narrow_slabs": (500, 2048, 16), "latent_rows": (900, 512, 64),
+         "long_scan": (2113, 96, 33), "past_caps": (16449, 96, 33), "past_caps_vec": (16449, 128, 32)}
 
 
 @functools.lru_cache(maxsize=None)
