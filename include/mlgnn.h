@@ -1162,6 +1162,31 @@ int mlgnn_mutual_info_cd(const double* x, const int32_t* labels, const double* p
                          int32_t* counts, int64_t n, int64_t n_features, int k, int n_labels, void* stream);
 
 /*
+ * Mutual information between continuous features and a continuous target (csrc/mutual_info_cc.hip), fp64: the estimator
+ * of Kraskov, Stoegbauer and Grassberger 2004 as scikit-learn's mutual_info_regression evaluates it (_compute_mi_cc), one
+ * workgroup per feature, one launch.
+ *   x [F, N] feature-major (row f = the prepared column of feature f: scaled, noise added), y [N] the prepared target in
+ *   the same sample order (unsorted: the kernel sorts its own copy); k = n_neighbors.
+ *     d_ij = max(fl|x_j - x_i|, fl|y_j - y_i|)                  Chebyshev; one IEEE subtraction each, no expanded form
+ *     r_i  = the k-th smallest d_ij over j != i
+ *     nx_i = #{ j != i : fl|x_j - x_i| <= nextafter(r_i, 0) },  ny_i = #{ j != i : fl|y_j - y_i| <= nextafter(r_i, 0) }
+ *     mi [F] = max(0, (base - (1 / N) sum_i psi[nx_i + 1]) - (1 / N) sum_i psi[ny_i + 1])
+ *   psi [N + 1]: psi[j] = digamma(j) for j = 1 .. N (entry 0 is not used), base = digamma(N) + digamma(k): both from the
+ *   host, neither depends on the feature.  nx, ny [F, N] int32 in the input's sample order, or NULL (not wanted, each on
+ *   its own).
+ * No atomics, every sum in a fixed order: bitwise reproducible.  Shapes (mlgnn_mutual_info_cc_supported): 2 <= N <= 2048,
+ * F >= 0 with F * N * 8 below 4 GiB, 1 <= k <= min(N - 1, MLGNN_MI_CC_MAX_NEIGHBORS) (the per-lane list of the k nearest
+ * distances lives in LDS).  MLGNN_E_NULL for a NULL x, y, psi or mi, then MLGNN_E_SHAPE for anything else (as in
+ * mlgnn_mutual_info_cd, NULL operands are reported before shape errors); both before anything is launched.  F = 0 is a
+ * no-op (nothing is read or written).  No workspace.  No index depends on a value: NaN input gives NaN or arbitrary
+ * counts, never an access out of bounds.
+ */
+#define MLGNN_MI_CC_MAX_NEIGHBORS 32
+int mlgnn_mutual_info_cc_supported(int64_t n, int64_t n_features, int k);
+int mlgnn_mutual_info_cc(const double* x, const double* y, const double* psi, double base, double* mi, int32_t* nx,
+                         int32_t* ny, int64_t n, int64_t n_features, int k, void* stream);
+
+/*
  * PathwayConv's message + aggregation (csrc/pathway_conv.hip; the reference's torch_vertex.py:107-178): the second
  * message-passing step over the gene -> pathway-node membership edges, for MLGNN_AGGR_MAX and MLGNN_AGGR_SOFTMAX (add and
  * mean are two weighted sums of the existing aggregation by linearity; MLGNN_E_MODE here).  fp32, no atomics, every

@@ -16,5 +16,7 @@ from .latent import vae_latent, vae_latent_supported  # noqa: F401
 from .criterion import TrainCriterion, criterion_supported, train_criterion  # noqa: F401
 from .pathway_conv import PathwayTopology, pathway_aggregate, pathway_conv_supported  # noqa: F401
 from .mutual_info import mutual_info_classif, mutual_info_supported, tree_path  # noqa: F401
+from .mutual_info import (mutual_info_cc, mutual_info_regression, mutual_info_regression_supported,  # noqa: F401
+                          prepare_regression)
 from .ops import (LowRankEdge, RankOneEdge, TableEdge, edge_type_embedding, gen_aggregate, share_edge_gradient,  # noqa: F401
                   weighted_mean_aggregate)

@@ -139,6 +139,8 @@ SIGNATURES = {
     "mlgnn_criterion_bwd": (_INT, [_P, _P, _P, _I64, _P, _P, _P, _P, _F, _INT, _P, _P, _I64, _I64, _P]),
     "mlgnn_mutual_info_supported": (_INT, [_I64, _I64, _INT, _INT]),
     "mlgnn_mutual_info_cd": (_INT, [_P, _P, _P, _c.c_double, _P, _P, _I64, _I64, _INT, _INT, _P]),
+    "mlgnn_mutual_info_cc_supported": (_INT, [_I64, _I64, _INT]),
+    "mlgnn_mutual_info_cc": (_INT, [_P, _P, _P, _c.c_double, _P, _P, _P, _I64, _I64, _INT, _P]),
     "mlgnn_pathway_conv_supported": (_INT, [_I64] * 3),
     "mlgnn_pathway_conv_fwd": (_INT, [_P] * 9 + [_I64] * 4 + [_INT, _F, _P, _P]),
     "mlgnn_pathway_conv_bwd_workspace_floats": (_I64, [_I64] * 4 + [_INT]),

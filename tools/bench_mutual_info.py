@@ -18,7 +18,11 @@ the two legs alternate over three repeats, so the scikit-learn leg's own spread 
 
 The first shape is run once untimed on the op's leg before the sweep (the first launch of a process carries the load of
 its code object).  Results are written after every shape.  Writes profiles/mutual_info.json.  Development tool; run it
-under a time limit of its own (``timeout -k 10 900 python tools/bench_mutual_info.py``)."""
+under a time limit of its own (``timeout -k 10 900 python tools/bench_mutual_info.py``).
+
+``--regression``: the same protocol for ``mlgnn.mutual_info_regression`` (csrc/mutual_info_cc.hip, the Kraskov estimator)
+against scikit-learn's ``mutual_info_regression`` at the same shapes, with the target ``generate_mutual_mask`` hands over
+when ``mutual_classif`` is false: the two-valued label as float.  Writes profiles/mutual_info_regression.json."""
 import argparse
 import json
 import os
@@ -84,6 +88,54 @@ def kernel_ms(prepared, y, k, warmup, iters):
     return s.elapsed_time(e) / iters
 
 
+def kernel_ms_regression(prepared, y_prepared, k, warmup, iters):
+    """The launch of mlgnn_mutual_info_cc alone, operands resident on the device."""
+    from scipy.special import digamma
+    n, F = prepared.shape
+    dev = torch.device("cuda:0")
+    psi = np.zeros(n + 1)
+    psi[1:] = digamma(np.arange(1, n + 1))
+    base = float(digamma(n) + digamma(k))
+    xt = torch.from_numpy(prepared).to(dev).t().contiguous()
+    y_d, psi_d = torch.from_numpy(y_prepared).to(dev), torch.from_numpy(psi).to(dev)
+    mi = torch.empty(F, dtype=torch.float64, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def launch():
+        _lib.check(_lib.lib.mlgnn_mutual_info_cc(xt.data_ptr(), y_d.data_ptr(), psi_d.data_ptr(), base, mi.data_ptr(), None,
+                                                 None, n, F, k, stream), "mlgnn_mutual_info_cc")
+
+    for _ in range(warmup):
+        launch()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    s.record()
+    for _ in range(iters):
+        launch()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / iters
+
+
+def bench_shape_regression(name, n, F, k, warmup, iters, repeats):
+    from sklearn.feature_selection import mutual_info_regression as sk_regression
+    x, labels = make_data(n, F, 7)
+    y = labels.astype(np.float64)                                             # what train.py passes
+    assert MI.mutual_info_regression_supported(n, F, k), (n, F, k)
+    entry = {"shape": name, "N": n, "F": F, "k": k, "label_counts": [int(c) for c in MI.label_counts(labels)],
+             "hip_end_to_end_ms": [], "sklearn_ms": [], "prepare_ms": [], "kernel_ms": []}
+    got = want = None
+    for _ in range(repeats):                                                  # the legs alternate
+        ms, got = wall(lambda: MI.mutual_info_regression(x, y, n_neighbors=k, random_state=SEED))
+        entry["hip_end_to_end_ms"].append(ms)
+        ms, want = wall(lambda: sk_regression(x, y, n_neighbors=k, random_state=SEED))
+        entry["sklearn_ms"].append(ms)
+        ms, (prepared, y_prepared) = wall(lambda: MI.prepare_regression(x, y, SEED))
+        entry["prepare_ms"].append(ms)
+        entry["kernel_ms"].append(kernel_ms_regression(prepared, y_prepared, k, warmup, iters))
+    return summarise(entry, got, want, repeats)
+
+
 def bench_shape(name, n, F, k, warmup, iters, repeats):
     from sklearn.feature_selection import mutual_info_classif as sk_classif
     x, y = make_data(n, F, 7)
@@ -100,6 +152,10 @@ def bench_shape(name, n, F, k, warmup, iters, repeats):
         ms, (prepared, _) = wall(lambda: MI.prepare(x, y, SEED))
         entry["prepare_ms"].append(ms)
         entry["kernel_ms"].append(kernel_ms(prepared, y, k, warmup, iters))
+    return summarise(entry, got, want, repeats)
+
+
+def summarise(entry, got, want, repeats):
     entry["max_abs_diff_to_sklearn"] = float(np.abs(got - want).max())
     entry["masks_equal_at_the_mean_threshold"] = bool(np.array_equal(got < got.mean(), want < want.mean()))
     hip, ref = entry["hip_end_to_end_ms"], entry["sklearn_ms"]
@@ -118,14 +174,23 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=REPEATS)
     ap.add_argument("--shapes", default=",".join(s[0] for s in SHAPES))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mutual_info.json"))
+    ap.add_argument("--regression", action="store_true",
+                    help="mutual_info_regression (csrc/mutual_info_cc.hip) instead of mutual_info_classif")
+    ap.add_argument("--out", default=None, help="default: profiles/mutual_info.json, with --regression "
+                                                "profiles/mutual_info_regression.json")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "mutual_info_regression.json" if a.regression else "mutual_info.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_mutual_info.py needs the GPU: there is no CPU path of the op to time")
     import scipy
     import sklearn
-    result = {"workload": "mutual_info_classif over every gene column (generate_mutual_mask), fp64: the op of "
-                          "csrc/mutual_info.hip against the scikit-learn call (MLGNN_MI_FUSED=0), same input and random_state",
+    workload = ("mutual_info_regression over every gene column (generate_mutual_mask with mutual_classif false; the "
+                "target is the two-valued label as float), fp64: the op of csrc/mutual_info_cc.hip (MLGNN_MI_REG_FUSED=1) "
+                "against the scikit-learn call, same input and random_state") if a.regression else \
+        ("mutual_info_classif over every gene column (generate_mutual_mask), fp64: the op of "
+         "csrc/mutual_info.hip against the scikit-learn call (MLGNN_MI_FUSED=0), same input and random_state")
+    result = {"workload": workload,
               "timing": "wall clock around each call with a device synchronise, the two legs alternating over %d repeats, "
                         "one process; the kernel alone by device events, mean of %d launches after %d" % (a.repeats, a.iters,
                                                                                                         a.warmup),
@@ -133,14 +198,19 @@ def main():
               "versions": {"sklearn": sklearn.__version__, "numpy": np.__version__, "scipy": scipy.__version__},
               "shapes": []}
     x, y = make_data(SHAPES[0][1], 512, 1)
-    MI.mutual_info_classif(x, y, n_neighbors=SHAPES[0][3], random_state=SEED)      # discarded: the code object loads
+    if a.regression:                                                               # discarded: the code object loads
+        MI.mutual_info_regression(x, y.astype(np.float64), n_neighbors=SHAPES[0][3], random_state=SEED)
+    else:
+        MI.mutual_info_classif(x, y, n_neighbors=SHAPES[0][3], random_state=SEED)
     for name, n, F, k in SHAPES:
         if name not in a.shapes.split(","):
             continue
-        entry = bench_shape(name, n, F, k, a.warmup, a.iters, a.repeats)
+        entry = (bench_shape_regression if a.regression else bench_shape)(name, n, F, k, a.warmup, a.iters, a.repeats)
         result["shapes"].append(entry)
         print(json.dumps(entry), flush=True)
-        result["ships_enabled"] = all(e["summary"]["beats_sklearn_by_more_than_its_spread"] for e in result["shapes"]) \
+        # (the regression switch ships as 0 whatever the timing: mlgnn/mutual_info.py, next to DEFAULT_REG_ENABLED)
+        verdict = "beats_sklearn_at_every_shape" if a.regression else "ships_enabled"
+        result[verdict] = all(e["summary"]["beats_sklearn_by_more_than_its_spread"] for e in result["shapes"]) \
             and len(result["shapes"]) == len(SHAPES)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as fh:
