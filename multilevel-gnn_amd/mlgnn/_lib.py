@@ -302,6 +302,28 @@ def call(name, *args):
     check(getattr(lib, name)(*argv), name)
 
 
+def size(name, *dims, or_none=False):
+    """The count the size query ``name`` (looked up on ``lib`` at call time, as in :func:`call`) answers for ``dims``.  A
+    negative status -- a shape it does not take -- raises :class:`MlgnnError`; ``or_none`` (predicates): ``None`` instead."""
+    n = int(getattr(lib, name)(*dims))
+    if n < 0 and or_none:
+        return None
+    check(min(n, 0), name)
+    return n
+
+
+def workspace(name, *dims, device, times=1, unit=None):
+    """``(scratch tensor, n)``, ``n = times * size(name, *dims)`` being the size the entry point is told (``times``: one
+    workspace per graph of a batch).  The element type comes from the query's name -- ``*_floats`` / ``*_bytes`` -- or from
+    ``unit`` where the name has no such suffix.  The tensor has ``max(n, 1)`` elements, so it is never NULL: no entry point
+    refuses a non-NULL workspace of size 0 (csrc/: they compare ``workspace_floats < need`` or test ``!workspace``)."""
+    dtype = {"floats": torch.float32, "bytes": torch.uint8}.get(unit or name.rsplit("_", 1)[-1])
+    if dtype is None:
+        raise ValueError("%s: the name says neither _floats nor _bytes; pass unit=" % name)
+    n = times * size(name, *dims)
+    return torch.empty(max(n, 1), dtype=dtype, device=device), n
+
+
 def require_gpu(t, who):
     if not (torch.is_tensor(t) and t.is_cuda):
         raise RuntimeError("%s has no CPU path (the kernels are HIP only); move the tensors to the GPU" % who)

@@ -65,8 +65,7 @@ class _Conv2d(torch.autograd.Function):
         gb = torch.empty((Cout,), **f32) if need_b else None
         floats, ws = 0, None
         if need_w or need_b:
-            floats = int(_lib.lib.mlgnn_conv2d_bwd_workspace_floats(B, H, W, Cin, Cout, k))
-            ws = torch.empty(max(floats, 1), **f32)
+            ws, floats = _lib.workspace("mlgnn_conv2d_bwd_workspace_floats", B, H, W, Cin, Cout, k, device=xr.device)
         _lib.call("mlgnn_conv2d_bwd", gy, xr, weight, y, int(relu), gx, gw, gb, ws, floats, B, H, W, Cin, Cout, k,
                   _lib.stream())
         if B == 0:

@@ -54,9 +54,7 @@ class _Criterion(torch.autograd.Function):
         dev = pred.device
         loss = torch.empty((), dtype=torch.float32, device=dev)
         terms = torch.empty(3, dtype=torch.float32, device=dev)
-        n_ws = _lib.lib.mlgnn_criterion_workspace(B, M)
-        _lib.check(min(n_ws, 0), "mlgnn_criterion_workspace")
-        ws = torch.empty(n_ws, dtype=torch.float32, device=dev) if n_ws else None
+        ws, n_ws = _lib.workspace("mlgnn_criterion_workspace", B, M, device=dev, unit="floats")
         stats = torch.empty((2, M), dtype=torch.float32, device=dev) if (M and want[1]) else None
         cw_rows = 0 if (cw is None or cw.dim() == 1) else cw.shape[0]
         _lib.call("mlgnn_criterion_fwd", pred, y, cw, cw_rows, feat, coef, mode, ws, n_ws, stats, loss, terms, B, M,

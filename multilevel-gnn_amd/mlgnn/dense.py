@@ -36,8 +36,7 @@ def tall_matmul_nt(a, bt, bias=None, residual=None, row_max=None, ln=None, bt_tr
     a, bt = _aligned(a), _aligned(bt)
     dt = _DTYPE_IDS[a.dtype]
     out = torch.empty((N, J), dtype=a.dtype, device=a.device)
-    nbytes = int(_lib.lib.mlgnn_tallgemm_workspace_bytes(R, J, dt))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
+    ws, nbytes = _lib.workspace("mlgnn_tallgemm_workspace_bytes", R, J, dt, device=a.device)
     if residual is not None:
         residual = residual.contiguous()
     if bias is not None:
@@ -67,8 +66,7 @@ def tall_matmul_lnin_postln(xhat, w, bias, residual, row_max, gamma, beta, post)
     f32 = dict(dtype=torch.float32, device=xhat.device)
     out, y = torch.empty((N, J), **f32), torch.empty((N, J), **f32)
     mean, rstd = torch.empty(N, **f32), torch.empty(N, **f32)
-    nbytes = int(_lib.lib.mlgnn_tallgemm_workspace_bytes(R, J, 0))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=xhat.device)
+    ws, nbytes = _lib.workspace("mlgnn_tallgemm_workspace_bytes", R, J, 0, device=xhat.device)
     if residual is not None:
         residual = residual.contiguous()
     if bias is not None:
@@ -91,8 +89,7 @@ def tall_matmul_nt_shift(a, w, row_max, lse, rowptr):
     gx = torch.empty((N, J), dtype=torch.float32, device=a.device)
     gt = torch.empty_like(gx)
     flag = torch.empty(4, dtype=torch.int32, device=a.device)
-    nbytes = int(_lib.lib.mlgnn_tallgemm_workspace_bytes(R, J, 0))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
+    ws, nbytes = _lib.workspace("mlgnn_tallgemm_workspace_bytes", R, J, 0, device=a.device)
     ROW_MAX_STATS["given" if row_max is not None else "computed"] += 1
     _lib.call("mlgnn_tallgemm_nt_shift", a, w, 1, row_max, lse, rowptr, gx, gt, flag, ws, nbytes, N, R, J,
               _lib.stream())
@@ -109,8 +106,7 @@ def tall_matmul_bf16_shift(go, weight, lse):
     gx = torch.empty((N, K), dtype=torch.bfloat16, device=go.device)
     gt = torch.empty_like(gx)
     flag = torch.empty(4, dtype=torch.int32, device=go.device)
-    nbytes = int(_lib.lib.mlgnn_tallgemm_workspace_bytes(M, K, 1))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=go.device)
+    ws, nbytes = _lib.workspace("mlgnn_tallgemm_workspace_bytes", M, K, 1, device=go.device)
     _lib.call("mlgnn_tallgemm_bf16_shift", go, bt, lse, gx, gt, flag, ws, nbytes, N, M, K, _lib.stream())
     return gx, gt, flag
 
@@ -125,8 +121,7 @@ def tall_matmul_ln_backward(go, w, xhat, rstd, gamma, beta, row_max=None):
     gh = torch.empty((N, J), dtype=torch.float32, device=go.device)
     ggb = torch.empty((2, J), dtype=torch.float32, device=go.device)
     rmax = torch.empty(N, dtype=torch.float32, device=go.device)
-    nbytes = int(_lib.lib.mlgnn_tallgemm_lnbwd_workspace_bytes(R, J))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=go.device)
+    ws, nbytes = _lib.workspace("mlgnn_tallgemm_lnbwd_workspace_bytes", R, J, device=go.device)
     ROW_MAX_STATS["given" if row_max is not None else "computed"] += 1
     _lib.call("mlgnn_tallgemm_lnbwd", go, w, 1, row_max, xhat, rstd, gamma.contiguous(), beta.contiguous(), gh, rmax,
               ggb, ws, nbytes, N, R, J, _lib.stream())
@@ -165,9 +160,7 @@ def linear_backward(go, w, x, go_max, x_max, epilogue, rstd=None, gamma=None, be
     parts = torch.empty(256, **f32)
     gt = torch.empty((N, K), **f32) if epilogue == LB_SHIFT else None
     flag = torch.empty(4, dtype=torch.int32, device=go.device) if epilogue == LB_SHIFT else None
-    n = int(_lib.lib.mlgnn_linear_bwd_workspace_floats(N, M, K, epilogue))
-    _lib.check(min(n, 0), "mlgnn_linear_bwd_workspace_floats")
-    ws = torch.empty(n, **f32)
+    ws, n = _lib.workspace("mlgnn_linear_bwd_workspace_floats", N, M, K, epilogue, device=go.device)
     if gamma is not None:
         gamma, beta = gamma.contiguous(), beta.contiguous()
     _lib.call("mlgnn_linear_bwd", go, w, x, go_max, int(go_max_is_parts), x_max, epilogue, rstd, gamma, beta, lse, dx,
@@ -189,6 +182,11 @@ def tall_matmul_supported(N, R, J, dtype=torch.float32):
 _WGRAD_EXACT = os.environ.get("MLGNN_WGRAD_EXACT", "0") == "1"        # always the exact three-way bf16 split
 
 
+def wgrad_supported(N, M, K, dtype_id=0):
+    """The split-row weight-gradient kernels (:func:`_wgrad`) tile ``go [N,M]^T x [N,K]`` in this storage type."""
+    return bool(_lib.size("mlgnn_linear_wgrad_workspace_floats", N, M, K, dtype_id, or_none=True))
+
+
 def _wgrad(go, x, x_gamma=None, x_beta=None, go_max=None, x_max=None, out_dtype=None):
     """``(go^T x' [M,K], colsum go [M])`` with ``x' = x`` or ``relu(x_gamma x + x_beta)`` (``csrc/wgrad.hip``).
     ``go_max`` / ``x_max``: ``max |row|`` of ``go`` and of ``x'`` ([N] fp32, the side outputs of the kernels that produced
@@ -197,8 +195,7 @@ def _wgrad(go, x, x_gamma=None, x_beta=None, go_max=None, x_max=None, out_dtype=
     N, K = x.shape
     M = go.shape[1]
     dt = _DTYPE_IDS[x.dtype]
-    n = int(_lib.lib.mlgnn_linear_wgrad_workspace_floats(N, M, K, dt))
-    ws = torch.empty(n, dtype=torch.float32, device=x.device)
+    ws, n = _lib.workspace("mlgnn_linear_wgrad_workspace_floats", N, M, K, dt, device=x.device)
     out = torch.empty(M * K + M, dtype=torch.float32, device=x.device)          # fp32 for either storage type
     if (x.dtype != torch.float32 or go_max is None or x_max is None or _WGRAD_EXACT
             or go_max.shape[0] != N or x_max.shape[0] != N):
@@ -253,7 +250,7 @@ class _TallLinear(torch.autograd.Function):
                 gx = go.matmul(weight)
         gw = gb = None
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            if x.dtype == torch.float32 or _lib.lib.mlgnn_linear_wgrad_workspace_floats(N, M, K, _DTYPE_IDS[x.dtype]) > 0:
+            if x.dtype == torch.float32 or wgrad_supported(N, M, K, _DTYPE_IDS[x.dtype]):
                 gw, gb = _wgrad(go, x, go_max=row_max_of(go), x_max=ctx.x_max, out_dtype=x.dtype)
                 gb = gb if ctx.has_bias else None
             else:                                    # bf16 widths the transposed-read kernel does not tile
@@ -406,8 +403,7 @@ def fused_mlp2_supported(x, w1, w2):
     k, h, o = x.shape[1], w1.shape[0], w2.shape[0]
     ok = (64, 128, 256)
     return (k in ok and h in ok and o in ok and k * h * 4 <= 128 * 1024 and h * o * 4 <= 128 * 1024 and h <= 256
-            and _lib.lib.mlgnn_linear_wgrad_workspace_floats(x.shape[0], h, k, 0) > 0
-            and _lib.lib.mlgnn_linear_wgrad_workspace_floats(x.shape[0], o, h, 0) > 0)
+            and wgrad_supported(x.shape[0], h, k) and wgrad_supported(x.shape[0], o, h))
 
 
 def fused_mlp2(x, w1, b1, gamma, beta, eps, w2, b2, residual=None, post_norm=None):
@@ -439,11 +435,11 @@ class _WideLinearF32(torch.autograd.Function):
         N, R = x.shape
         J = weight.shape[0]
         x, weight = x.contiguous(), weight.contiguous()
-        Np = int(_lib.lib.mlgnn_linear_f32x3_padded_rows(N))
+        Np = _lib.size("mlgnn_linear_f32x3_padded_rows", N)
         y = torch.empty((Np, J), dtype=torch.float32, device=x.device)
-        ws = torch.empty(int(_lib.lib.mlgnn_linear_f32x3_fwd_workspace_bytes(N, R, J)), dtype=torch.uint8, device=x.device)
+        ws, nbytes = _lib.workspace("mlgnn_linear_f32x3_fwd_workspace_bytes", N, R, J, device=x.device)
         b = bias.contiguous() if bias is not None else None
-        _lib.call("mlgnn_linear_f32x3_fwd", x, weight, b, y, ws, ws.numel(), N, R, J, _lib.stream())
+        _lib.call("mlgnn_linear_f32x3_fwd", x, weight, b, y, ws, nbytes, N, R, J, _lib.stream())
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         return y[:N]
@@ -454,12 +450,12 @@ class _WideLinearF32(torch.autograd.Function):
         N, R = x.shape
         J = weight.shape[0]
         go = go.contiguous()
-        Np = int(_lib.lib.mlgnn_linear_f32x3_padded_rows(N))
+        Np = _lib.size("mlgnn_linear_f32x3_padded_rows", N)
         gx = torch.empty((Np, R), dtype=torch.float32, device=x.device) if ctx.needs_input_grad[0] else None
         gw = torch.empty((J, R), dtype=torch.float32, device=x.device)
-        ws = torch.empty(int(_lib.lib.mlgnn_linear_f32x3_bwd_workspace_bytes(N, R, J)), dtype=torch.uint8, device=x.device)
+        ws, nbytes = _lib.workspace("mlgnn_linear_f32x3_bwd_workspace_bytes", N, R, J, device=x.device)
         gb = torch.empty(J, dtype=torch.float32, device=x.device) if ctx.has_bias else None
-        _lib.call("mlgnn_linear_f32x3_bwd", go, x, weight, gx, gw, gb, ws, ws.numel(), N, R, J, _lib.stream())
+        _lib.call("mlgnn_linear_f32x3_bwd", go, x, weight, gx, gw, gb, ws, nbytes, N, R, J, _lib.stream())
         return (gx[:N] if gx is not None else None), gw, gb
 
 
@@ -495,8 +491,7 @@ class _SkinnyLinear(torch.autograd.Function):
         M, K = x.shape
         J = w.shape[0]
         y = torch.empty((M, J), dtype=torch.float32, device=x.device)
-        n = int(_lib.lib.mlgnn_skinny_linear_fwd_workspace_floats(M, J, K))
-        ws = torch.empty(n, dtype=torch.float32, device=x.device)
+        ws, n = _lib.workspace("mlgnn_skinny_linear_fwd_workspace_floats", M, J, K, device=x.device)
         b = bias.contiguous() if bias is not None else None
         _lib.call("mlgnn_skinny_linear_fwd", x, w, b, y, ws, n, M, J, K, _lib.stream())
         ctx.save_for_backward(x, w)
@@ -552,8 +547,7 @@ class _NarrowLinear(torch.autograd.Function):
         go = _aligned(go)
         gw = gb = None
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            n = int(_lib.lib.mlgnn_narrow_linear_bwd_workspace_floats(R, J))
-            ws = torch.empty(n, dtype=torch.float32, device=x.device)
+            ws, n = _lib.workspace("mlgnn_narrow_linear_bwd_workspace_floats", R, J, device=x.device)
             out = torch.empty(J * R + J, dtype=torch.float32, device=x.device)
             _lib.call("mlgnn_narrow_linear_bwd", go, x, out, ws, n, N, R, J, _lib.stream())
             gw, gb = out[:J * R].view(J, R), (out[J * R:] if ctx.has_bias else None)
@@ -577,7 +571,7 @@ def linear(x, weight, bias=None, residual=None):
         return out if residual is None else out + residual
     if (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= WGRAD_MIN_ROWS
             and x.is_contiguous() and torch.is_grad_enabled()
-            and _lib.lib.mlgnn_linear_wgrad_workspace_floats(x.shape[0], weight.shape[0], weight.shape[1], 0) > 0):
+            and wgrad_supported(x.shape[0], weight.shape[0], weight.shape[1])):
         return _TallLinear.apply(x, weight, bias, residual)
     if (x.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and x.dim() == 2
             and x.shape[0] >= WGRAD_MIN_ROWS and x.is_contiguous()
@@ -625,8 +619,7 @@ class _DenseSageFused(torch.autograd.Function):
         gx = torch.empty_like(x)
         gadj = torch.empty((B, n, n), dtype=x.dtype, device=x.device) if need_adj else None
         gw = torch.empty(2 * O * C + O, dtype=torch.float32, device=x.device)
-        ws_n = int(_lib.lib.mlgnn_dense_sage_bwd_workspace_floats(B, C, O))
-        ws = torch.empty(ws_n, dtype=torch.float32, device=x.device)
+        ws, ws_n = _lib.workspace("mlgnn_dense_sage_bwd_workspace_floats", B, C, O, device=x.device)
         _lib.call("mlgnn_dense_sage_bwd", gy, y, rinv, x, adj, w_rel, w_root, gx, gadj, gw, ws, ws_n, B, n, C, O,
                   int(batched), int(normalize), _DTYPE_IDS[x.dtype], _lib.stream())
         if need_adj and not batched:
@@ -727,9 +720,9 @@ class _DiffPoolLarge(torch.autograd.Function):
         a_out = torch.empty((B, K, K), dtype=out_dtype, device=dev)
         stats = torch.empty(3, dtype=torch.float32, device=dev)
         scal = torch.empty(2, dtype=out_dtype, device=dev)
-        ws = torch.empty(B * int(_lib.lib.mlgnn_diffpool_large_workspace_bytes(N, K, C)), dtype=torch.uint8, device=dev)
+        ws, nbytes = _lib.workspace("mlgnn_diffpool_large_workspace_bytes", N, K, C, device=dev, times=B)
         _lib.call("mlgnn_diffpool_large_fwd", zb, ab, s, _DTYPE_IDS[s.dtype], S, x_out, a_out, scal,
-                  _DTYPE_IDS[out_dtype], stats, ws, ws.numel(), N, K, C, B, adj_batched, _lib.stream())
+                  _DTYPE_IDS[out_dtype], stats, ws, nbytes, N, K, C, B, adj_batched, _lib.stream())
         ctx.save_for_backward(zb, ab, s, S, ws, stats)
         ctx.cfg = (bool(adj_symmetric), z.dtype, adj_batched)
         ctx.adj_dtype, ctx.adj_shape = adj.dtype, adj.shape
@@ -751,10 +744,9 @@ class _DiffPoolLarge(torch.autograd.Function):
         # the adjacency of a second pooling level is the first level's S^T A S (diff_pooling.py:116-127): its gradient
         # is two more products of the same chain
         gadj = torch.empty((B, N, N), dtype=s.dtype, device=dev) if ctx.needs_input_grad[1] else None
-        wb = torch.empty(B * int(_lib.lib.mlgnn_diffpool_large_bwd_workspace_bytes(N, K, C, int(sym))), dtype=torch.uint8,
-                         device=dev)
+        wb, nbytes = _lib.workspace("mlgnn_diffpool_large_bwd_workspace_bytes", N, K, C, int(sym), device=dev, times=B)
         _lib.call("mlgnn_diffpool_large_bwd", zb, ab, s, _DTYPE_IDS[s.dtype], S, ws, gx, ga, _DTYPE_IDS[gdt], g_link,
-                  g_ent, _DTYPE_IDS[g_link.dtype], stats, gz, gs, gadj, int(sym), wb, wb.numel(), N, K, C, B,
+                  g_ent, _DTYPE_IDS[g_link.dtype], stats, gz, gs, gadj, int(sym), wb, nbytes, N, K, C, B,
                   adj_batched, _lib.stream())
         if gadj is not None:
             if not adj_batched and B > 1:
@@ -781,8 +773,8 @@ class _DiffPoolLargeFP32(torch.autograd.Function):
         a_out = torch.empty((B, K, K), dtype=torch.float32, device=dev)
         stats = torch.empty(3, dtype=torch.float32, device=dev)
         scal = torch.empty(2, dtype=torch.float32, device=dev)
-        ws = torch.empty(B * int(_lib.lib.mlgnn_diffpool_large_f32_workspace_bytes(N, K, C)), dtype=torch.uint8, device=dev)
-        _lib.call("mlgnn_diffpool_large_f32_fwd", z, adj, s, S, x_out, a_out, scal, stats, ws, ws.numel(), N, K, C, B,
+        ws, nbytes = _lib.workspace("mlgnn_diffpool_large_f32_workspace_bytes", N, K, C, device=dev, times=B)
+        _lib.call("mlgnn_diffpool_large_f32_fwd", z, adj, s, S, x_out, a_out, scal, stats, ws, nbytes, N, K, C, B,
                   adj_batched, _lib.stream())
         ctx.save_for_backward(adj, s, ws, stats)
         ctx.cfg = (bool(adj_symmetric), adj_batched, (B, N, K, C))
@@ -800,10 +792,9 @@ class _DiffPoolLargeFP32(torch.autograd.Function):
         gs = torch.empty((B, N, K), dtype=torch.float32, device=dev)
         # the adjacency of a second pooling level is the first level's S^T A S (diff_pooling.py:116-127)
         gadj = torch.empty((B, N, N), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
-        wb = torch.empty(B * int(_lib.lib.mlgnn_diffpool_large_f32_bwd_workspace_bytes(N, K, C, int(sym))), dtype=torch.uint8,
-                         device=dev)
+        wb, nbytes = _lib.workspace("mlgnn_diffpool_large_f32_bwd_workspace_bytes", N, K, C, int(sym), device=dev, times=B)
         _lib.call("mlgnn_diffpool_large_f32_bwd", adj, s, ws, gx, ga, g_link, g_ent, stats, gz, gs, gadj, int(sym), wb,
-                  wb.numel(), N, K, C, B, adj_batched, _lib.stream())
+                  nbytes, N, K, C, B, adj_batched, _lib.stream())
         if gadj is not None:
             if not adj_batched and B > 1:
                 gadj = gadj.sum(0, keepdim=True)                 # shared adjacency: the sum over the graphs that read it

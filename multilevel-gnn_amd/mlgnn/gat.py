@@ -71,8 +71,7 @@ class _GatAggregate(torch.autograd.Function):
                     t.zero_()
         else:
             gy = _aligned(gy)
-            floats = int(_lib.lib.mlgnn_gat_bwd_workspace_floats(N, E, H, C))
-            ws = torch.empty(max(floats, 1), **f32)
+            ws, floats = _lib.workspace("mlgnn_gat_bwd_workspace_floats", N, E, H, C, device=z.device)
             _lib.call("mlgnn_gat_aggregate_bwd", gy, y, z, a_src, a_dst, lse, att_s, att_d, b, g.rowptr, g.rowptr_t,
                       g.col_t, g.pos_t, gz, gs, gd, gb, ws, floats, N, E, H, C, neg, act, _lib.stream())
         return (gz, gs.reshape(shape_s) if need_s else None, gd.reshape(shape_d) if need_d else None,

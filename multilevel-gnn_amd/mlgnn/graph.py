@@ -148,7 +148,7 @@ class CSRGraph:
             self.hub_tables("src" if direction == "dst" else "dst")
             del self._hub[direction]
         if hit is None:
-            cap_rows = int(_lib.lib.mlgnn_hub_capacity(self.num_edges, cap))
+            cap_rows = _lib.size("mlgnn_hub_capacity", self.num_edges, cap)
             i32 = dict(dtype=torch.int32, device=self.device)
             vrows, hubs, counts = torch.empty((cap_rows, 3), **i32), torch.empty((cap_rows, 3), **i32), torch.empty(2, **i32)
             rowptr = self.rowptr if direction == "dst" else self.rowptr_t
@@ -189,8 +189,7 @@ class CSRGraph:
         if tabs[6] is False:
             return None, ()                               # no row longer than HUB_CAP in this direction
         vrows, hubs, counts, cap_rows = tabs[:4]
-        nbytes = int(_lib.lib.mlgnn_hub_scratch_bytes(cap_rows, d))
-        tmp = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        tmp, nbytes = _lib.workspace("mlgnn_hub_scratch_bytes", cap_rows, d, device=self.device)
         st = _lib.HubStruct(getattr(self, "hub_cap", HUB_CAP), cap_rows, vrows.data_ptr(), hubs.data_ptr(), counts.data_ptr(), tmp.data_ptr(), nbytes)
         return ctypes.byref(st), (st, tmp)
 
@@ -202,8 +201,7 @@ class CSRGraph:
         self.rowptr, self.rowptr_t = torch.empty(N + 1, **i32), torch.empty(N + 1, **i32)
         self.col, self.eid = torch.empty(E, **i32), torch.empty(E, **i32)
         self.col_t, self.pos_t, self.eid_t = torch.empty(E, **i32), torch.empty(E, **i32), torch.empty(E, **i32)
-        nbytes = int(_lib.lib.mlgnn_coo_to_csr_workspace_bytes(N, E))
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        ws, nbytes = _lib.workspace("mlgnn_coo_to_csr_workspace_bytes", N, E, device=dev)
         self._bad_ids = torch.empty(1, **i32)               # cleared by the build itself
         _lib.call("mlgnn_coo_to_csr", ei, E, N, self.rowptr, self.col, self.eid, self.rowptr_t, self.col_t, self.pos_t,
                   self.eid_t, self._bad_ids, ws, nbytes, _lib.stream())

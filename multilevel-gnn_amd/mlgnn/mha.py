@@ -51,8 +51,7 @@ class _MhaAttention(torch.autograd.Function):
         B, P, H, D, keep_scale = ctx.cfg
         go = _aligned(go)
         gqkv = torch.empty_like(qkv)
-        floats = int(_lib.lib.mlgnn_mha_bwd_workspace_floats(B, P, H, D))
-        ws = torch.empty(floats, dtype=torch.float32, device=qkv.device) if floats > 0 else None
+        ws, floats = _lib.workspace("mlgnn_mha_bwd_workspace_floats", B, P, H, D, device=qkv.device)
         _lib.call("mlgnn_mha_bwd", go, qkv, out, lse, ctx.keep, keep_scale, gqkv, ws, floats, B, P, H, D, _lib.stream())
         return gqkv, None, None, None, None
 

@@ -66,8 +66,7 @@ def _ln_bwd(go, x, weight, bias, mean, rstd, relu, extra=None, keep=None, keep_s
     gx = torch.empty_like(x)
     ggb = torch.empty((2, d), dtype=torch.float32, device=x.device)
     dt = _DTYPE_IDS[x.dtype]
-    n = int(_lib.lib.mlgnn_layernorm_bwd_workspace_floats(rows, d, dt))
-    ws = torch.empty(n, dtype=torch.float32, device=x.device)
+    ws, n = _lib.workspace("mlgnn_layernorm_bwd_workspace_floats", rows, d, dt, device=x.device)
     row_max = torch.empty(rows, dtype=torch.float32, device=x.device) if x.dtype == torch.float32 else None
     _lib.call("mlgnn_layernorm_act_bwd", go, x, weight, bias, mean, rstd, extra, gx, row_max, ggb, ws, n, keep,
               keep_scale, rows, d, int(relu), dt, _lib.stream())
@@ -164,8 +163,7 @@ class _MsgNormAdd(torch.autograd.Function):
         gh = gh.contiguous()
         gx, gm = torch.empty_like(x), torch.empty_like(m)
         gs = torch.empty(1, dtype=torch.float32, device=x.device)
-        n = int(_lib.lib.mlgnn_msgnorm_bwd_workspace_floats(rows, d))
-        ws = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
+        ws, n = _lib.workspace("mlgnn_msgnorm_bwd_workspace_floats", rows, d, device=x.device)
         _lib.call("mlgnn_msgnorm_add_bwd", gh, x, m, scale, gx, gm, gs, ws, n, rows, d, _DTYPE_IDS[x.dtype],
                   _lib.stream())
         return gx, gm, (gs.to(ctx.scale_dtype) if ctx.needs_input_grad[2] else None)

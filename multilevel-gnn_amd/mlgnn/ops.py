@@ -533,8 +533,8 @@ class _GenAggregate(torch.autograd.Function):
             # the cotangent through the outer power and the mean (and d loss / dp): one streaming pass (csrc/power.hip)
             go_k = torch.empty_like(go)
             gp = torch.empty(1, dtype=torch.float32, device=x.device) if learn_p else None
-            pw_n = int(_lib.lib.mlgnn_power_bwd_prologue_workspace_floats())
-            pw_ws = torch.empty(pw_n, dtype=torch.float32, device=x.device) if learn_p else None
+            pw_ws, pw_n = (_lib.workspace("mlgnn_power_bwd_prologue_workspace_floats", device=x.device) if learn_p
+                           else (None, 0))                   # (the partial sums of d loss / dp are its only use)
             _lib.call("mlgnn_power_bwd_prologue", go, aux, g.rowptr, out if learn_p else None,
                       aux2 if learn_p else None, float(p), p_dev, go_k, gp, pw_ws, pw_n, N, d, _DTYPE_IDS[x.dtype],
                       _lib.stream())
@@ -552,7 +552,7 @@ class _GenAggregate(torch.autograd.Function):
         route = _edge_grad_route(ctx, x, argmax, go_k)       # chosen once: the ROUTE_* list below, in order of precedence
         ge = guv = None
         if route == ROUTE_WINNERS:
-            _max_winners_backward(go_k, argmax, g, gx, add_root, te, sink)          # (no KERNEL_TIMER record)
+            _max_winners_backward(go_k, argmax, g, gx, add_root, te, sink, ctx.winner_records)   # (no KERNEL_TIMER record)
         else:
             gx, ge, guv = _gather_backward(ctx, saved, route, go_k, gx, shifted)
         geu, gev = (guv[:ctx.uv_rows].to(ctx.uv_dtype), guv[rank].to(ctx.uv_dtype)) if guv is not None else (None, None)
@@ -585,7 +585,9 @@ def _edge_grad_route(ctx, x, argmax, go_k):
     # the edge reads -- through compact per-edge runs of (value, channel) pairs instead of whole gathered rows
     if (SPARSE_MAX and aligned and ctx.post_ln is None and g.num_edges > 0
             and (edge_mode == EDGE_NONE or (edge_mode == EDGE_FULL and te is not None and TABLE_DEST))
-            and int(_lib.lib.mlgnn_max_sparse_records(N, d, g.num_edges)) > 0 and g.known_short_rows()):
+            and (records := _lib.size("mlgnn_max_sparse_records", N, d, g.num_edges, or_none=True))
+            and g.known_short_rows()):
+        ctx.winner_records = records                     # (the size of the route's winner list, asked once)
         return ROUTE_WINNERS
     if TABLE_DEST and table_wants_grad and aligned and d % 4 == 0:
         streamed = bool(_lib.lib.mlgnn_max_table_grad_supported(N, d, te.table_rows))
@@ -602,17 +604,16 @@ def _streamed_table_grad(go_k, argmax, g, te, sink):
     T = te.table_rows
     total, accumulate = sink.table_total(T, d, go_k.device)
     rows_dst = te.rows_for(g)[0]
-    mt_n = int(_lib.lib.mlgnn_max_table_grad_workspace_floats(N, d, T))
-    mt_ws = torch.empty(mt_n, dtype=torch.float32, device=go_k.device)
+    mt_ws, mt_n = _lib.workspace("mlgnn_max_table_grad_workspace_floats", N, d, T, device=go_k.device)
     _lib.call("mlgnn_max_table_grad", go_k, argmax, rows_dst, total, mt_ws, mt_n, N, d, T, accumulate, _lib.stream())
     TABLE_DEST_STATS["streamed"] += 1
 
 
-def _max_winners_backward(go_k, argmax, g, gx, add_root, te, sink):
-    """ROUTE_WINNERS: ``gx`` -- and the table's gradient, if the table wants one -- from compact winner lists
-    (csrc/max_sparse.hip) instead of the row-gather kernel."""
+def _max_winners_backward(go_k, argmax, g, gx, add_root, te, sink, records):
+    """ROUTE_WINNERS: ``gx`` -- and the table's gradient, if the table wants one -- from compact winner lists of
+    ``records`` (``mlgnn_max_sparse_records``) pairs (csrc/max_sparse.hip) instead of the row-gather kernel."""
     (N, d), dev = go_k.shape, go_k.device
-    recs = torch.empty((int(_lib.lib.mlgnn_max_sparse_records(N, d, g.num_edges)), 2), dtype=torch.int32, device=dev)
+    recs = torch.empty((records, 2), dtype=torch.int32, device=dev)
     meta = torch.empty((g.num_edges, 2), dtype=torch.int32, device=dev)
     _lib.call("mlgnn_max_winners", go_k, argmax, g.rowptr, recs, meta, N, d, _lib.stream())
     _lib.call("mlgnn_max_sparse_bwd", recs, meta, g.rowptr_t, g.pos_t, go_k if add_root else None, gx, N, d,
@@ -634,21 +635,21 @@ def _max_winners_backward(go_k, argmax, g, gx, add_root, te, sink):
 def _fixed_point_begin(go_k, te, sink):
     """ROUTE_TABLE_FIXED, before the kernel: the fixed-point accumulator (kept on the sink), scaled for this cotangent."""
     N, d = go_k.shape
-    nbytes = int(_lib.lib.mlgnn_table_grad_bytes(te.table_rows, d))
+    nbytes = _lib.size("mlgnn_table_grad_bytes", te.table_rows, d)
     if sink.fix is None or sink.fix.numel() != nbytes:
         sink.fix = torch.zeros(nbytes, dtype=torch.uint8, device=go_k.device)
     _lib.call("mlgnn_table_grad_begin", go_k, N, d, sink.fix, _lib.stream())
     return sink.fix
 
 
-def _by_type_table_grad(go_k, argmax, g, te, sink, ws, rank):
+def _by_type_table_grad(go_k, argmax, g, te, sink, ws, ws_n, rank):
     """ROUTE_TABLE_BY_TYPE, behind the backward kernel (it reads that call's winner slots in ``ws``): one row per KEGG
     membership (tens of thousands) -- a wavefront per table row gathers its edges' winners."""
     N, d = go_k.shape
     total, accumulate = sink.table_total(te.table_rows, d, go_k.device)
     pos_s, dst_s, rp_s, rel_s = te.winners_by_type(g)
-    off = int(_lib.lib.mlgnn_csr_aggregate_bwd_slots_offset_floats(N, d, rank))
-    slots = ws.data_ptr() + 4 * off if (ws is not None and off >= 0 and TABLE_SLOTS) else None
+    off = _lib.size("mlgnn_csr_aggregate_bwd_slots_offset_floats", N, d, rank, or_none=True)
+    slots = ws.data_ptr() + 4 * off if (ws_n > 0 and off is not None and TABLE_SLOTS) else None
     _lib.call("mlgnn_max_table_grad_by_type", go_k, argmax, dst_s, pos_s, rel_s, rp_s, slots, total, N, d,
               te.table_rows, accumulate, _lib.stream())
     TABLE_DEST_STATS["by_type"] += 1
@@ -661,8 +662,8 @@ def _ln_fold_backward(tag, x, gx, launch):
     tag.claim()
     N, d = x.shape
     f32 = dict(dtype=torch.float32, device=x.device)
-    ln_n = int(_lib.lib.mlgnn_csr_aggregate_bwd_ln_workspace_floats(N, d))
-    ln_ws, ggb, row_max = torch.empty(ln_n, **f32), torch.empty((2, d), **f32), torch.empty(N, **f32)
+    ln_ws, ln_n = _lib.workspace("mlgnn_csr_aggregate_bwd_ln_workspace_floats", N, d, device=x.device)
+    ggb, row_max = torch.empty((2, d), **f32), torch.empty(N, **f32)
     extra = tag.extra if (tag.extra is not None and tag.extra.dtype == torch.float32
                           and tag.extra.shape == x.shape and tag.extra.is_contiguous()) else None
     gamma, beta = f32_cached(tag.gamma), f32_cached(tag.beta)
@@ -699,10 +700,8 @@ def _gather_backward(ctx, saved, route, go_k, gx, shifted):
         ge = torch.empty((g.num_edges, d), dtype=efull.dtype, device=efull.device)
         if sink is not None:
             sink.buf = ge
-    ws_n = int(_lib.lib.mlgnn_csr_aggregate_bwd_workspace_floats(
-        N, d, _DTYPE_IDS[x.dtype], rank, AGGR_SUM if shifted is not None else aggr_id, int(learn_t)))
-    _lib.check(min(ws_n, 0), "mlgnn_csr_aggregate_bwd_workspace_floats")
-    ws = torch.empty(ws_n, dtype=torch.float32, device=x.device) if ws_n > 0 else None
+    ws, ws_n = _lib.workspace("mlgnn_csr_aggregate_bwd_workspace_floats", N, d, _DTYPE_IDS[x.dtype], rank,
+                              AGGR_SUM if shifted is not None else aggr_id, int(learn_t), device=x.device)
     guv = torch.empty((rank + 1, d), dtype=torch.float32, device=x.device) if edge_mode == EDGE_RANK1 else None
     timer = KERNEL_TIMER
     t0 = timer.start() if timer is not None else None
@@ -720,7 +719,7 @@ def _gather_backward(ctx, saved, route, go_k, gx, shifted):
         launch(hub=hub)
     del hub_keep
     if route == ROUTE_TABLE_BY_TYPE:
-        _by_type_table_grad(go_k, argmax, g, te, sink, ws, rank)
+        _by_type_table_grad(go_k, argmax, g, te, sink, ws, ws_n, rank)
     if route == ROUTE_TABLE_FIXED:
         total, accumulate = sink.table_total(te.table_rows, d, x.device)
         _lib.call("mlgnn_table_grad_finish", sink.fix, total, te.table_rows, d, accumulate, _lib.stream())

@@ -49,7 +49,7 @@ class FlatAdam:
         self.param_groups = [dict(lr=lr, initial_lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)]
         self.clip = float(clip_grad_norm) if clip_grad_norm else 0.0
         self.step_count = 0
-        self._ws = torch.zeros(int(_lib.lib.mlgnn_adam_workspace_floats()), dtype=torch.float32, device=dev) \
+        self._ws = torch.zeros(_lib.size("mlgnn_adam_workspace_floats"), dtype=torch.float32, device=dev) \
             if dev.type == "cuda" else None
         self._offsets = torch.tensor(offs, dtype=torch.int64, device=dev)
 

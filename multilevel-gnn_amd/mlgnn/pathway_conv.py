@@ -123,8 +123,7 @@ class _PathwayAggregate(torch.autograd.Function):
         gy = torch.empty_like(y)
         gb = torch.empty(d, **f32) if need_b else None
         gt = torch.empty(1, **f32) if learn_t else None
-        floats = int(_lib.lib.mlgnn_pathway_conv_bwd_workspace_floats(N, E, R, d, int(learn_t)))
-        ws = torch.empty(max(floats, 1), **f32)
+        ws, floats = _lib.workspace("mlgnn_pathway_conv_bwd_workspace_floats", N, E, R, d, int(learn_t), device=y.device)
         _lib.call("mlgnn_pathway_conv_bwd", go, y, out, b, winner, lse, g.rowptr_t, g.col_t, g.pos_t, topo.attr_src,
                   topo.row_of, gy, gb, gt, ws, floats, N, E, R, d, aggr_id, t_imm, t_dev, int(learn_t), _lib.stream())
         STATS["bwd"] += 1

@@ -18,8 +18,7 @@ class _SegmentPool(torch.autograd.Function):
         B = ptr.numel() - 1
         out = torch.empty((B, d), dtype=torch.float32, device=x.device)
         argmax = torch.empty((B, d), dtype=torch.int32, device=x.device) if kind == 2 else None
-        nbytes = int(_lib.lib.mlgnn_segment_pool_workspace_bytes(B, d))
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+        ws, nbytes = _lib.workspace("mlgnn_segment_pool_workspace_bytes", B, d, device=x.device)
         _lib.call("mlgnn_segment_pool_fwd", x, ptr, out, argmax, ws, nbytes, B, d, kind, DTYPE_F32, _lib.stream())
         ctx.kind, ctx.shape = kind, (N, d)
         ctx.save_for_backward(ptr, batch, argmax)

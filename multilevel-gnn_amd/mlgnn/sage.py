@@ -18,7 +18,7 @@ the aggregation's transpose, ``dx = dz W_x + (that)`` (tall GEMM, the sum in its
 import torch
 
 from . import _lib
-from .dense import WGRAD_MIN_ROWS, _aligned, _wgrad, tall_matmul_nt, tall_matmul_supported
+from .dense import WGRAD_MIN_ROWS, _aligned, _wgrad, tall_matmul_nt, tall_matmul_supported, wgrad_supported
 from .ops import AGGR_MEAN, AGGR_SUM, MSG_IDENTITY, MSG_WEIGHTED, _aggregate_bwd, _aggregate_fwd
 from .tags import tag_row_max
 
@@ -36,7 +36,7 @@ def sage_layer_supported(x, w_nn, w_r, has_conv_bias):
     if w_nn.shape[1] != cin + cout or tuple(w_r.shape) != (cout, cin) or w_nn.dtype != torch.float32:
         return False
     return (bool(_lib.lib.mlgnn_tallgemm_dual_supported(n, cin, cin, cout))
-            and tall_matmul_supported(n, cout, cin) and _lib.lib.mlgnn_linear_wgrad_workspace_floats(n, cout, cin, 0) > 0)
+            and tall_matmul_supported(n, cout, cin) and wgrad_supported(n, cout, cin))
 
 
 class _SageLayer(torch.autograd.Function):
@@ -61,8 +61,7 @@ class _SageLayer(torch.autograd.Function):
         y = torch.empty((N, cout), dtype=torch.float32, device=dev)
         y_max = torch.empty(N, dtype=torch.float32, device=dev)
         a_max = torch.empty(N, dtype=torch.float32, device=dev)
-        nbytes = int(_lib.lib.mlgnn_tallgemm_workspace_bytes(2 * cin, cout, 0))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws, nbytes = _lib.workspace("mlgnn_tallgemm_workspace_bytes", 2 * cin, cout, 0, device=dev)
         bias = b_nn.contiguous() if b_nn is not None else None
         rs = row_scale.reshape(-1).contiguous() if row_scale is not None else None
         _lib.call("mlgnn_tallgemm_dual", x, agg, w_cat, bias, float(slope), rs, y, y_max, a_max, ws, nbytes, N, cin,
@@ -176,8 +175,7 @@ class _LinearAct(torch.autograd.Function):
         y = torch.empty((N, J), dtype=torch.float32, device=x.device)
         y_max = torch.empty(N, dtype=torch.float32, device=x.device)
         a_max = torch.empty(N, dtype=torch.float32, device=x.device)
-        nbytes = int(_lib.lib.mlgnn_tallgemm_workspace_bytes(R, J, 0))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        ws, nbytes = _lib.workspace("mlgnn_tallgemm_workspace_bytes", R, J, 0, device=x.device)
         bias = b.contiguous() if b is not None else None
         _lib.call("mlgnn_tallgemm_dual", x, None, w, bias, float(slope), None, y, y_max, a_max, ws, nbytes, N, R, 0, J,
                   _lib.stream())
@@ -207,7 +205,7 @@ def linear_act_supported(x, w):
     n, r = x.shape
     j = w.shape[0]
     return (bool(_lib.lib.mlgnn_tallgemm_dual_supported(n, r, 0, j)) and tall_matmul_supported(n, j, r)
-            and _lib.lib.mlgnn_linear_wgrad_workspace_floats(n, j, r, 0) > 0)
+            and wgrad_supported(n, j, r))
 
 
 def linear_act(x, w, b, slope):

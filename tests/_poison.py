@@ -64,6 +64,9 @@ class Log:
 
     def note(self, frame):
         self.count += 1
+        # the one workspace allocation of the binding (mlgnn._lib.workspace) counts for the line that asked for it
+        while frame.f_globals.get("__name__") == "mlgnn._lib" and frame.f_back is not None:
+            frame = frame.f_back
         module = frame.f_globals.get("__name__", "")
         if module == "mlgnn" or module.startswith("mlgnn."):
             self.sites.add((module, frame.f_lineno))
@@ -108,14 +111,16 @@ def poisoned(float_fill, int_fill, device=on_device, log=None):
 
 
 def empty_call_lines(source):
-    """The lines of ``source`` that hold a call to ``torch.empty``, ``torch.empty_like`` or ``<anything>.new_empty``,
-    sorted, each once.  The line is the one of the called name -- where the interpreter reports a call that spans lines."""
+    """The lines of ``source`` that hold a call to ``torch.empty``, ``torch.empty_like``, ``<anything>.new_empty`` or
+    ``_lib.workspace`` (whose ``torch.empty`` :meth:`Log.note` records at its caller), sorted, each once.  The line is the
+    one of the called name -- where the interpreter reports a call that spans lines."""
     lines = set()
     for node in ast.walk(ast.parse(source)):
         if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute)):
             continue
         f = node.func
-        if f.attr == "new_empty" or (f.attr in ("empty", "empty_like") and isinstance(f.value, ast.Name)
-                                     and f.value.id == "torch"):
+        owner = f.value.id if isinstance(f.value, ast.Name) else None
+        if f.attr == "new_empty" or (f.attr in ("empty", "empty_like") and owner == "torch") \
+                or (f.attr == "workspace" and owner == "_lib"):
             lines.add(f.end_lineno)
     return sorted(lines)

@@ -138,6 +138,39 @@ def test_call_sites_inside_the_package_are_recorded(monkeypatch):
     assert again.count == 12 and again.sites == log.sites
 
 
+_FIXTURE_WS = '''from mlgnn import _lib
+
+
+def work(n):
+    ws, size = _lib.workspace("mlgnn_fixture_workspace_floats", n,
+                              device="cpu")
+    other = workspace(n)                     # not a site
+    return ws, size, other, _lib.size("mlgnn_fixture_workspace_floats", n)      # nor this
+
+
+def workspace(n):
+    return None
+'''
+
+
+def test_workspace_calls_are_sites_recorded_at_the_caller_of_the_binding(monkeypatch):
+    """``_lib.workspace`` allocates inside ``mlgnn._lib``: the scan names the line of the call to it, and the log walks up
+    from the binding's frame to that same line -- never to a line of ``mlgnn._lib`` itself."""
+    from mlgnn import _lib
+    assert empty_call_lines(_FIXTURE_WS) == [5]
+    monkeypatch.setattr(_lib.lib, "mlgnn_fixture_workspace_floats", lambda n: 2 * n, raising=False)
+    mod = types.ModuleType("mlgnn._fixture_ws")
+    exec(compile(_FIXTURE_WS, "mlgnn/_fixture_ws.py", "exec"), mod.__dict__)
+    monkeypatch.setitem(sys.modules, "mlgnn._fixture_ws", mod)
+    with poisoned(float("nan"), 1, device=ALWAYS) as log:
+        ws, size, _, asked = mod.work(3)
+    assert (size, asked, ws.numel(), ws.dtype) == (6, 6, 6, torch.float32) and bool(torch.isnan(ws).all())
+    assert log.count == 1 and log.sites == {("mlgnn._fixture_ws", 5)}
+    with poisoned(float("nan"), 1, device=ALWAYS) as log:       # straight from a test: counted, no site inside the package
+        _lib.workspace("mlgnn_fixture_workspace_floats", 1, device="cpu")
+    assert log.count == 1 and log.sites == set()
+
+
 def test_package_scan_finds_the_allocation_surface():
     """The real package: every module that allocates is found, and the known host allocation is among the lines."""
     import os

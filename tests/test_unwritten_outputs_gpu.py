@@ -1567,8 +1567,6 @@ def test_poisoned_runs_agree(name, monkeypatch):
 # needs more than one GPU; behind a switch that not even monkeypatch.setattr on the module can flip.
 UNREACHED = {
     ("mlgnn.graph", 158): "pinned host memory: the asynchronous copy of the hub counts",
-    ("mlgnn.mha", 55): "behind `floats > 0`, and the library asks for no backward workspace at any shape it supports "
-                       "(mlgnn_mha_bwd_workspace_floats returns 0): no switch of the module leads there",
 }
 
 
@@ -1577,7 +1575,8 @@ def _package_sites():
     found = set()
     for info in pkgutil.iter_modules(mlgnn.__path__):
         path = os.path.join(os.path.dirname(mlgnn.__file__), info.name + ".py")
-        if os.path.exists(path):
+        # (mlgnn._lib: its one torch.empty, in workspace(), is recorded at -- and scanned as -- each line that calls it)
+        if os.path.exists(path) and info.name != "_lib":
             with open(path) as fh:
                 found.update(("mlgnn." + info.name, line) for line in empty_call_lines(fh.read()))
     return found
