@@ -287,6 +287,19 @@ def stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def aligned(t):
+    """``t`` (``None`` stays ``None``) as a kernel operand: contiguous and on a 16-byte boundary.  :func:`call` passes
+    ``data_ptr()`` and nothing else, and the kernels read their operands with 16-byte loads; most entry points answer
+    ``MLGNN_E_ALIGN`` for anything else.  A contiguous tensor on a boundary -- every fresh allocation, every slot of
+    mlgnn.optim.FlatAdam -- is returned as it is (one ``data_ptr()`` on the host); a strided view is copied by
+    ``contiguous()``, a contiguous view at an odd offset of somebody's flat buffer (``flat[1:1 + n].view(...)``) is
+    cloned once."""
+    if t is None:
+        return None
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 def call(name, *args):
     """Launch the status-returning entry point ``name``: every tensor goes in as its address (``None`` as NULL), anything
     else unchanged; a non-zero status raises :class:`MlgnnError`.  A tensor a kernel cannot read (neither on the device nor

@@ -39,8 +39,9 @@ class _Conv2d(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xr, weight, bias, relu):
-        xr, weight = xr.contiguous(), weight.contiguous()
-        bias = bias.contiguous() if bias is not None else None
+        xr, weight = _lib.aligned(xr), _lib.aligned(weight)
+        # (a bias of another type is cast, never reinterpreted; conv2d_supported holds x and weight to fp32)
+        bias = _lib.aligned(bias.detach().to(torch.float32)) if bias is not None else None
         B, H, W, Cin = xr.shape
         Cout, k = weight.shape[0], weight.shape[2]
         y = torch.empty((B, H, W, Cout), dtype=torch.float32, device=xr.device)
@@ -58,7 +59,7 @@ class _Conv2d(torch.autograd.Function):
         need_b = has_bias and ctx.needs_input_grad[2]
         if not (need_x or need_w or need_b):
             return None, None, None, None
-        gy = gy.contiguous()
+        gy = _lib.aligned(gy)
         f32 = dict(dtype=torch.float32, device=xr.device)
         gx = torch.empty_like(xr) if need_x else None
         gw = torch.empty_like(weight) if need_w else None

@@ -75,7 +75,7 @@ class _Criterion(torch.autograd.Function):
         pred, y, cw, feat, stats, terms = ctx.saved_tensors
         B = pred.shape[0]
         M = 0 if feat is None else feat.shape[1]
-        grad_loss = grad_loss.to(torch.float32).contiguous()
+        grad_loss = _lib.aligned(grad_loss.to(torch.float32))
         grad_pred = torch.empty_like(pred) if want_pred else None
         grad_feat = torch.empty_like(feat) if want_feat else None
         _lib.call("mlgnn_criterion_bwd", pred, y, cw, cw_rows, feat, stats, terms, grad_loss, coef, mode, grad_pred,
@@ -97,7 +97,7 @@ def train_criterion(pred, y, feat=None, pca_loss_coef=0.0, mode="plain", class_w
                          "with B >= 2 rows, < 4 GiB)" % (tuple(pred.shape), pred.dtype,
                                                          None if feat is None else (tuple(feat.shape), feat.dtype)))
     B = pred.shape[0]
-    pred = pred.to(torch.float32).contiguous()
+    pred = _lib.aligned(pred.to(torch.float32))
     y = torch.as_tensor(y, device=pred.device).detach().reshape(-1, 2).to(torch.float32).contiguous()
     if y.shape[0] != B:
         raise ValueError("train_criterion: y holds %d rows, pred %d" % (y.shape[0], B))
@@ -110,7 +110,7 @@ def train_criterion(pred, y, feat=None, pca_loss_coef=0.0, mode="plain", class_w
         if not (tuple(cw.shape) == (2,) or rows_ok):
             raise ValueError("train_criterion: class_weight %s does not fit mode %r at B = %d" % (tuple(cw.shape), mode, B))
     if feat is not None:
-        feat = feat.contiguous().reshape(B, -1)
+        feat = _lib.aligned(feat).reshape(B, -1)
     grad = torch.is_grad_enabled()
     want = (grad and pred.requires_grad, grad and feat is not None and feat.requires_grad)
     loss, terms = _Criterion.apply(pred, y, cw, feat, float(pca_loss_coef), MODES[mode], want)

@@ -86,7 +86,7 @@ class _Decoder(torch.autograd.Function):
             return (None,) * 9
         h, w1, b1, w2, hid_off, out_off, w2_off = ctx.saved_tensors
         B, P, H = h.shape
-        g = g.to(torch.float32).contiguous()
+        g = _lib.aligned(g.to(torch.float32))
         like = (h, w1, b1, w2)
         grads = [torch.empty_like(like[i]) if needs[i] else None for i in range(4)]
         grads.append(torch.empty(ctx.b2_shape, dtype=torch.float32, device=h.device) if needs[4] else None)
@@ -119,5 +119,5 @@ def pathway_decoders(h, w1, b1, w2, b2, hid_off, out_off, w2_off, limits=None):
     if b2.numel() != limits[2] or w1.numel() != b1.numel() * H or w2.numel() > limits[2] * limits[0]:
         raise ValueError("pathway_decoders: packed parameter sizes %s do not match the tables (N = %d, H = %d)"
                          % ([t.numel() for t in params], limits[2], H))
-    w1, b1, w2, b2 = (t.reshape(-1).contiguous() for t in params)
-    return _Decoder.apply(h.contiguous(), w1, b1, w2, b2, *(t.contiguous() for t in tables), limits)
+    w1, b1, w2, b2 = (_lib.aligned(t.reshape(-1)) for t in params)
+    return _Decoder.apply(_lib.aligned(h), w1, b1, w2, b2, *(_lib.aligned(t) for t in tables), limits)

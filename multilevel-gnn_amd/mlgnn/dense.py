@@ -18,8 +18,7 @@ ROW_MAX_STATS = {"given": 0, "computed": 0}      # tall GEMMs whose operand came
 def _aligned(t):
     """Contiguous and on a 16-byte boundary (the kernels read operands with 16-byte loads): a view at an odd offset of
     somebody's flat buffer is copied once (mlgnn.optim.FlatAdam aligns its slots, so its views never are)."""
-    t = t.contiguous()
-    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+    return _lib.aligned(t)
 
 
 def tall_matmul_nt(a, bt, bias=None, residual=None, row_max=None, ln=None, bt_transposed=False):
@@ -37,8 +36,7 @@ def tall_matmul_nt(a, bt, bias=None, residual=None, row_max=None, ln=None, bt_tr
     dt = _DTYPE_IDS[a.dtype]
     out = torch.empty((N, J), dtype=a.dtype, device=a.device)
     ws, nbytes = _lib.workspace("mlgnn_tallgemm_workspace_bytes", R, J, dt, device=a.device)
-    if residual is not None:
-        residual = residual.contiguous()
+    residual = _aligned(residual)
     if bias is not None:
         bias = f32_cached(bias)                          # [J]; the kernels add it in fp32
     if a.dtype == torch.float32:
@@ -46,7 +44,7 @@ def tall_matmul_nt(a, bt, bias=None, residual=None, row_max=None, ln=None, bt_tr
     mode, gamma, beta, eps, rstd, rmax = 0, None, None, 0.0, None, None
     if ln is not None:
         mode = 1 if ln[0] == "out" else 2
-        gamma, beta = ln[1].contiguous(), ln[2].contiguous()
+        gamma, beta = f32_cached(ln[1]), f32_cached(ln[2])
         if mode == 1:
             eps = float(ln[3])
             rstd = torch.empty(N, dtype=torch.float32, device=a.device)
@@ -67,14 +65,13 @@ def tall_matmul_lnin_postln(xhat, w, bias, residual, row_max, gamma, beta, post)
     out, y = torch.empty((N, J), **f32), torch.empty((N, J), **f32)
     mean, rstd = torch.empty(N, **f32), torch.empty(N, **f32)
     ws, nbytes = _lib.workspace("mlgnn_tallgemm_workspace_bytes", R, J, 0, device=xhat.device)
-    if residual is not None:
-        residual = residual.contiguous()
+    residual = _aligned(residual)
     if bias is not None:
         bias = f32_cached(bias)
     ROW_MAX_STATS["given" if row_max is not None else "computed"] += 1
     g2, b2, eps2, relu = post
-    _lib.call("mlgnn_tallgemm_lnin_postln", xhat, w, bias, residual, row_max, gamma.contiguous(), beta.contiguous(),
-              g2.contiguous(), b2.contiguous(), float(eps2), int(bool(relu)), out, y, mean, rstd, ws, nbytes, N, R, J,
+    _lib.call("mlgnn_tallgemm_lnin_postln", xhat, w, bias, residual, row_max, f32_cached(gamma), f32_cached(beta),
+              f32_cached(g2), f32_cached(b2), float(eps2), int(bool(relu)), out, y, mean, rstd, ws, nbytes, N, R, J,
               _lib.stream())
     return out, y, mean, rstd
 
@@ -102,7 +99,7 @@ def tall_matmul_bf16_shift(go, weight, lse):
     ``-> (gx, gx * 2^(-lse), flag)``."""
     N, M = go.shape
     K = weight.shape[1]
-    go, bt = go.contiguous(), weight.t().contiguous()             # [K, M]: the contraction index contiguous
+    go, bt = _aligned(go), weight.t().contiguous()             # [K, M]: the contraction index contiguous
     gx = torch.empty((N, K), dtype=torch.bfloat16, device=go.device)
     gt = torch.empty_like(gx)
     flag = torch.empty(4, dtype=torch.int32, device=go.device)
@@ -123,7 +120,7 @@ def tall_matmul_ln_backward(go, w, xhat, rstd, gamma, beta, row_max=None):
     rmax = torch.empty(N, dtype=torch.float32, device=go.device)
     ws, nbytes = _lib.workspace("mlgnn_tallgemm_lnbwd_workspace_bytes", R, J, device=go.device)
     ROW_MAX_STATS["given" if row_max is not None else "computed"] += 1
-    _lib.call("mlgnn_tallgemm_lnbwd", go, w, 1, row_max, xhat, rstd, gamma.contiguous(), beta.contiguous(), gh, rmax,
+    _lib.call("mlgnn_tallgemm_lnbwd", go, w, 1, row_max, xhat, rstd, f32_cached(gamma), f32_cached(beta), gh, rmax,
               ggb, ws, nbytes, N, R, J, _lib.stream())
     return gh, ggb[0], ggb[1], rmax
 
@@ -162,7 +159,7 @@ def linear_backward(go, w, x, go_max, x_max, epilogue, rstd=None, gamma=None, be
     flag = torch.empty(4, dtype=torch.int32, device=go.device) if epilogue == LB_SHIFT else None
     ws, n = _lib.workspace("mlgnn_linear_bwd_workspace_floats", N, M, K, epilogue, device=go.device)
     if gamma is not None:
-        gamma, beta = gamma.contiguous(), beta.contiguous()
+        gamma, beta = f32_cached(gamma), f32_cached(beta)
     _lib.call("mlgnn_linear_bwd", go, w, x, go_max, int(go_max_is_parts), x_max, epilogue, rstd, gamma, beta, lse, dx,
               gt, flag, gwb, parts, ws, n, N, M, K, _lib.stream())
     out = dict(dx=dx, gw=gwb[:M * K].view(M, K), gb=gwb[M * K:M * K + M], parts=parts, gt=gt, flag=flag)
@@ -194,6 +191,9 @@ def _wgrad(go, x, x_gamma=None, x_beta=None, go_max=None, x_max=None, out_dtype=
     three-way bf16 split."""
     N, K = x.shape
     M = go.shape[1]
+    go, x = _aligned(go), _aligned(x)
+    if x_gamma is not None:
+        x_gamma, x_beta = f32_cached(x_gamma), f32_cached(x_beta)
     dt = _DTYPE_IDS[x.dtype]
     ws, n = _lib.workspace("mlgnn_linear_wgrad_workspace_floats", N, M, K, dt, device=x.device)
     out = torch.empty(M * K + M, dtype=torch.float32, device=x.device)          # fp32 for either storage type
@@ -223,7 +223,7 @@ class _TallLinear(torch.autograd.Function):
         if tall_matmul_supported(x.shape[0], x.shape[1], weight.shape[0], x.dtype):
             # fp32: the kernel holds the residual tile in registers (<= 128 columns); bf16: any width
             fuse = residual is not None and (weight.shape[0] <= 128 or x.dtype == torch.bfloat16)
-            out = tall_matmul_nt(x, weight, bias.contiguous() if bias is not None else None, residual if fuse else None,
+            out = tall_matmul_nt(x, weight, bias, residual if fuse else None,
                                  row_max_of(x))
             return out if (residual is None or fuse) else out + residual
         # addmm on the transposed view picks a faster library kernel than F.linear for these tall
@@ -234,7 +234,7 @@ class _TallLinear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, go):
         x, weight = ctx.saved_tensors
-        go = go.contiguous()
+        go = _aligned(go)
         N, K = x.shape
         M = weight.shape[0]
         gx = None
@@ -283,7 +283,7 @@ class _FusedMLP2(torch.autograd.Function):
         # backward instead of being returned (mlgnn.tags.PostLN)
         ctx.res_tag = getattr(residual, "_mlgnn_post_ln_of", None) if (ops.LN_FOLD and residual is not None) else None
         ctx.post_tag = None
-        x = x.contiguous()
+        x = _aligned(x)
         xhat, rstd, rmax = tall_matmul_nt(x, w1, b1, None, row_max_of(x), ln=("out", gamma, beta, eps))
         fuse = residual is not None and w2.shape[0] <= 128
         ctx.post = post_gamma is not None
@@ -347,7 +347,7 @@ class _FusedMLP2(torch.autograd.Function):
         else:
             x, xhat, rstd, w1, w2, gamma, beta = ctx.saved_tensors
         has_b1, has_b2 = ctx.flags
-        go = go.contiguous()
+        go = _aligned(go)
         x_max, act_max = ctx.maxima
         N = go.shape[0]
         gh_parts = None
@@ -360,7 +360,7 @@ class _FusedMLP2(torch.autograd.Function):
             LINEAR_BWD_STATS["ln"] += 1
         else:
             # go^T relu(gamma xhat + beta)
-            gw2, gb2 = _wgrad(go, xhat, gamma.contiguous(), beta.contiguous(), go_max=row_max_of(go), x_max=act_max)
+            gw2, gb2 = _wgrad(go, xhat, gamma, beta, go_max=row_max_of(go), x_max=act_max)
             if tall_matmul_ln_backward_supported(go.shape[0], go.shape[1], w2.shape[1]):
                 # dA = go W2 never reaches memory: ReLU + LayerNorm backward run in the product's epilogue
                 gh, ggamma, gbeta, gh_max = tall_matmul_ln_backward(go, w2, xhat, rstd, gamma, beta, row_max_of(go))
@@ -400,6 +400,8 @@ def fused_mlp2_supported(x, w1, w2):
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= WGRAD_MIN_ROWS
             and torch.is_grad_enabled()):
         return False
+    if w1.dtype != torch.float32 or w2.dtype != torch.float32:
+        return False
     k, h, o = x.shape[1], w1.shape[0], w2.shape[0]
     ok = (64, 128, 256)
     return (k in ok and h in ok and o in ok and k * h * 4 <= 128 * 1024 and h * o * 4 <= 128 * 1024 and h <= 256
@@ -434,11 +436,11 @@ class _WideLinearF32(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         N, R = x.shape
         J = weight.shape[0]
-        x, weight = x.contiguous(), weight.contiguous()
+        x, weight = _aligned(x), _aligned(weight)
         Np = _lib.size("mlgnn_linear_f32x3_padded_rows", N)
         y = torch.empty((Np, J), dtype=torch.float32, device=x.device)
         ws, nbytes = _lib.workspace("mlgnn_linear_f32x3_fwd_workspace_bytes", N, R, J, device=x.device)
-        b = bias.contiguous() if bias is not None else None
+        b = f32_cached(bias) if bias is not None else None       # (a bias of another type: cast, never reinterpreted)
         _lib.call("mlgnn_linear_f32x3_fwd", x, weight, b, y, ws, nbytes, N, R, J, _lib.stream())
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
@@ -449,7 +451,7 @@ class _WideLinearF32(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         N, R = x.shape
         J = weight.shape[0]
-        go = go.contiguous()
+        go = _aligned(go)
         Np = _lib.size("mlgnn_linear_f32x3_padded_rows", N)
         gx = torch.empty((Np, R), dtype=torch.float32, device=x.device) if ctx.needs_input_grad[0] else None
         gw = torch.empty((J, R), dtype=torch.float32, device=x.device)
@@ -492,7 +494,7 @@ class _SkinnyLinear(torch.autograd.Function):
         J = w.shape[0]
         y = torch.empty((M, J), dtype=torch.float32, device=x.device)
         ws, n = _lib.workspace("mlgnn_skinny_linear_fwd_workspace_floats", M, J, K, device=x.device)
-        b = bias.contiguous() if bias is not None else None
+        b = f32_cached(bias) if bias is not None else None       # (a bias of another type: cast, never reinterpreted)
         _lib.call("mlgnn_skinny_linear_fwd", x, w, b, y, ws, n, M, J, K, _lib.stream())
         ctx.save_for_backward(x, w)
         ctx.has_bias = bias is not None
@@ -504,7 +506,7 @@ class _SkinnyLinear(torch.autograd.Function):
         x, w = ctx.saved_tensors
         M, K = x.shape
         J = w.shape[0]
-        go = go.contiguous()
+        go = _aligned(go)
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         gw = None
         if ctx.needs_input_grad[1]:
@@ -529,11 +531,11 @@ class _NarrowLinear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        x, w = x.contiguous(), weight.contiguous()
+        x, w = _aligned(x), _aligned(weight)
         N, R = x.shape
         J = w.shape[0]
         y = torch.empty((N, J), dtype=torch.float32, device=x.device)
-        b = bias.contiguous() if bias is not None else None
+        b = f32_cached(bias) if bias is not None else None       # (a bias of another type: cast, never reinterpreted)
         _lib.call("mlgnn_narrow_linear_fwd", x, w, b, y, N, R, J, _lib.stream())
         ctx.save_for_backward(x, w)
         ctx.has_bias = bias is not None
@@ -558,7 +560,10 @@ class _NarrowLinear(torch.autograd.Function):
 def linear(x, weight, bias=None, residual=None):
     """``nn.Linear`` forward (+ ``residual``: the identity branch of a residual block, added in the GEMM
     epilogue) with the tall-matrix kernels behind it when they apply (2-D fp32 CUDA input, >= 8192 rows,
-    <= 32 output tiles of 32x32); ``F.linear`` otherwise."""
+    <= 32 output tiles of 32x32, ``x`` contiguous); ``F.linear`` otherwise -- a non-contiguous ``x`` included.  ``x`` and
+    ``weight`` in different types are refused (``TypeError``) before anything is launched; a bias of another type is cast."""
+    if x.is_cuda and weight.dtype != x.dtype and not torch.is_autocast_enabled():        # (CPU tensors: ATen's own error)
+        raise TypeError("linear: x is %s but weight is %s; cast one of them" % (x.dtype, weight.dtype))
     if (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 2
             and x.shape[1] >= SKINNY_MIN_K and torch.is_grad_enabled()
             and _lib.lib.mlgnn_skinny_linear_supported(x.shape[0], weight.shape[0], x.shape[1])):
@@ -569,8 +574,8 @@ def linear(x, weight, bias=None, residual=None):
             and _lib.lib.mlgnn_narrow_linear_supported(x.shape[0], x.shape[1], weight.shape[0])):
         out = _NarrowLinear.apply(x, weight, bias)
         return out if residual is None else out + residual
-    if (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= WGRAD_MIN_ROWS
-            and x.is_contiguous() and torch.is_grad_enabled()
+    if (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 2
+            and x.shape[0] >= WGRAD_MIN_ROWS and x.is_contiguous() and torch.is_grad_enabled()
             and wgrad_supported(x.shape[0], weight.shape[0], weight.shape[1])):
         return _TallLinear.apply(x, weight, bias, residual)
     if (x.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and x.dim() == 2
@@ -584,6 +589,8 @@ def linear(x, weight, bias=None, residual=None):
         # fp32 widths past the tall kernels (hidden 512): three-term bf16 products instead of the library's fp32 GEMMs
         out = _WideLinearF32.apply(x, weight, bias)
         return out if residual is None else out + residual
+    if bias is not None and bias.dtype != x.dtype and not torch.is_autocast_enabled():
+        bias = bias.to(x.dtype)
     out = F.linear(x, weight, bias)
     return out if residual is None else out + residual
 
@@ -636,13 +643,15 @@ class _DenseSageFused(torch.autograd.Function):
 
 def dense_sage(x, adj, w_rel, w_root, b_root, normalize=True):
     """``normalize(W_rel (A x / clamp(rowsum A, 1)) + W_root x + b)``; 2-D ``adj`` broadcasts.
-    Pooled graphs of up to 160 nodes / 128 input / 64 output channels run as one fused launch."""
+    Pooled graphs of up to 160 nodes / 128 input / 64 output channels run as one fused launch (fp32 or bf16; ``adj`` and
+    the weights are cast to ``x``'s type); any other shape or type runs the library formula in ``x``'s type."""
     x = x.unsqueeze(0) if x.dim() == 2 else x
     adj = adj.unsqueeze(0) if adj.dim() == 2 else adj
     B, n, c = x.shape
-    if (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and adj.shape[0] in (1, B)
+    if (x.is_cuda and x.is_floating_point() and adj.shape[0] in (1, B)
             and (adj.dtype != x.dtype or w_rel.dtype != x.dtype or w_root.dtype != x.dtype)):
-        # (mixed storage types, e.g. an fp32 adjacency buffer in a bf16 model: one type for the kernel)
+        # (mixed storage types, e.g. an fp32 adjacency buffer in a bf16 model: one type -- x's -- for the kernel, or, for
+        # a type the kernel does not take, for the library formula below)
         adj, w_rel, w_root = adj.to(x.dtype), w_rel.to(x.dtype), w_root.to(x.dtype)
     if (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and adj.dtype == x.dtype and adj.shape[0] in (1, B)
             and adj.shape[-1] == n and adj.shape[-2] == n
@@ -663,7 +672,7 @@ class _DiffPoolFused(torch.autograd.Function):
     def forward(ctx, z, adj, s):
         B, N, C = z.shape
         K = s.shape[2]
-        z, s, adj = z.contiguous(), s.contiguous(), adj.contiguous()
+        z, s, adj = _aligned(z), _aligned(s), _aligned(adj)
         batched = adj.dim() == 3 and adj.shape[0] == B and B > 1
         adj_k = adj if batched else adj.reshape(N, N)
         S = torch.empty_like(s)
@@ -692,7 +701,7 @@ class _DiffPoolFused(torch.autograd.Function):
         gs = torch.empty_like(S)
         need_adj = ctx.needs_input_grad[1]
         gadj = torch.empty((B, N, N), dtype=z.dtype, device=z.device) if need_adj else None
-        gx, ga = gx.to(z.dtype).contiguous(), ga.to(z.dtype).contiguous()
+        gx, ga = _aligned(gx.to(z.dtype)), _aligned(ga.to(z.dtype))
         _lib.call("mlgnn_diffpool_bwd", z, adj, S, gx, ga, coef, gz, gs, gadj, B, N, K, C, int(batched),
                   _DTYPE_IDS[z.dtype], _lib.stream())
         if need_adj and not batched:
@@ -710,9 +719,7 @@ class _DiffPoolLarge(torch.autograd.Function):
         B, N, C = z.shape
         K = s.shape[2]
         dev = z.device
-        zb = z.contiguous() if z.dtype == torch.bfloat16 else z.to(torch.bfloat16).contiguous()
-        ab = adj.contiguous() if adj.dtype == torch.bfloat16 else adj.to(torch.bfloat16).contiguous()
-        s = s.contiguous()
+        zb, ab, s = _aligned(z.to(torch.bfloat16)), _aligned(adj.to(torch.bfloat16)), _aligned(s)
         out_dtype = z.dtype
         adj_batched = int(adj.shape[0] == B and B > 1)
         S = torch.empty((B, N, K), dtype=torch.bfloat16, device=dev)
@@ -736,7 +743,7 @@ class _DiffPoolLarge(torch.autograd.Function):
         K = S.shape[2]
         dev = zb.device
         gdt = torch.float32 if gx.dtype == torch.float32 else torch.bfloat16
-        gx, ga = gx.to(gdt).contiguous(), ga.to(gdt).contiguous()
+        gx, ga = _aligned(gx.to(gdt)), _aligned(ga.to(gdt))
         if g_link.dtype != g_ent.dtype or g_link.dtype not in (torch.float32, torch.bfloat16):
             g_link, g_ent = g_link.float(), g_ent.float()
         gz = torch.empty((B, N, C), dtype=s.dtype, device=dev)
@@ -766,7 +773,7 @@ class _DiffPoolLargeFP32(torch.autograd.Function):
         B, N, C = z.shape
         K = s.shape[2]
         dev = z.device
-        z, adj, s = z.contiguous(), adj.contiguous(), s.contiguous()
+        z, adj, s = _aligned(z), _aligned(adj), _aligned(s)
         adj_batched = int(adj.shape[0] == B and B > 1)
         S = torch.empty((B, N, K), dtype=torch.float32, device=dev)
         x_out = torch.empty((B, K, C), dtype=torch.float32, device=dev)
@@ -786,7 +793,7 @@ class _DiffPoolLargeFP32(torch.autograd.Function):
         adj, s, ws, stats = ctx.saved_tensors
         sym, adj_batched, (B, N, K, C) = ctx.cfg
         dev = s.device
-        gx, ga = gx.float().contiguous(), ga.float().contiguous()
+        gx, ga = _aligned(gx.float()), _aligned(ga.float())
         g_link, g_ent = g_link.float().contiguous(), g_ent.float().contiguous()
         gz = torch.empty((B, N, C), dtype=torch.float32, device=dev)
         gs = torch.empty((B, N, K), dtype=torch.float32, device=dev)
@@ -830,7 +837,8 @@ def dense_diff_pool(z, adj, s, adj_symmetric=False):
     Pooled graphs of up to 160 nodes / 48 clusters / 64 channels (the reference's 146 -> 37 -> 10)
     run as one fused fp32-MFMA launch; graphs whose sizes are multiples of 128 (BASELINE configs[4]:
     4096 nodes, 1024 clusters) as the matrix-core product chain of csrc/diffpool_large.hip (bf16) or its three-term
-    fp32-accurate form (csrc/diffpool_large_f32.hip); anything else as batched library GEMMs.  ``adj_symmetric`` promises ``adj == adj^T`` (saves a third of the large backward)."""
+    fp32-accurate form (csrc/diffpool_large_f32.hip); anything else -- ``z``, ``adj`` and ``s`` in types the kernels do not
+    take together included -- as batched library GEMMs in the widest of the three types.  ``adj_symmetric`` promises ``adj == adj^T`` (saves a third of the large backward)."""
     z = z.unsqueeze(0) if z.dim() == 2 else z
     adj = adj.unsqueeze(0) if adj.dim() == 2 else adj
     s = s.unsqueeze(0) if s.dim() == 2 else s
@@ -842,4 +850,6 @@ def dense_diff_pool(z, adj, s, adj_symmetric=False):
         return _DiffPoolFused.apply(z, adj.to(z.dtype), s.to(z.dtype))
     if adj.shape[0] in (1, B) and diff_pool_large_supported(z, adj, s):
         return _diff_pool_large(z, adj, s, adj_symmetric)
-    return _diff_pool_library(z, adj, s)
+    # (mixed types: the widest of the three for the library products)
+    dt = torch.promote_types(torch.promote_types(z.dtype, adj.dtype), s.dtype)
+    return _diff_pool_library(z.to(dt), adj.to(dt), s.to(dt))

@@ -54,7 +54,7 @@ class _VaeLatent(torch.autograd.Function):
             return None, None, None, None, None
         x, w_mu, w_ls, mu, sigma = ctx.saved_tensors
         B, P, H = x.shape
-        cots = [None if g is None else g.to(torch.float32).contiguous() for g in (g_mu, g_sigma, g_std, g_corr, g_kld)]
+        cots = [None if g is None else _lib.aligned(g.to(torch.float32)) for g in (g_mu, g_sigma, g_std, g_corr, g_kld)]
         grad_x = torch.empty_like(x) if need[0] else None
         grads = [(torch.empty_like(t) if P else torch.zeros_like(t)) if n else None
                  for t, n in zip((w_mu, w_mu[0], w_ls, w_ls[0]), need[1:])]
@@ -81,4 +81,4 @@ def vae_latent(x, w_mu, b_mu, w_ls, b_ls):
     for name, t, shape in (("w_mu", w_mu, (H, H)), ("b_mu", b_mu, (H,)), ("w_ls", w_ls, (H, H)), ("b_ls", b_ls, (H,))):
         if not (torch.is_tensor(t) and t.device == x.device and t.dtype == torch.float32 and tuple(t.shape) == shape):
             raise ValueError("vae_latent: %s must be an fp32 device tensor of shape %s" % (name, shape))
-    return _VaeLatent.apply(x, w_mu.contiguous(), b_mu.contiguous(), w_ls.contiguous(), b_ls.contiguous())
+    return _VaeLatent.apply(_lib.aligned(x), *(_lib.aligned(t) for t in (w_mu, b_mu, w_ls, b_ls)))

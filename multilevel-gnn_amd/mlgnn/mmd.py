@@ -54,7 +54,7 @@ class _Mmd(torch.autograd.Function):
         z, prior = ctx.saved_tensors
         kind, c_eps, c = ctx.cfg
         B, P, H = z.shape
-        grad_mmd = grad_mmd.to(torch.float32).contiguous()
+        grad_mmd = _lib.aligned(grad_mmd.to(torch.float32))
         grad_z = torch.empty_like(z)
         _lib.call("mlgnn_mmd_bwd", z, prior, grad_mmd, grad_z, kind, c_eps, c, B, P, H, _lib.stream())
         return grad_z, None, None, None, None
@@ -73,7 +73,7 @@ def mmd_per_pathway(z, prior, kind="imq", z_var=2.0, return_terms=False):
                          "B <= 256, B * H <= 8192, < 4 GiB)" % (tuple(z.shape), z.dtype, z.stride()))
     if not (torch.is_tensor(prior) and prior.device == z.device and prior.shape == z.shape):
         raise ValueError("mmd_per_pathway: prior must be a device tensor of z's shape %s" % (tuple(z.shape),))
-    prior = prior.detach().to(torch.float32).contiguous()
+    prior = _lib.aligned(prior.detach().to(torch.float32))
     c = 2 * z.shape[-1] * z_var                              # Python floats: eps + c is formed in double, as torch does
-    mmd, terms = _Mmd.apply(z, prior, KINDS[kind], float(EPS + c), float(c))
+    mmd, terms = _Mmd.apply(_lib.aligned(z), prior, KINDS[kind], float(EPS + c), float(c))
     return (mmd, terms) if return_terms else mmd

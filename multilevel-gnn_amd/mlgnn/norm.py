@@ -31,7 +31,7 @@ def _keep_mask(x, p):
 class _LayerNormAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps, relu, keep=None, keep_scale=1.0):
-        x = x.contiguous()
+        x = _lib.aligned(x)
         rows, d = x.shape
         out = torch.empty_like(x)
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
@@ -43,6 +43,7 @@ class _LayerNormAct(torch.autograd.Function):
         ctx.row_max = torch.empty(rows, dtype=torch.float32, device=x.device) if x.dtype == torch.float32 else None
         if keep is not None and (keep.shape != x.shape or keep.dtype != torch.uint8 or not keep.is_contiguous()):
             raise ValueError("dropout keep mask must be a contiguous uint8 tensor of the input's shape")
+        keep = _lib.aligned(keep)
         _lib.call("mlgnn_layernorm_act_fwd", x, weight, bias, out, mean, rstd, ctx.row_max, keep, float(keep_scale),
                   rows, d, float(eps), int(relu), _DTYPE_IDS[x.dtype], _lib.stream())
         ctx.relu = bool(relu)
@@ -60,9 +61,7 @@ def _ln_bwd(go, x, weight, bias, mean, rstd, relu, extra=None, keep=None, keep_s
     """The launch of ``mlgnn_layernorm_act_bwd`` (``weight`` / ``bias`` fp32, contiguous; ``mean`` None: ``x`` is stored
     normalised): ``-> (grad_x (+ extra), [grad_gamma; grad_beta] [2, d] fp32, max |grad_x| per row -- fp32 storage only)``."""
     rows, d = x.shape
-    go = go.contiguous()
-    if extra is not None:
-        extra = extra.contiguous()
+    go, extra = _lib.aligned(go), _lib.aligned(extra)
     gx = torch.empty_like(x)
     ggb = torch.empty((2, d), dtype=torch.float32, device=x.device)
     dt = _DTYPE_IDS[x.dtype]
@@ -94,7 +93,7 @@ def ln_backward_saved(go, x, weight, bias, mean, rstd, relu, extra=None):
 def ln_backward_normalised(go, xhat, weight, bias, rstd, relu=True):
     """LayerNorm(+ReLU) backward when the stored activation is already normalised (``xhat``, ``rstd`` from the
     first GEMM of :class:`mlgnn.dense._FusedMLP2`, fp32): ``-> (grad_x, grad_gamma, grad_beta, max |grad_x| per row)``."""
-    gx, ggb, row_max = _ln_bwd(go, xhat, weight.contiguous(), bias.contiguous(), None, rstd, relu)
+    gx, ggb, row_max = _ln_bwd(go, xhat, f32_cached(weight), f32_cached(bias), None, rstd, relu)
     return gx, ggb[0], ggb[1], row_max
 
 
@@ -118,10 +117,12 @@ def layer_norm_act(x, weight, bias, eps=1e-5, relu=False, dropout_p=0.0, dropout
     """``dropout?(relu?(LayerNorm(x)))`` over the last dimension of a 2-D tensor -- norm, activation and the dropout
     the res+ block puts behind them (deepergcn.py:239-240,246-247) in one pass.  ``dropout_p``: probability (the
     caller passes 0 outside training); ``dropout_mask``: explicit uint8 keep flags instead of a fresh draw (tests).
-    Shapes the fused kernel does not cover (see :func:`fused_supported`) take ATen on the same device."""
+    Shapes and types the fused kernel does not cover (see :func:`fused_supported`) take ATen on the same device."""
     if weight is not None and bias is not None and fused_supported(x):
         keep, scale = (dropout_mask, 1.0 / (1.0 - dropout_p)) if dropout_mask is not None else _keep_mask(x, dropout_p)
         return _tag_from_node(_LayerNormAct.apply(x, weight, bias, eps, relu, keep, scale))
+    if x.dtype == torch.float64 and weight is not None and weight.dtype != x.dtype:      # (ATen wants one type there)
+        weight, bias = weight.to(x.dtype), (bias.to(x.dtype) if bias is not None else None)
     y = F.layer_norm(x, (x.shape[-1],), weight, bias, eps)
     y = F.relu(y) if relu else y
     if dropout_mask is not None:
@@ -136,7 +137,8 @@ def _tag_from_node(y):
 
 def layer_norm_act_fork(x, weight, bias, eps=1e-5, relu=False, dropout_p=0.0, dropout_mask=None):
     """``(layer_norm_act(x), x)`` for a residual block: use the second value as the identity branch
-    (``h = f(y) + x``) so that its gradient is added inside the LayerNorm backward kernel."""
+    (``h = f(y) + x``) so that its gradient is added inside the LayerNorm backward kernel.  A non-contiguous ``x`` (or one
+    the fused kernel does not cover) takes :func:`layer_norm_act` and a plain identity branch."""
     if weight is not None and bias is not None and fused_supported(x) and x.is_contiguous():
         keep, scale = (dropout_mask, 1.0 / (1.0 - dropout_p)) if dropout_mask is not None else _keep_mask(x, dropout_p)
         y, identity = _LayerNormActFork.apply(x, weight, bias, eps, relu, keep, scale)
@@ -147,7 +149,7 @@ def layer_norm_act_fork(x, weight, bias, eps=1e-5, relu=False, dropout_p=0.0, dr
 class _MsgNormAdd(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, m, scale):
-        x, m = x.contiguous(), m.contiguous()
+        x, m = _lib.aligned(x), _lib.aligned(m)
         rows, d = x.shape
         h = torch.empty_like(x)
         scale32 = scale if scale.dtype == torch.float32 else scale.float()       # the learnable scalar stays fp32
@@ -160,7 +162,7 @@ class _MsgNormAdd(torch.autograd.Function):
     def backward(ctx, gh):
         x, m, scale = ctx.saved_tensors
         rows, d = x.shape
-        gh = gh.contiguous()
+        gh = _lib.aligned(gh)
         gx, gm = torch.empty_like(x), torch.empty_like(m)
         gs = torch.empty(1, dtype=torch.float32, device=x.device)
         ws, n = _lib.workspace("mlgnn_msgnorm_bwd_workspace_floats", rows, d, device=x.device)
@@ -171,7 +173,8 @@ class _MsgNormAdd(torch.autograd.Function):
 
 def msg_norm_add(x, m, scale):
     """``x + normalize(m, dim=1) * ||x|| * scale`` (MsgNorm + GENConv root add, torch_message.py:175-179,
-    torch_vertex.py:86-89) in one HIP pass each way; ATen ops for widths the kernel does not cover."""
+    torch_vertex.py:86-89) in one HIP pass each way; ATen ops for widths and types (``x`` and ``m`` in different ones
+    included) the kernel does not cover."""
     if (m.shape == x.shape and m.dtype == x.dtype and x.is_cuda and x.dim() == 2
             and ((x.dtype == torch.float32 and 0 < x.shape[1] <= 256 and x.shape[1] % 4 == 0)
                  or (x.dtype == torch.bfloat16 and 0 < x.shape[1] <= 512 and x.shape[1] % 8 == 0))):

@@ -100,7 +100,7 @@ def _dev_f32(t, what):
         raise RuntimeError("%s must live on the GPU: libmlgnn has no CPU path" % what)
     if t.dtype != torch.float32:
         raise TypeError("%s must be float32, got %s" % (what, t.dtype))
-    return t.contiguous()
+    return _lib.aligned(t)
 
 
 def _dev_act(t, what, like=None):
@@ -113,7 +113,7 @@ def _dev_act(t, what, like=None):
         raise TypeError("%s must be float32 or bfloat16, got %s" % (what, t.dtype))
     if like is not None and t.dtype != like.dtype:
         t = t.to(like.dtype)
-    return t.contiguous()
+    return _lib.aligned(t)
 
 
 # Off by default.  Measured at BASELINE configs[1] (same-box A/B, bench.py): the epilogue costs the aggregation backward
@@ -209,7 +209,7 @@ class _EdgeTypeEmbedding(torch.autograd.Function):
     @staticmethod
     def backward(ctx, ge):
         (idx,) = ctx.saved_tensors
-        ge = ge.contiguous()
+        ge = _lib.aligned(ge)                     # (mlgnn_embedding_bwd gathers 16-byte rows: MLGNN_E_ALIGN otherwise)
         order, rowptr = _sort_by_table_row(idx, ctx.rows)
         return _sum_rows_by_table_row(ge, order, rowptr, ctx.rows), None
 
@@ -665,7 +665,8 @@ def _ln_fold_backward(tag, x, gx, launch):
     ln_ws, ln_n = _lib.workspace("mlgnn_csr_aggregate_bwd_ln_workspace_floats", N, d, device=x.device)
     ggb, row_max = torch.empty((2, d), **f32), torch.empty(N, **f32)
     extra = tag.extra if (tag.extra is not None and tag.extra.dtype == torch.float32
-                          and tag.extra.shape == x.shape and tag.extra.is_contiguous()) else None
+                          and tag.extra.shape == x.shape and tag.extra.is_contiguous()
+                          and tag.extra.data_ptr() % 16 == 0) else None
     gamma, beta = f32_cached(tag.gamma), f32_cached(tag.beta)
     st = _lib.LnFoldStruct(tag.h.data_ptr(), tag.mean.data_ptr(), tag.rstd.data_ptr(), gamma.data_ptr(),
                            beta.data_ptr(), _lib.ptr(extra), row_max.data_ptr(), ggb.data_ptr(), ln_ws.data_ptr(),
@@ -809,5 +810,7 @@ def weighted_mean_aggregate(x, graph, weight=None, mean=True):
     """``mean_{e: dst(e)=i} w_e x_src(e)`` (count = number of edges, not sum of weights): the SAGE
     neighbourhood reduction applied BEFORE ``lin_r`` (torch_vertex.py:279-286 by linearity).
     ``weight``: ``[E]`` / ``[E,1]`` in COO order or ``None``.  No gradient flows to ``weight``."""
+    if x.dtype not in _DTYPE_IDS:                        # (refused before the edge table is built)
+        raise TypeError("x must be float32 or bfloat16, got %s" % x.dtype)
     ew_pair = graph.edge_scalar(weight) if weight is not None else None
     return _WeightedAggregate.apply(x, graph, ew_pair, bool(mean))

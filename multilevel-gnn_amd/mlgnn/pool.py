@@ -13,7 +13,7 @@ _KINDS = {"sum": 0, "add": 0, "mean": 1, "max": 2}
 class _SegmentPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, ptr, batch, kind):
-        x = x.contiguous()
+        x = _lib.aligned(x)                      # (mlgnn_segment_pool_fwd reads 16-byte rows: MLGNN_E_ALIGN otherwise)
         N, d = x.shape
         B = ptr.numel() - 1
         out = torch.empty((B, d), dtype=torch.float32, device=x.device)

@@ -66,7 +66,7 @@ class _PoolFlatten(torch.autograd.Function):
             return None, None, None, None, None, None
         keep, winner = ctx.saved_tensors
         B, H, W, C, ph, pw, keep_scale, has_age = ctx.cfg
-        go = go.contiguous()
+        go = _lib.aligned(go)
         gx = torch.empty((B, H, W, C), dtype=torch.float32, device=go.device)
         _lib.call("mlgnn_pool_flatten_bwd", go, keep, keep_scale, winner, gx, int(has_age), B, H, W, C, ph, pw,
                   _lib.stream())
@@ -88,16 +88,16 @@ def pool_flatten(x, window, dropout_p=0.0, training=False, age=None, dropout_mas
     if age is not None:
         if not (torch.is_tensor(age) and age.is_cuda and age.numel() == B):
             raise ValueError("pool_flatten: age must be a device tensor with one value per sample")
-        age = age.detach().reshape(B).to(torch.float32).contiguous()
+        age = _lib.aligned(age.detach().reshape(B).to(torch.float32))
     keep, keep_scale = None, 1.0
     if dropout_mask is not None:
         if dropout_mask.numel() != B * n:
             raise ValueError("pool_flatten: dropout_mask must hold one flag per pooled element (%d x %d)" % (B, n))
-        keep = dropout_mask.to(device=x.device, dtype=torch.uint8).reshape(B, n).contiguous()
+        keep = _lib.aligned(dropout_mask.to(device=x.device, dtype=torch.uint8).reshape(B, n))
         keep_scale = 1.0 / (1.0 - dropout_p) if dropout_p < 1.0 else 0.0
     elif training and dropout_p:
         keep, keep_scale = _keep_mask(x.new_empty(1).expand(B, n), dropout_p)
-    return _PoolFlatten.apply(x.permute(0, 2, 3, 1), age, keep, float(keep_scale), ph, pw)
+    return _PoolFlatten.apply(_lib.aligned(x.permute(0, 2, 3, 1)), age, keep, float(keep_scale), ph, pw)
 
 
 def _module_window(pool):

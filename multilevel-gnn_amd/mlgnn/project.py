@@ -74,7 +74,7 @@ class _SegmentProject(torch.autograd.Function):
         if x.dtype == torch.bfloat16:
             if not x.is_cuda:
                 raise RuntimeError("x must be a CUDA tensor (no CPU fallback)")
-            x = x.contiguous()
+            x = _lib.aligned(x)
         else:
             x = _dev_f32(x, "x")
         ctx.w_dtype = w.dtype
@@ -99,7 +99,7 @@ class _SegmentProject(torch.autograd.Function):
         t = ctx.tables
         R, C = x.shape
         G, K = w.shape
-        gout_t = gout_t.to(x.dtype).contiguous() if ctx.dt == DTYPE_BF16 else _dev_f32(gout_t, "grad_out")
+        gout_t = _lib.aligned(gout_t.to(x.dtype)) if ctx.dt == DTYPE_BF16 else _dev_f32(gout_t, "grad_out")
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         gwp = torch.empty((t.B * G, K), dtype=torch.float32, device=x.device) if ctx.needs_input_grad[1] else None
         _lib.call("mlgnn_segment_project_bwd", gout_t, x, w, t.seg_ptr, t.seg_mem, t.mem_row, t.mem_seg, t.node_ptr,

@@ -20,7 +20,7 @@ import torch
 from . import _lib
 from .dense import WGRAD_MIN_ROWS, _aligned, _wgrad, tall_matmul_nt, tall_matmul_supported, wgrad_supported
 from .ops import AGGR_MEAN, AGGR_SUM, MSG_IDENTITY, MSG_WEIGHTED, _aggregate_bwd, _aggregate_fwd
-from .tags import tag_row_max
+from .tags import f32_cached, tag_row_max
 
 STATS = {"fused": 0, "fallback": 0}
 
@@ -33,7 +33,8 @@ def sage_layer_supported(x, w_nn, w_r, has_conv_bias):
         return False
     n, cin = x.shape
     cout = w_nn.shape[0]
-    if w_nn.shape[1] != cin + cout or tuple(w_r.shape) != (cout, cin) or w_nn.dtype != torch.float32:
+    if (w_nn.shape[1] != cin + cout or tuple(w_r.shape) != (cout, cin) or w_nn.dtype != torch.float32
+            or w_r.dtype != torch.float32):
         return False
     return (bool(_lib.lib.mlgnn_tallgemm_dual_supported(n, cin, cin, cout))
             and tall_matmul_supported(n, cout, cin) and wgrad_supported(n, cout, cin))
@@ -54,7 +55,7 @@ class _SageLayer(torch.autograd.Function):
         hub, hub_keep = graph.hub_arg("dst", cin)
         _aggregate_fwd(x, graph, agg, msg, aggr, hub, ew_pair=ew_pair)
         # lin_r folded into the update's weight: [W_x (- W_c) | W_c], W_c = W_a W_r  (one small launch)
-        w_nn_c, w_r_c = w_nn.contiguous(), w_r.contiguous()
+        w_nn_c, w_r_c = _aligned(w_nn), _aligned(w_r)
         f32 = dict(dtype=torch.float32, device=dev)
         w_cat, w_x1, w_c = torch.empty((cout, 2 * cin), **f32), torch.empty((cout, cin), **f32), torch.empty((cout, cin), **f32)
         _lib.call("mlgnn_sage_fold_fwd", w_nn_c, w_r_c, w_cat, w_x1, w_c, cin, cout, int(bool(relative)), _lib.stream())
@@ -62,8 +63,8 @@ class _SageLayer(torch.autograd.Function):
         y_max = torch.empty(N, dtype=torch.float32, device=dev)
         a_max = torch.empty(N, dtype=torch.float32, device=dev)
         ws, nbytes = _lib.workspace("mlgnn_tallgemm_workspace_bytes", 2 * cin, cout, 0, device=dev)
-        bias = b_nn.contiguous() if b_nn is not None else None
-        rs = row_scale.reshape(-1).contiguous() if row_scale is not None else None
+        bias = f32_cached(b_nn) if b_nn is not None else None        # (a bias of another type: cast)
+        rs = _aligned(row_scale.reshape(-1)) if row_scale is not None else None
         _lib.call("mlgnn_tallgemm_dual", x, agg, w_cat, bias, float(slope), rs, y, y_max, a_max, ws, nbytes, N, cin,
                   cin, cout, _lib.stream())
         ctx.save_for_backward(x, agg, y, w_nn_c, w_r_c, w_x1, w_c, rs, a_max)
@@ -126,7 +127,7 @@ class _NodeEmbed(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, emb):
         nodes, C = emb.shape
-        x = x.reshape(-1).contiguous()
+        x = _aligned(x.reshape(-1))
         batch = x.numel() // nodes
         emb = _aligned(emb)
         h = torch.empty((batch * nodes, C), dtype=torch.float32, device=x.device)
@@ -176,7 +177,7 @@ class _LinearAct(torch.autograd.Function):
         y_max = torch.empty(N, dtype=torch.float32, device=x.device)
         a_max = torch.empty(N, dtype=torch.float32, device=x.device)
         ws, nbytes = _lib.workspace("mlgnn_tallgemm_workspace_bytes", R, J, 0, device=x.device)
-        bias = b.contiguous() if b is not None else None
+        bias = f32_cached(b) if b is not None else None
         _lib.call("mlgnn_tallgemm_dual", x, None, w, bias, float(slope), None, y, y_max, a_max, ws, nbytes, N, R, 0, J,
                   _lib.stream())
         ctx.save_for_backward(x, w, y, a_max)
@@ -219,6 +220,7 @@ class _TransposeBatched(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x):
+        x = _aligned(x)
         B, R, C = x.shape
         y = torch.empty((B, C, R), dtype=torch.float32, device=x.device)
         _lib.call("mlgnn_transpose_batched", x, y, B, R, C, _lib.stream())
@@ -226,7 +228,7 @@ class _TransposeBatched(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        gy = gy.contiguous()
+        gy = _aligned(gy)
         B, C, R = gy.shape
         gx = torch.empty((B, R, C), dtype=torch.float32, device=gy.device)
         _lib.call("mlgnn_transpose_batched", gy, gx, B, C, R, _lib.stream())

@@ -3,6 +3,8 @@ they describe (row maxima, the softmax log-sum-exp, the rescaled cotangent, the 
 belongs to ONE backward, and the fp32 copies of non-fp32 parameters.  No kernel is launched from here."""
 import torch
 
+from ._lib import aligned as _aligned
+
 
 def tag_row_max(t, row_max):
     """Attach ``max |row|`` ([N] fp32, written by the kernel that produced ``t``) to a 2-D tensor; the tall GEMM
@@ -119,8 +121,8 @@ def invalidate_param_cache():
 
 
 def f32_cached(t):
-    """``t`` as a contiguous fp32 tensor for a kernel argument (LayerNorm gamma / beta, a bias: the kernels read their
-    [d]-sized parameters in fp32).  A non-fp32 tensor is cast per call -- always correct -- unless it is a parameter some
+    """``t`` as a contiguous, 16-byte aligned fp32 tensor for a kernel argument (LayerNorm gamma / beta, a bias: the
+    kernels read their [d]-sized parameters in fp32).  A non-fp32 tensor is cast per call -- always correct -- unless it is a parameter some
     ``torch.optim.Optimizer`` has stepped: its copy is then kept until the next optimizer step of the process (a global
     post-step hook counts them: updates through ``p.data.copy_`` inside an optimizer, as the reference's utils/optim.py
     does, are seen although they do not bump the version counter), a version bump, or a change of storage address /
@@ -128,7 +130,7 @@ def f32_cached(t):
     BASELINE configs[4]).  Edits through ``.data`` between optimizer steps: :func:`invalidate_param_cache`.
     Only for use inside autograd Functions (the copy is detached)."""
     if t.dtype == torch.float32:
-        return t.contiguous()
+        return _aligned(t)
     if not getattr(t, "_mlgnn_stepped", False):
         return t.detach().float().contiguous()
     key = (_PARAM_EPOCH[0], t._version, t.data_ptr(), t.device)

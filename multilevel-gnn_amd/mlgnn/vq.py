@@ -70,9 +70,9 @@ class _Vq(torch.autograd.Function):
         N, D = z.shape
         K = codebook.shape[0]
         if g_out is not None:
-            g_out = g_out.to(torch.float32).contiguous()
+            g_out = _lib.aligned(g_out.to(torch.float32))
         if g_loss is not None:
-            g_loss = g_loss.to(torch.float32).contiguous()
+            g_loss = _lib.aligned(g_loss.to(torch.float32))
         grad_z = torch.empty_like(z) if need_z else None
         grad_cb = None
         if need_cb:
@@ -96,6 +96,6 @@ def vector_quantize(latents, codebook, beta=0.25, return_indices=False):
             tuple(latents.shape), latents.dtype, tuple(codebook.shape) if torch.is_tensor(codebook) else None,
             getattr(codebook, "dtype", None), RULE))
     D = codebook.shape[1]
-    out, loss, index = _Vq.apply(latents.reshape(-1, D).contiguous(), codebook.contiguous(), float(beta))
+    out, loss, index = _Vq.apply(_lib.aligned(latents.reshape(-1, D)), _lib.aligned(codebook), float(beta))
     out = out.view(latents.shape)
     return (out, loss, index.view(latents.shape[:-1])) if return_indices else (out, loss)

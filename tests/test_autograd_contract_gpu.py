@@ -14,6 +14,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _forms
 from _util import assert_close, assert_close_own_scale
 from oracle import gcn_lib as G
 from oracle import models as OM
@@ -516,8 +517,10 @@ def _cotangents(outs, use, form, seed, dtype):
 
 
 def _on_device(c, form, dtype):
-    """``c`` on the device in the cotangent form under test: an expanded scalar (zero strides), or every other element
-    of a twice-as-wide buffer (non-contiguous)."""
+    """``c`` on the device in the cotangent form under test: an expanded scalar (zero strides), every other element of
+    a twice-as-wide buffer (non-contiguous), or a contiguous view one element off a 16-byte boundary (offset)."""
+    if form == "offset" and c.dim():
+        return _forms.offset(c.to(device=DEV, dtype=dtype))
     if form == "zero_stride" and c.dim():
         return torch.full((), float(c.reshape(-1)[0]), dtype=dtype, device=DEV).expand(c.shape)
     if form == "noncontig" and c.dim() and c.shape[-1] > 1:
@@ -716,11 +719,11 @@ def test_partial_grad_then_full_backward(patched):
 # ------------------------------------------------------------------------------------------------------------------- (d)
 
 @_params(NAMES)
-@pytest.mark.parametrize("form", ["zero_stride", "noncontig"])
+@pytest.mark.parametrize("form", ["zero_stride", "noncontig", "offset"])
 def test_cotangent_forms(patched, form):
     name = patched
     entry = REGISTRY[name]
-    ref = _reference(name, (0,), form)
+    ref = _reference(name, (0,), "dense" if form == "offset" else form)      # (offset: the dense values, moved)
     t = _inputs(entry, 0, entry.diff, DEV)
     outs = _forward(entry, t)
     _loss(outs, _cotangents(outs, _use(entry, outs), form, 0, entry.dtype), form).backward()

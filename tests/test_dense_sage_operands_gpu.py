@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import test_pooled_levels_gpu as PL
+from _forms import at_offset as _at_offset
 
 gpu = pytest.mark.gpu
 DEV = PL.DEV
@@ -50,16 +51,6 @@ def test_each_output_and_gradient(case):
 
 
 # ------------------------------------------------------------------------------------------------------ B. alignment
-
-def _at_offset(t, elems):
-    """``t``'s values as a contiguous tensor that starts ``elems`` elements into a larger, 16-byte aligned buffer."""
-    buf = torch.zeros(t.numel() + 8, dtype=t.dtype, device=t.device)
-    assert buf.data_ptr() % 16 == 0
-    view = buf[elems:elems + t.numel()].view(t.shape)
-    view.copy_(t)
-    assert view.is_contiguous() and view.data_ptr() == buf.data_ptr() + elems * t.element_size()
-    return view
-
 
 def _run(tensors, grad_adj):
     """y and every gradient, on the device; the leaves are the tensors as given (their storage offset is kept)."""
