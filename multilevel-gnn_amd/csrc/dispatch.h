@@ -17,6 +17,15 @@ bool dispatch_int(int v, F&& f) {
   return ((v == Vs && (f(IC<Vs>{}), true)) || ...);
 }
 
+// A compile-time list of admitted values.  One list serves both sides of an entry point: the `_supported` predicate asks
+// has(), the launcher dispatches over the same values, so the two cannot drift apart.
+template <int... Vs>
+struct IntList {
+  static constexpr bool has(int64_t v) { return ((v == Vs) || ...); }
+  template <class F>
+  static bool dispatch(int v, F&& f) { return dispatch_int<Vs...>(v, std::forward<F>(f)); }
+};
+
 // every pointer a multiple of A bytes; a null pointer (an optional argument that is absent) counts as aligned
 template <size_t A = 16, class... P>
 bool aligned(const P*... p) {

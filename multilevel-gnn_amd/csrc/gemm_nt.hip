@@ -40,16 +40,11 @@
 // all eight waves doing both DMA and MFMA (48 us), a second pair of MFMA waves splitting K with an LDS reduce (42 us),
 // a fifth stage / three K-steps in flight (same), s_setprio around the MFMAs (same).
 #include "gemm_nt.h"
+#include "split_precision.h"
 #include "launch.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
-
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using i32x4 = __attribute__((ext_vector_type(4))) int;
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void glb_void_t;
 
 constexpr int kGConsumers = 4;                                 // MFMA waves (1 per SIMD)
 constexpr int kGLoaders = 4;                                   // LDS-DMA waves (1 per SIMD)
@@ -369,5 +364,5 @@ extern "C" int mlgnn_gemm_bf16_nt(const void* const* a, const void* const* b, co
   d.ct = (uint16_t*)ct; d.ldct = ldct;
   d.aux = aux; d.ldaux = ldaux; d.aux_f32 = aux_dtype == MLGNN_DTYPE_F32; d.alpha = alpha;
   d.dot = (const uint16_t*)dot; d.lddot = lddot; d.dot_partial = dot_partial;
-  return gemm_nt_launch(d, (hipStream_t)stream);
+  return gemm_nt_launch(d, as_stream(stream));
 }

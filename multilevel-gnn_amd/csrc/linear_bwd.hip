@@ -31,58 +31,24 @@
 // go through LDS once per stage.  SHIFT / PLAIN (M = 256, K = 128: the first Linear): dX is written as it is; with the
 // log-sum-exp of the softmax aggregation that produced x, also dX 2^(-lse) (the rescaled cotangent that aggregation's
 // backward gathers, csrc/aggregate_bwd.hip).  All partial results are reduced in a fixed order: bitwise reproducible.
-#include "common.h"
+#include "split_precision.h"
 #include "launch.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
 
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using i32x4 = __attribute__((ext_vector_type(4))) int;
-using i32x2 = __attribute__((ext_vector_type(2))) int;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void glb_void_t;
-
 constexpr int kLbThreads = 512, kLbWaves = 8, kLbStage = 32;
-constexpr int kLbParts = 256;                 // partial maxima per operand (= the most workgroups a launch has)
 enum { LB_LN = 0, LB_PLAIN = 1, LB_SHIFT = 2 };
 
 struct LbArgs {
   const float* go; const float* w; const float* x;        // [N,M], [M,K], [N,K]
-  const float* go_parts; const float* x_parts;            // [kLbParts] partial maxima of |go| and of |x'| (the dW operand)
-  float* dx; float* ws; float* out_parts;                 // [N,K]; per-workgroup partial slabs; [kLbParts] max |dx| (or null)
+  const float* go_parts; const float* x_parts;            // [kMaxParts] partial maxima of |go| and of |x'| (the dW operand)
+  float* dx; float* ws; float* out_parts;                 // [N,K]; per-workgroup partial slabs; [kMaxParts] max |dx| (or null)
   const float* rstd; const float* gamma; const float* beta;          // LB_LN
   const float* lse; float* gt; int* spread;                          // LB_SHIFT
   int N; int slab_cols;
   int parts_max_with_old;                                            // a later row slab: out_parts = max(old, this slab's)
 };
-
-__device__ __forceinline__ void lb_pow2_scale(float max_abs, float& s, float& inv) {    // as in tallgemm.hip
-  int e = (int)((__builtin_bit_cast(uint32_t, max_abs) >> 23) & 0xff);
-  e = min(max(e, 20), 234);
-  s = __builtin_bit_cast(float, (uint32_t)(254 + 13 - e) << 23);
-  inv = __builtin_bit_cast(float, (uint32_t)(e - 13) << 23);
-}
-__device__ __forceinline__ float lb_fold_parts(const float* part) {           // the same value in every lane
-  const int lane = threadIdx.x & (kWave - 1);
-  float m = 0.f;
-#pragma unroll
-  for (int i = 0; i < kLbParts / kWave; ++i) m = fmaxf(m, part[lane + i * kWave]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-  return m;
-}
-__device__ __forceinline__ void lb_split2(const float (&v)[8], float s, f16x8& h, f16x8& l) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float x = v[j] * s;
-    const _Float16 hh = (_Float16)x;
-    h[j] = hh;
-    l[j] = (_Float16)(x - (float)hh);
-  }
-}
 
 // LDS reads of the main loop are inline asm: the compiler treats an LDS-DMA in flight as a pending write to the whole
 // shared array and would drain every DMA (s_waitcnt vmcnt(0)) in front of any ds_read it can see
@@ -152,15 +118,9 @@ __device__ __forceinline__ void lb_wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <int ROR>
-__device__ __forceinline__ float lb_row_ror(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + ROR, 0xf, 0xf, false));
-}
-
 // rows of a 32-row stage are named in the accumulator order of the 32x32 MFMA: register r of a lane in half h is row
-// rho(r, h) = (r & 3) + 8 (r >> 2) + 4 h.  Row group G = 2 kk + h (kk = 16-deep k-step of the dW product) holds
-// rho(8 kk + j, h), j = 0..7: rows 16 kk + 4 h + {0..3} and + 8 + {0..3}.
-__device__ __forceinline__ constexpr int lb_rho(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+// rho(r, h) = mfma32_row(r, h) = (r & 3) + 8 (r >> 2) + 4 h.  Row group G = 2 kk + h (kk = 16-deep k-step of the dW
+// product) holds rho(8 kk + j, h), j = 0..7: rows 16 kk + 4 h + {0..3} and + 8 + {0..3}.
 
 template <int M, int K, int EPI>
 __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) {
@@ -198,22 +158,21 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
 
   // ---- scales -------------------------------------------------------------------------------------------------------
   float sa, ia, sx, ix, sw, iw;
-  lb_pow2_scale(lb_fold_parts(p.go_parts), sa, ia);
-  lb_pow2_scale(lb_fold_parts(p.x_parts), sx, ix);
+  pow2_scale(fold_max_parts(p.go_parts), sa, ia);
+  pow2_scale(fold_max_parts(p.x_parts), sx, ix);
   {
     float m = 0.f;
     for (int i = tid; i < M * K / 4; i += kLbThreads) {
       const float4 q = reinterpret_cast<const float4*>(p.w)[i];
       m = fmaxf(m, fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fmaxf(fabsf(q.z), fabsf(q.w))));
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+    m = wave_max(m);
     if (lane == 0) ex[wave] = m;
     __syncthreads();
     m = ex[0];
 #pragma unroll
     for (int i = 1; i < kLbWaves; ++i) m = fmaxf(m, ex[i]);
-    lb_pow2_scale(m, sw, iw);
+    pow2_scale(m, sw, iw);
     __syncthreads();
   }
   // (wave-uniform values the compiler cannot see as uniform: keep them in scalar registers)
@@ -228,7 +187,7 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = p.w[(size_t)(mh * MW + 16 * s + 8 * h + j) * K + col];
-    lb_split2(v, sw, wh[s], wl[s]);
+    split2(v, sw, wh[s], wl[s]);
   }
   float gam = 0.f, bet = 0.f;
   if constexpr (EPI == LB_LN) { gam = p.gamma[col]; bet = p.beta[col]; }
@@ -287,7 +246,7 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
       }
       bsum[q] += s;
       f16x8 hi, lo;
-      lb_split2(v, sa, hi, lo);
+      split2(v, sa, hi, lo);
       unsigned char* dst = smem + buf * kBufB + ulds[q];
       *reinterpret_cast<f16x8*>(dst) = hi;
       *reinterpret_cast<f16x8*>(dst + kPlaneB) = lo;
@@ -367,7 +326,7 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
         } else {
 #pragma unroll
           for (int q = 0; q < 8; ++q)
-            lse8[q] = glb_load_f32<0>(p.lse, (uint32_t)(min(r0 + lb_rho(8 * mh + q, h), p.N - 1) * K + col) * 4u);
+            lse8[q] = glb_load_f32<0>(p.lse, (uint32_t)(min(r0 + mfma32_row(8 * mh + q, h), p.N - 1) * K + col) * 4u);
         }
       }
       fetch_go(row_of(i + 1));
@@ -378,7 +337,7 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
       float xv[16];
       {
         const uint32_t ax = a_x + (uint32_t)xbuf * kXStageB;
-#define LB_XV(R) xv[R] = lds_read_f32<(((R) & 3) + 8 * ((R) >> 2)) * K * 4>(ax);
+#define LB_XV(R) xv[R] = lds_read_f32<mfma32_row(R, 0) * K * 4>(ax);
         LB_XV(0) LB_XV(1) LB_XV(2) LB_XV(3) LB_XV(4) LB_XV(5) LB_XV(6) LB_XV(7)
         LB_XV(8) LB_XV(9) LB_XV(10) LB_XV(11) LB_XV(12) LB_XV(13) LB_XV(14) LB_XV(15)
 #undef LB_XV
@@ -398,7 +357,7 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
           if constexpr (EPI == LB_LN) v[j] = relu_keep_nan(fmaf(v[j], gam, bet));
         }
         f16x8 bh, bl;
-        lb_split2(v, sx, bh, bl);
+        split2(v, sx, bh, bl);
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
           const int step = kk * MT + t, slot = step & 1;
@@ -471,7 +430,7 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
         float mine = 0.f;                              // the row sum this lane hands in: row r_mine of its 16-lane row
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const bool live = full || r0 + lb_rho(r, h) < p.N;
+          const bool live = full || r0 + mfma32_row(r, h) < p.N;
           const float y = fmaf(xv[r], gam, bet);
           const float gy = (live && y > 0.f) ? accx[r] * ux : 0.f;
           dgam = fmaf(gy, xv[r], dgam);
@@ -485,7 +444,7 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
           const float recv = __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(
               __builtin_bit_cast(int, odd_row ? g[r] : gx), 0x401f));          // lane ^ 16
           float u = (odd_row ? gx : g[r]) + recv;
-          u += lb_row_ror<8>(u); u += lb_row_ror<4>(u); u += lb_row_ror<2>(u); u += lb_row_ror<1>(u);
+          u += dpp_row_ror<8>(u); u += dpp_row_ror<4>(u); u += dpp_row_ror<2>(u); u += dpp_row_ror<1>(u);
           mine = (r_mine == r) ? u : mine;
         }
         // value index = lane: row16 = lane >> 4 is (sum g, h = 0), (sum g xhat, h = 0), (sum g, h = 1), (sum g xhat, h = 1)
@@ -518,7 +477,7 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
           const float s1 = __shfl(tot, 32 * h + r) * inv_k;
           const float s2 = __shfl(tot, 32 * h + 16 + r) * inv_k;
           g[r] = rs[r] * (g[r] - s1 - xv[r] * s2);
-          if (!full && r0 + lb_rho(r, h) >= p.N) g[r] = 0.f;              // (rows past the end: rstd is not theirs)
+          if (!full && r0 + mfma32_row(r, h) >= p.N) g[r] = 0.f;              // (rows past the end: rstd is not theirs)
           om = fmaxf(om, fabsf(g[r]));
         }
         // (uniform base + 32-bit lane offset: one address register for the 16 stores)
@@ -527,12 +486,12 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
         if (full) {
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            *reinterpret_cast<float*>(out + (o0 + (uint32_t)(((r & 3) + 8 * (r >> 2)) * K * 4))) = g[r];
+            *reinterpret_cast<float*>(out + (o0 + (uint32_t)(mfma32_row(r, 0) * K * 4))) = g[r];
         } else {
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            if (r0 + lb_rho(r, h) < p.N)
-              *reinterpret_cast<float*>(out + (o0 + (uint32_t)(((r & 3) + 8 * (r >> 2)) * K * 4))) = g[r];
+            if (r0 + mfma32_row(r, h) < p.N)
+              *reinterpret_cast<float*>(out + (o0 + (uint32_t)(mfma32_row(r, 0) * K * 4))) = g[r];
         }
       } else {
         // the two waves of a column strip hold the two halves of the contraction: wave mh finishes registers
@@ -577,17 +536,17 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
         if (full) {
 #pragma unroll
           for (int q = 0; q < 8; ++q)
-            *reinterpret_cast<float*>(out + (o0 + (uint32_t)(((q & 3) + 8 * (q >> 2)) * K * 4))) = v[q];
+            *reinterpret_cast<float*>(out + (o0 + (uint32_t)(mfma32_row(q, 0) * K * 4))) = v[q];
           if (EPI == LB_SHIFT && shift) {
 #pragma unroll
             for (int q = 0; q < 8; ++q)
-              *reinterpret_cast<float*>(out_t + (o0 + (uint32_t)(((q & 3) + 8 * (q >> 2)) * K * 4))) = gt[q];
+              *reinterpret_cast<float*>(out_t + (o0 + (uint32_t)(mfma32_row(q, 0) * K * 4))) = gt[q];
           }
         } else {
 #pragma unroll
           for (int q = 0; q < 8; ++q) {
-            if (r0 + lb_rho(8 * mh + q, h) < p.N) {
-              const uint32_t o = o0 + (uint32_t)(((q & 3) + 8 * (q >> 2)) * K * 4);
+            if (r0 + mfma32_row(8 * mh + q, h) < p.N) {
+              const uint32_t o = o0 + (uint32_t)(mfma32_row(q, 0) * K * 4);
               *reinterpret_cast<float*>(out + o) = v[q];
               if (EPI == LB_SHIFT && shift) *reinterpret_cast<float*>(out_t + o) = gt[q];
             }
@@ -626,7 +585,7 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
   for (int t = 0; t < MT; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      slab[(size_t)(mh * MW + 32 * t + lb_rho(r, h)) * K + col] = accw[t][r] * uw;
+      slab[(size_t)(mh * MW + 32 * t + mfma32_row(r, h)) * K + col] = accw[t][r] * uw;
   __syncthreads();
 #pragma unroll
   for (int q = 0; q < UPT; ++q) {
@@ -655,7 +614,7 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
   }
 }
 
-// row maxima [n] -> kLbParts partial maxima (slices), one or two arrays per launch
+// row maxima [n] -> kMaxParts partial maxima (slices), one or two arrays per launch
 __global__ __launch_bounds__(256) void lb_rowmax_parts_kernel(const float* __restrict__ a, float* __restrict__ pa,
                                                              const float* __restrict__ b, float* __restrict__ pb, int n,
                                                              int* __restrict__ zero4, float* __restrict__ zero_parts) {
@@ -664,7 +623,7 @@ __global__ __launch_bounds__(256) void lb_rowmax_parts_kernel(const float* __res
   // instead of by memset launches of their own)
   if (blockIdx.x == 0 && threadIdx.x < 4 && zero4) zero4[threadIdx.x] = 0;
   if (threadIdx.x == 0 && zero_parts) zero_parts[blockIdx.x] = 0.f;
-  const int per = (n + kLbParts - 1) / kLbParts;
+  const int per = (n + kMaxParts - 1) / kMaxParts;
   const int lo = blockIdx.x * per, hi = min(n, lo + per);
   float ma = 0.f, mb = 0.f;
   for (int i = lo + threadIdx.x; i < hi; i += 256) { if (a) ma = fmaxf(ma, a[i]); if (b) mb = fmaxf(mb, b[i]); }
@@ -701,11 +660,11 @@ extern "C" int mlgnn_linear_bwd_supported(int64_t N, int64_t M, int64_t K, int e
   return lb_shape_ok(N, M, K, epilogue) ? 1 : 0;
 }
 
-// workspace (floats): one partial slab per workgroup, then 3 x kLbParts partial maxima
+// workspace (floats): one partial slab per workgroup, then 3 x kMaxParts partial maxima
 extern "C" int64_t mlgnn_linear_bwd_workspace_floats(int64_t N, int64_t M, int64_t K, int epilogue) {
   if (!mlgnn_linear_bwd_supported(N, M, K, epilogue)) return MLGNN_E_SHAPE;
   const int64_t cols = M * K + M + (epilogue == LB_LN ? 2 * K : 0);
-  return (int64_t)kLbParts * cols + 3 * kLbParts;
+  return (int64_t)kMaxParts * cols + 3 * kMaxParts;
 }
 
 extern "C" int mlgnn_linear_bwd(const float* go, const float* w, const float* x, const float* go_max, int go_max_is_parts,
@@ -720,28 +679,26 @@ extern "C" int mlgnn_linear_bwd(const float* go, const float* w, const float* x,
   if (epilogue == LB_SHIFT && (!lse || !grad_shifted || !shift_flag)) return MLGNN_E_NULL;
   if (workspace_floats < mlgnn_linear_bwd_workspace_floats(N, M, K, epilogue)) return MLGNN_E_WORKSPACE;
   if (!aligned(go, w, x, rstd)) return MLGNN_E_ALIGN;
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = as_stream(stream);
   const int cols = (int)(M * K + M + (epilogue == LB_LN ? 2 * K : 0));
-  float* parts = workspace + (int64_t)kLbParts * cols;           // [go | x | (unused)]
+  float* parts = workspace + (int64_t)kMaxParts * cols;           // [go | x | (unused)]
   const int64_t stages = (N + kLbStage - 1) / kLbStage;
-  const int grid = (int)(stages < kLbParts ? stages : kLbParts);
-  hipLaunchKernelGGL(lb_rowmax_parts_kernel, dim3(kLbParts), dim3(256), 0, s, go_max_is_parts ? nullptr : go_max, parts,
-                     x_row_max, parts + kLbParts, (int)N, epilogue == LB_SHIFT ? shift_flag : nullptr,
-                     (dx_max_parts && grid < kLbParts) ? dx_max_parts : nullptr);
+  const int grid = (int)(stages < kMaxParts ? stages : kMaxParts);
+  hipLaunchKernelGGL(lb_rowmax_parts_kernel, dim3(kMaxParts), dim3(256), 0, s, go_max_is_parts ? nullptr : go_max, parts,
+                     x_row_max, parts + kMaxParts, (int)N, epilogue == LB_SHIFT ? shift_flag : nullptr,
+                     (dx_max_parts && grid < kMaxParts) ? dx_max_parts : nullptr);
   int err;
   LbArgs a;
-  a.w = w; a.go_parts = go_max_is_parts ? go_max : parts; a.x_parts = parts + kLbParts;
+  a.w = w; a.go_parts = go_max_is_parts ? go_max : parts; a.x_parts = parts + kMaxParts;
   a.ws = workspace; a.out_parts = dx_max_parts;
   a.gamma = gamma; a.beta = beta;
   a.spread = shift_flag;
   a.slab_cols = cols;
-#define MLGNN_LB_LAUNCH(M_, K_, EPI_)                                                                        \
-  {                                                                                                          \
-    constexpr int lds_bytes = lb_lds_bytes<M_, K_>();                                                        \
-    if (const hipError_t e_ = allow_dynamic_lds(&linear_bwd_kernel<M_, K_, EPI_>, lds_bytes); e_ != hipSuccess) \
-      return (int)e_;                                                                                        \
-    hipLaunchKernelGGL((linear_bwd_kernel<M_, K_, EPI_>), dim3(grid), dim3(kLbThreads), lds_bytes, s, a);    \
-  }
+  const auto launch = [&](auto kernel, int lds_bytes, int grid) {
+    if (const hipError_t e = allow_dynamic_lds(kernel, lds_bytes); e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kLbThreads), lds_bytes, s, a);
+    return (int)hipGetLastError();
+  };
   if (epilogue == LB_PLAIN) { lse = nullptr; grad_shifted = nullptr; a.spread = nullptr; }
   // row slabs below 4 GiB (one at BASELINE configs[1]; two at 5.12 M rows): operand bases advance, the operand scales stay
   // those of the whole input, a slab's partial sums are added to its predecessors' in slab order
@@ -749,17 +706,16 @@ extern "C" int mlgnn_linear_bwd(const float* go, const float* w, const float* x,
   for (int64_t r0 = 0; r0 < N; r0 += slab_rows) {
     const int64_t n = N - r0 < slab_rows ? N - r0 : slab_rows;
     const int64_t st = (n + kLbStage - 1) / kLbStage;
-    const int grid = (int)(st < kLbParts ? st : kLbParts);
+    const int grid = (int)(st < kMaxParts ? st : kMaxParts);
     a.go = go + r0 * M; a.x = x + r0 * K; a.dx = dx + r0 * K;
     a.rstd = rstd ? rstd + r0 : nullptr;
     a.lse = lse ? lse + r0 * K : nullptr; a.gt = grad_shifted ? grad_shifted + r0 * K : nullptr;
     a.N = (int)n; a.parts_max_with_old = r0 > 0;
-    if (epilogue == LB_LN) MLGNN_LB_LAUNCH(128, 256, LB_LN)
-    else MLGNN_LB_LAUNCH(256, 128, LB_SHIFT)            // (plain = the same instantiation without lse / grad_shifted)
-    err = (int)hipGetLastError();
+    // (plain = the SHIFT instantiation without lse / grad_shifted)
+    err = epilogue == LB_LN ? launch(&linear_bwd_kernel<128, 256, LB_LN>, lb_lds_bytes<128, 256>(), grid)
+                            : launch(&linear_bwd_kernel<256, 128, LB_SHIFT>, lb_lds_bytes<256, 128>(), grid);
     if (err) return err;
     launch_reduce_partials(workspace, grad_w_b, grid, cols, s, r0 > 0);
   }
-#undef MLGNN_LB_LAUNCH
   return (int)hipGetLastError();
 }

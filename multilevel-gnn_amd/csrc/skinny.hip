@@ -13,7 +13,7 @@
 //   dW        workgroup = (64 rows of J) x (128 columns of K), the whole M range inside: dW tile written once
 //
 // Deterministic: no atomics, fixed summation orders.
-#include "common.h"
+#include "split_precision.h"
 #include "launch.h"
 #include "mlgnn.h"
 
@@ -24,10 +24,8 @@ constexpr int kSkJ = 64;            // J tile
 constexpr int kSkK = 128;           // K tile
 constexpr int kSkLd = kSkK + 4;     // LDS row stride (floats): 16-byte aligned rows, neighbouring rows 4 banks apart
 constexpr int kSkThreads = 256;
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 // v_mfma_f32_32x32x2_f32: lane l supplies A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31];
-// C/D: register r of lane l is row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31.
-__device__ __forceinline__ int sk_crow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+// C/D: register r of lane l is row mfma32_row(r, l >> 5), column l & 31.
 
 // global [rows, ld] tile (rows x 128 floats from column k0, zero past `rows_valid` rows / `k_valid` columns) -> LDS [64][132]
 __device__ __forceinline__ void sk_load_tile(float* __restrict__ lds, const float* __restrict__ src, int64_t ld, int row0,
@@ -81,7 +79,7 @@ __global__ __launch_bounds__(kSkThreads) void skinny_fwd_kernel(const float* __r
   const int j = jt * kSkJ + 32 * wj + i31;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int m = 32 * wm + sk_crow(r, h);
+    const int m = 32 * wm + mfma32_row(r, h);
     if (m < M && j < J) out[(size_t)m * J + j] = acc[r] + ((split == 0 && bias) ? bias[j] : 0.f);   // (the bias enters once)
   }
 }
@@ -129,7 +127,7 @@ __global__ __launch_bounds__(kSkThreads) void skinny_dx_kernel(const float* __re
     const int k = k0 + 64 * wk + 32 * t + i31;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int m = 32 * wm + sk_crow(r, h);
+      const int m = 32 * wm + mfma32_row(r, h);
       if (m < M && k < K) dx[(size_t)m * K + k] = acc[t][r];
     }
   }
@@ -243,7 +241,7 @@ extern "C" int mlgnn_skinny_linear_fwd(const float* x, const float* w, const flo
   int kps;
   const int splits = sk_plan(J, K, &kps);
   if (workspace_floats < (int64_t)splits * M * J) return MLGNN_E_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = as_stream(stream);
   constexpr int lds_bytes = (kSkM + kSkJ) * kSkLd * 4;
   if (const hipError_t e = allow_dynamic_lds(&skinny_fwd_kernel, lds_bytes); e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(skinny_fwd_kernel, dim3((unsigned)((J + kSkJ - 1) / kSkJ), (unsigned)splits), dim3(kSkThreads), lds_bytes, s,
@@ -257,7 +255,7 @@ extern "C" int mlgnn_skinny_linear_bwd(const float* grad_out, const float* x, co
   if (!sk_ok(M, J, K)) return MLGNN_E_SHAPE;
   if (!grad_out || (grad_x && !w) || (grad_w && !x)) return MLGNN_E_NULL;
   if (!aligned(x, w, grad_x, grad_w)) return MLGNN_E_ALIGN;
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = as_stream(stream);
   const unsigned kt = (unsigned)((K + kSkK - 1) / kSkK);
   if (grad_x) hipLaunchKernelGGL(skinny_dx_kernel, dim3(kt), dim3(kSkThreads), 0, s, grad_out, w, grad_x, (int)M, (int)J, (int)K);
   if (grad_w)

@@ -21,26 +21,15 @@
 // 16-byte loads (lane l = row l&31, k-half l>>5): once for the row maxima, once -- from L1/L2 -- through
 // the k-step loop that scales, splits and issues 3 MFMAs (v_mfma_f32_32x32x16_f16) per 32-column tile.
 // HBM-bound: reads N*R*4, writes N*J*4.
-#include "common.h"
+#include "split_precision.h"
 #include "launch.h"
 #include "dense_bf16.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
 
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
 constexpr int kTgMaxLds = 128 * 1024;      // split weight image
 constexpr int kTgHeader = 4;               // f16x8 slots (64 B) in front of the image: [0] = 1 / weight scale
-
-// power of two s with  max * s in [2^13, 2^14)  and its inverse; max = 0 or denormal -> 1
-__device__ __forceinline__ void pow2_scale(float max_abs, float& s, float& inv) {
-  int e = (int)((__builtin_bit_cast(uint32_t, max_abs) >> 23) & 0xff);       // biased exponent
-  e = min(max(e, 20), 234);
-  s = __builtin_bit_cast(float, (uint32_t)(254 + 13 - e) << 23);             // 2^(13 - (e - 127))
-  inv = __builtin_bit_cast(float, (uint32_t)(e - 13) << 23);                 // 2^((e - 127) - 13)
-}
 
 // Bt [J,R] fp32 -> frag[kstep][tile][hi|lo][lane][8] fp16: lane l of tile t, k-step s holds
 // Bt[32 t + (l & 31)][16 s + 8 (l >> 5) + j] * scale, j = 0..7  (B operand of v_mfma_f32_32x32x16_f16).
@@ -58,8 +47,7 @@ __global__ __launch_bounds__(kBlock) void tallgemm_split_weight_kernel(const flo
     const float4 q = reinterpret_cast<const float4*>(bt)[i];
     m = fmaxf(m, fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fmaxf(fabsf(q.z), fabsf(q.w))));
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+  m = wave_max(m);
   if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = m;
   __syncthreads();
   m = red[0];
@@ -74,34 +62,34 @@ __global__ __launch_bounds__(kBlock) void tallgemm_split_weight_kernel(const flo
   if (idx >= ksteps * tiles * 64) return;
   const int lane = idx & 63, t = (idx >> 6) % tiles, s = (idx >> 6) / tiles;
   const int row = 32 * t + (lane & 31), k0 = 16 * s + 8 * (lane >> 5);
-  f16x8 hi, lo;
+  float v[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float v = (transposed ? bt[(size_t)(k0 + j) * J + row] : bt[(size_t)row * R + k0 + j]) * scale;
-    const _Float16 h = (_Float16)v;
-    hi[j] = h;
-    lo[j] = (_Float16)(v - (float)h);
-  }
+  for (int j = 0; j < 8; ++j) v[j] = transposed ? bt[(size_t)(k0 + j) * J + row] : bt[(size_t)row * R + k0 + j];
+  f16x8 hi, lo;
+  split2(v, scale, hi, lo);
   const size_t base = kTgHeader + ((size_t)(s * tiles + t) * 2) * 64 + lane;
   image[base] = hi;
   image[base + 64] = lo;
 }
 
 struct TgArgs {
-  const float* a; const f16x8* image; const float* bias; const float* res; const float* rowmax; float* c;
-  const float* gamma; const float* beta; float* rstd_out; float* rowmax_out; float ln_eps;
-  const float* xhat; const float* rstd_in; float* ws;        // LN = 3
+  const float* a = nullptr; const f16x8* image = nullptr; const float* bias = nullptr; const float* res = nullptr;
+  const float* rowmax = nullptr; float* c = nullptr;
+  const float* gamma = nullptr; const float* beta = nullptr; float* rstd_out = nullptr; float* rowmax_out = nullptr;
+  float ln_eps = 0.f;
+  const float* xhat = nullptr; const float* rstd_in = nullptr; float* ws = nullptr;        // LN = 3
   // POST: the result rows go through a SECOND LayerNorm (+ ReLU) in the epilogue -- the norm + activation the res+
   // block puts in front of the next conv (deepergcn.py:236-241) -- written to y next to c; mean / 1 sigma to
   // mean_out / rstd_out (what that LayerNorm's backward needs)
-  const float* pgamma; const float* pbeta; float* y; float* mean_out; float peps; int prelu;
+  const float* pgamma = nullptr; const float* pbeta = nullptr; float* y = nullptr; float* mean_out = nullptr;
+  float peps = 0.f; int prelu = 0;
   // SHIFT: res holds lse [N,J] of the softmax aggregation whose backward consumes c; y receives c * 2^(-lse)
-  const int* rowptr; int* spread;
+  const int* rowptr = nullptr; int* spread = nullptr;
   // DUAL (SAGE update, torch_vertex.py:288-291): A = [a | a2] column blocks of two tensors (k-steps [0, ks1) from a,
   // row stride 16 ks1; the rest from a2), c = leaky_relu(A Bt^T + bias, act_slope) * row_scale[row]; max |c| per row to
   // rowmax_out, max |A row| to amax_out
-  const float* a2; int ks1; float act_slope; const float* row_scale; float* amax_out;
-  int N; int R; int J;
+  const float* a2 = nullptr; int ks1 = 0; float act_slope = 1.f; const float* row_scale = nullptr; float* amax_out = nullptr;
+  int N = 0; int R = 0; int J = 0;
 };
 
 // k-steps of the A operand in flight ahead of the MFMAs: 4 where the registers allow it, 2 for the instantiations
@@ -549,10 +537,64 @@ __global__ __launch_bounds__((tg_block<JT, LN>())) void tallgemm_kernel(const Tg
   }
 }
 
-static bool tg_dims_ok(int64_t R, int64_t J) {
-  const bool j_ok = (J == 32 || J == 64 || J == 128 || J == 256);
-  const bool r_ok = (R == 16 || R == 32 || R == 64 || R == 128 || R == 256);
-  return j_ok && r_ok && R * J * 4 <= kTgMaxLds;
+// ---- which (JT, KS) = (J / 32, R / 16) each family of instantiations admits -------------------------------------------
+// Every family is the Cartesian product of a JT list and a KS list, less the pairs whose weight image exceeds the LDS
+// (tg_fits: only 8 x 16, i.e. 256 x 256).  The `_supported` predicates and the launcher below read the same lists.
+using TgPlainJT = IntList<1, 2, 4, 8>;
+using TgPlainKS = IntList<1, 2, 4, 8, 16>;
+using TgLnJT = IntList<2, 4, 8>;            // LN-out, LN-in and LN-backward: whole rows of 64 .. 256 columns
+using TgLnKS = IntList<4, 8, 16>;           // ... and the k range of every epilogue family
+using TgEpiJT = IntList<2, 4>;              // POST, SHIFT: the residual / lse tile sits in registers (<= 128 columns)
+using TgDualJT = IntList<1, 2, 4>;
+using TgDualKS = IntList<2, 4, 8, 16>;
+
+constexpr bool tg_fits(int64_t jt, int64_t ks) { return 32 * jt * 16 * ks * 4 <= kTgMaxLds; }
+
+template <class JTs, class KSs>
+constexpr bool tg_admits(int64_t R, int64_t J) {
+  return J % 32 == 0 && R % 16 == 0 && JTs::has(J / 32) && KSs::has(R / 16) && tg_fits(J / 32, R / 16);
+}
+static bool tg_dims_ok(int64_t R, int64_t J) { return tg_admits<TgPlainJT, TgPlainKS>(R, J); }
+
+template <int LN, bool POST = false, bool SHIFT = false, bool DUAL = false>
+struct TgVariant {
+  template <int JT, int KS>
+  static constexpr auto kernel() { return &tallgemm_kernel<JT, KS, LN, POST, SHIFT, DUAL>; }
+};
+
+// Launch Variant's instantiation for (J / 32, R / 16) out of JTs x KSs: raise its dynamic-LDS limit, then launch.  A pair
+// that is not admitted launches nothing: MLGNN_E_SHAPE.  Otherwise the status of the attribute call or of the launch.
+template <class Variant, class JTs, class KSs>
+static int tg_launch(const TgArgs& p, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+  int rc = MLGNN_E_SHAPE;
+  JTs::dispatch(p.J / 32, [&](auto jt) {
+    KSs::dispatch(p.R / 16, [&](auto ks) {
+      constexpr int JT = decltype(jt)::value, KS = decltype(ks)::value;
+      if constexpr (tg_fits(JT, KS)) {
+        constexpr auto kernel = Variant::template kernel<JT, KS>();
+        rc = (int)allow_dynamic_lds(kernel, kTgMaxLds + 4096);
+        if (rc != 0) return;
+        hipLaunchKernelGGL(kernel, grid, block, lds, s, p);
+        rc = (int)hipGetLastError();
+      }
+    });
+  });
+  return rc;
+}
+
+// the split-weight pre-pass: bt [J, R] (transposed: [R, J]) -> header + fragment image in `workspace`
+static int launch_split_weight(const float* bt, void* workspace, int64_t J, int64_t R, int transposed, hipStream_t s) {
+  const int n_frag_lanes = (int)(R / 16) * (int)(J / 32) * 64;
+  hipLaunchKernelGGL(tallgemm_split_weight_kernel, dim3((n_frag_lanes + 255) / 256), dim3(256), 0, s, bt,
+                     (f16x8*)workspace, (int)J, (int)R, transposed);
+  return (int)hipGetLastError();
+}
+
+// persistent grid: one workgroup per CU at most, `waves` 32-row tiles per round
+static int tg_grid(int64_t N, int waves, int cap) {
+  const int64_t tiles = (N + 31) / 32;
+  const int64_t grid = (tiles + waves - 1) / waves;
+  return (int)(grid > cap ? cap : grid);
 }
 
 }  // namespace mlgnn
@@ -595,7 +637,7 @@ static int tallgemm_nt_any(const void* a, const void* bt, int bt_transposed, con
     if (!a || !bt || !c || !workspace) return MLGNN_E_NULL;
     if (workspace_bytes < R * J * 2) return MLGNN_E_WORKSPACE;
     if (!aligned(a, bt, workspace) || !aligned<4>(c, residual)) return MLGNN_E_ALIGN;
-    return tallgemm_bf16(a, bt, bias, residual, c, workspace, N, R, J, (hipStream_t)stream);
+    return tallgemm_bf16(a, bt, bias, residual, c, workspace, N, R, J, as_stream(stream));
   }
   if (!tg_dims_ok(R, J)) return MLGNN_E_SHAPE;
   if (!a || !bt || !c || !workspace) return MLGNN_E_NULL;
@@ -603,7 +645,7 @@ static int tallgemm_nt_any(const void* a, const void* bt, int bt_transposed, con
   if (ln_mode < 0 || ln_mode > 2) return MLGNN_E_MODE;
   if (ln_mode != 0 && (!gamma || !beta)) return MLGNN_E_NULL;
   if (ln_mode == 1 && (!rstd_out || !row_max_out || residual)) return MLGNN_E_NULL;
-  if (ln_mode != 0 && (R < 64 || J < 64)) return MLGNN_E_SHAPE;      // LN modes are instantiated for 64..256 only
+  if (ln_mode != 0 && !tg_admits<TgLnJT, TgLnKS>(R, J)) return MLGNN_E_SHAPE;      // LN modes: 64 .. 256 only
   if (post) {
     if (ln_mode != 2 || J > 128) return MLGNN_E_MODE;
     if (!post->gamma || !post->beta || !post->y || !post->mean || !post->rstd) return MLGNN_E_NULL;
@@ -614,73 +656,29 @@ static int tallgemm_nt_any(const void* a, const void* bt, int bt_transposed, con
   }
   if (workspace_bytes < R * J * 4 + kTgHeader * 16) return MLGNN_E_WORKSPACE;
   if (!aligned(a, bt, workspace)) return MLGNN_E_ALIGN;
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = as_stream(stream);
   if (shift) {
     int err0 = (int)hipMemsetAsync(shift->flag, 0, 16, s);
     if (err0) return err0;
   }
-  const int n_frag_lanes = (int)(R / 16) * (int)(J / 32) * 64;
-  hipLaunchKernelGGL(tallgemm_split_weight_kernel, dim3((n_frag_lanes + 255) / 256), dim3(256), 0, s,
-                     (const float*)bt, (f16x8*)workspace, (int)J, (int)R, bt_transposed);
-  int err = (int)hipGetLastError();
-  if (err) return err;
-  TgArgs p;
+  if (const int err = launch_split_weight((const float*)bt, workspace, J, R, bt_transposed, s)) return err;
+  TgArgs p{};
   p.a = (const float*)a; p.image = (const f16x8*)workspace; p.bias = bias; p.res = (const float*)residual;
   p.rowmax = row_max; p.c = (float*)c;
   p.gamma = gamma; p.beta = beta; p.rstd_out = rstd_out; p.rowmax_out = row_max_out; p.ln_eps = ln_eps;
-  p.xhat = nullptr; p.rstd_in = nullptr; p.ws = nullptr;
-  p.pgamma = nullptr; p.pbeta = nullptr; p.y = nullptr; p.mean_out = nullptr; p.peps = 0.f; p.prelu = 0;
   if (post) {
     p.pgamma = post->gamma; p.pbeta = post->beta; p.y = post->y; p.mean_out = post->mean; p.rstd_out = post->rstd;
     p.peps = post->eps; p.prelu = post->relu;
   }
-  p.rowptr = nullptr; p.spread = nullptr;
-  p.a2 = nullptr; p.ks1 = 0; p.act_slope = 1.f; p.row_scale = nullptr; p.amax_out = nullptr;
   if (shift) { p.res = shift->lse; p.y = shift->gt; p.rowptr = shift->rowptr; p.spread = shift->flag; }
   p.N = (int)N; p.R = (int)R; p.J = (int)J;
   const size_t lds = (size_t)R * J * 4 + (ln_mode == 2 ? (size_t)R * 8 : 0) + (ln_mode == 1 ? (size_t)J * 12 : 0);
-  const int64_t tiles = (N + 31) / 32;
-  int grid = (int)((tiles + kTgWaves - 1) / kTgWaves);
-  if (grid > 256) grid = 256;                      // persistent: one workgroup per CU
-  const dim3 g(grid), b(kTgBlock);
-  bool launched = false;
-#define MLGNN_TG_LAUNCH2(JT_, KS_, LN_, POST_, SHIFT_)                                                 \
-  {                                                                                                   \
-    if (const hipError_t e_ = allow_dynamic_lds(&tallgemm_kernel<JT_, KS_, LN_, POST_, SHIFT_>, kTgMaxLds + 4096); \
-        e_ != hipSuccess)                                                                             \
-      return (int)e_;                                                                                 \
-    hipLaunchKernelGGL((tallgemm_kernel<JT_, KS_, LN_, POST_, SHIFT_>), g, b, lds, s, p);              \
-    launched = true;                                                                                  \
-  }
-#define MLGNN_TG_LAUNCH(JT_, KS_, LN_, POST_) MLGNN_TG_LAUNCH2(JT_, KS_, LN_, POST_, false)
-#define MLGNN_TG_CASE(JT_, KS_)                                                                       \
-  if (!launched && ln_mode == 0 && !shift && J == 32 * JT_ && R == 16 * KS_) MLGNN_TG_LAUNCH(JT_, KS_, 0, false)
-#define MLGNN_TG_CASE_SHIFT(JT_, KS_)                                                                 \
-  if (!launched && shift && J == 32 * JT_ && R == 16 * KS_) MLGNN_TG_LAUNCH2(JT_, KS_, 0, false, true)
-#define MLGNN_TG_CASE_LN(JT_, KS_)                                                                    \
-  if (!launched && ln_mode == 1 && J == 32 * JT_ && R == 16 * KS_) MLGNN_TG_LAUNCH(JT_, KS_, 1, false)       \
-  if (!launched && ln_mode == 2 && !post && J == 32 * JT_ && R == 16 * KS_) MLGNN_TG_LAUNCH(JT_, KS_, 2, false)
-#define MLGNN_TG_CASE_POST(JT_, KS_)                                                                  \
-  if (!launched && ln_mode == 2 && post && J == 32 * JT_ && R == 16 * KS_) MLGNN_TG_LAUNCH(JT_, KS_, 2, true)
-#define MLGNN_TG_ROW(JT_) MLGNN_TG_CASE(JT_, 1) MLGNN_TG_CASE(JT_, 2) MLGNN_TG_CASE(JT_, 4) MLGNN_TG_CASE(JT_, 8)
-  MLGNN_TG_ROW(1) MLGNN_TG_ROW(2) MLGNN_TG_ROW(4) MLGNN_TG_ROW(8)
-  MLGNN_TG_CASE(1, 16) MLGNN_TG_CASE(2, 16) MLGNN_TG_CASE(4, 16)          // 256 x 256 exceeds the LDS image
-  MLGNN_TG_CASE_LN(2, 4) MLGNN_TG_CASE_LN(2, 8) MLGNN_TG_CASE_LN(2, 16)
-  MLGNN_TG_CASE_LN(4, 4) MLGNN_TG_CASE_LN(4, 8) MLGNN_TG_CASE_LN(4, 16)
-  MLGNN_TG_CASE_LN(8, 4) MLGNN_TG_CASE_LN(8, 8)
-  MLGNN_TG_CASE_POST(2, 4) MLGNN_TG_CASE_POST(2, 8) MLGNN_TG_CASE_POST(2, 16)
-  MLGNN_TG_CASE_POST(4, 4) MLGNN_TG_CASE_POST(4, 8) MLGNN_TG_CASE_POST(4, 16)
-  MLGNN_TG_CASE_SHIFT(2, 4) MLGNN_TG_CASE_SHIFT(2, 8) MLGNN_TG_CASE_SHIFT(2, 16)
-  MLGNN_TG_CASE_SHIFT(4, 4) MLGNN_TG_CASE_SHIFT(4, 8) MLGNN_TG_CASE_SHIFT(4, 16)
-#undef MLGNN_TG_CASE_SHIFT
-#undef MLGNN_TG_LAUNCH2
-#undef MLGNN_TG_ROW
-#undef MLGNN_TG_CASE_POST
-#undef MLGNN_TG_CASE_LN
-#undef MLGNN_TG_CASE
-#undef MLGNN_TG_LAUNCH
-  if (!launched) return MLGNN_E_SHAPE;
-  return (int)hipGetLastError();
+  const dim3 g(tg_grid(N, kTgWaves, 256)), b(kTgBlock);
+  if (shift) return tg_launch<TgVariant<0, false, true>, TgEpiJT, TgLnKS>(p, g, b, lds, s);
+  if (post) return tg_launch<TgVariant<2, true>, TgEpiJT, TgLnKS>(p, g, b, lds, s);
+  if (ln_mode == 1) return tg_launch<TgVariant<1>, TgLnJT, TgLnKS>(p, g, b, lds, s);
+  if (ln_mode == 2) return tg_launch<TgVariant<2>, TgLnJT, TgLnKS>(p, g, b, lds, s);
+  return tg_launch<TgVariant<0>, TgPlainJT, TgPlainKS>(p, g, b, lds, s);
 }
 
 extern "C" int mlgnn_tallgemm_nt(const void* a, const void* bt, int bt_transposed, const float* bias, const void* residual,
@@ -693,8 +691,7 @@ extern "C" int mlgnn_tallgemm_nt(const void* a, const void* bt, int bt_transpose
 }
 
 extern "C" int mlgnn_tallgemm_nt_shift_supported(int64_t N, int64_t R, int64_t J) {
-  const bool ok = (J == 64 || J == 128) && (R == 64 || R == 128 || R == 256) && R * J * 4 <= kTgMaxLds;
-  return (N > 0 && N <= INT32_MAX && ok) ? 1 : 0;
+  return (N > 0 && N <= INT32_MAX && tg_admits<TgEpiJT, TgLnKS>(R, J)) ? 1 : 0;
 }
 
 extern "C" int mlgnn_tallgemm_nt_shift(const float* a, const float* bt, int bt_transposed, const float* row_max,
@@ -709,8 +706,7 @@ extern "C" int mlgnn_tallgemm_nt_shift(const float* a, const float* bt, int bt_t
 }
 
 extern "C" int mlgnn_tallgemm_lnin_postln_supported(int64_t N, int64_t R, int64_t J) {
-  const bool ok = (J == 64 || J == 128) && (R == 64 || R == 128 || R == 256) && R * J * 4 <= kTgMaxLds;
-  return (N > 0 && N <= INT32_MAX && ok) ? 1 : 0;
+  return (N > 0 && N <= INT32_MAX && tg_admits<TgEpiJT, TgLnKS>(R, J)) ? 1 : 0;
 }
 
 extern "C" int mlgnn_tallgemm_lnin_postln(const float* xhat, const float* bt, const float* bias, const float* residual,
@@ -730,8 +726,7 @@ extern "C" int mlgnn_tallgemm_lnin_postln(const float* xhat, const float* bt, co
 extern "C" int mlgnn_tallgemm_dual_supported(int64_t N, int64_t R1, int64_t R2, int64_t J) {
   const int64_t R = R1 + R2;
   // (R2 = 0: one operand, the activation epilogue only)
-  const bool ok = R1 >= 16 && R2 >= 0 && R1 % 16 == 0 && R2 % 16 == 0 && (R == 32 || R == 64 || R == 128 || R == 256) &&
-                  (J == 32 || J == 64 || J == 128) && R * J * 4 <= kTgMaxLds;
+  const bool ok = R1 >= 16 && R2 >= 0 && R1 % 16 == 0 && R2 % 16 == 0 && tg_admits<TgDualJT, TgDualKS>(R, J);
   return (N > 0 && N <= INT32_MAX && ok) ? 1 : 0;
 }
 
@@ -746,39 +741,15 @@ extern "C" int mlgnn_tallgemm_dual(const float* a, const float* a2, const float*
   if (R2 == 0) a2 = a;                                    // (never dereferenced: every k-step comes from a)
   if (workspace_bytes < R * J * 4 + kTgHeader * 16) return MLGNN_E_WORKSPACE;
   if (!aligned(a, a2, bt, workspace)) return MLGNN_E_ALIGN;
-  hipStream_t s = (hipStream_t)stream;
-  const int n_frag_lanes = (int)(R / 16) * (int)(J / 32) * 64;
-  hipLaunchKernelGGL(tallgemm_split_weight_kernel, dim3((n_frag_lanes + 255) / 256), dim3(256), 0, s, bt,
-                     (f16x8*)workspace, (int)J, (int)R, 0);
-  int err = (int)hipGetLastError();
-  if (err) return err;
-  TgArgs p;
-  p.a = a; p.image = (const f16x8*)workspace; p.bias = bias; p.res = nullptr; p.rowmax = nullptr; p.c = c;
-  p.gamma = nullptr; p.beta = nullptr; p.rstd_out = nullptr; p.rowmax_out = row_max_out; p.ln_eps = 0.f;
-  p.xhat = nullptr; p.rstd_in = nullptr; p.ws = nullptr;
-  p.pgamma = nullptr; p.pbeta = nullptr; p.y = nullptr; p.mean_out = nullptr; p.peps = 0.f; p.prelu = 0;
-  p.rowptr = nullptr; p.spread = nullptr;
+  hipStream_t s = as_stream(stream);
+  if (const int err = launch_split_weight(bt, workspace, J, R, 0, s)) return err;
+  TgArgs p{};
+  p.a = a; p.image = (const f16x8*)workspace; p.bias = bias; p.c = c; p.rowmax_out = row_max_out;
   p.a2 = a2; p.ks1 = (int)(R1 / 16); p.act_slope = act_slope; p.row_scale = row_scale; p.amax_out = a_row_max_out;
   p.N = (int)N; p.R = (int)R; p.J = (int)J;
   const size_t lds = (size_t)R * J * 4;
-  const int64_t tiles = (N + 31) / 32;
-  int grid = (int)((tiles + kTgWaves - 1) / kTgWaves);
-  if (grid > 256) grid = 256;
-  bool launched = false;
-#define MLGNN_TG_DUAL(JT_, KS_)                                                                                  \
-  if (!launched && J == 32 * JT_ && R == 16 * KS_) {                                                             \
-    if (const hipError_t e_ = allow_dynamic_lds(&tallgemm_kernel<JT_, KS_, 0, false, false, true>, kTgMaxLds + 4096); \
-        e_ != hipSuccess)                                                                                        \
-      return (int)e_;                                                                                            \
-    hipLaunchKernelGGL((tallgemm_kernel<JT_, KS_, 0, false, false, true>), dim3(grid), dim3(kTgBlock), lds, s, p); \
-    launched = true;                                                                                             \
-  }
-  MLGNN_TG_DUAL(1, 2) MLGNN_TG_DUAL(1, 4) MLGNN_TG_DUAL(1, 8) MLGNN_TG_DUAL(1, 16)
-  MLGNN_TG_DUAL(2, 2) MLGNN_TG_DUAL(2, 4) MLGNN_TG_DUAL(2, 8) MLGNN_TG_DUAL(2, 16)
-  MLGNN_TG_DUAL(4, 2) MLGNN_TG_DUAL(4, 4) MLGNN_TG_DUAL(4, 8) MLGNN_TG_DUAL(4, 16)
-#undef MLGNN_TG_DUAL
-  if (!launched) return MLGNN_E_SHAPE;
-  return (int)hipGetLastError();
+  return tg_launch<TgVariant<0, false, false, true>, TgDualJT, TgDualKS>(p, dim3(tg_grid(N, kTgWaves, 256)),
+                                                                         dim3(kTgBlock), lds, s);
 }
 
 // ---- dA = go W through ReLU + LayerNorm backward in the epilogue (LN = 3 above) --------------------------------------
@@ -787,8 +758,7 @@ constexpr int kTgLnBwdBlocks = 256;        // persistent workgroups = rows of th
 }
 
 extern "C" int mlgnn_tallgemm_lnbwd_supported(int64_t N, int64_t R, int64_t J) {
-  const bool ok = (J == 64 || J == 128 || J == 256) && (R == 64 || R == 128 || R == 256) && R * J * 4 <= kTgMaxLds;
-  return (N > 0 && N <= INT32_MAX && ok) ? 1 : 0;
+  return (N > 0 && N <= INT32_MAX && tg_admits<TgLnJT, TgLnKS>(R, J)) ? 1 : 0;
 }
 
 extern "C" int64_t mlgnn_tallgemm_lnbwd_workspace_bytes(int64_t R, int64_t J) {
@@ -803,23 +773,15 @@ extern "C" int mlgnn_tallgemm_lnbwd(const float* go, const float* w, int w_trans
   if (N < 0 || N > INT32_MAX) return MLGNN_E_SHAPE;
   if (R <= 0 || J <= 0 || !mlgnn_tallgemm_lnbwd_supported(N > 0 ? N : 1, R, J)) return MLGNN_E_SHAPE;
   if (!grad_gamma_beta) return MLGNN_E_NULL;
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = as_stream(stream);
   if (N == 0) return (int)hipMemsetAsync(grad_gamma_beta, 0, 2 * J * sizeof(float), s);
   if (!go || !w || !xhat || !rstd || !gamma || !beta || !grad_h || !row_max_out || !workspace) return MLGNN_E_NULL;
   if (workspace_bytes < mlgnn_tallgemm_lnbwd_workspace_bytes(R, J)) return MLGNN_E_WORKSPACE;
   if (!aligned(go, w, workspace)) return MLGNN_E_ALIGN;
-  const int n_frag_lanes = (int)(R / 16) * (int)(J / 32) * 64;
-  hipLaunchKernelGGL(tallgemm_split_weight_kernel, dim3((n_frag_lanes + 255) / 256), dim3(256), 0, s, w,
-                     (f16x8*)workspace, (int)J, (int)R, w_transposed);
-  int err = (int)hipGetLastError();
-  if (err) return err;
-  TgArgs p;
-  p.image = (const f16x8*)workspace; p.bias = nullptr; p.res = nullptr;
-  p.gamma = gamma; p.beta = beta; p.rstd_out = nullptr; p.ln_eps = 0.f;
+  if (const int err = launch_split_weight(w, workspace, J, R, w_transposed, s)) return err;
+  TgArgs p{};
+  p.image = (const f16x8*)workspace; p.gamma = gamma; p.beta = beta;
   p.ws = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + R * J * 4 + kTgHeader * 16);
-  p.a2 = nullptr; p.ks1 = 0; p.act_slope = 1.f; p.row_scale = nullptr; p.amax_out = nullptr;
-  p.pgamma = nullptr; p.pbeta = nullptr; p.y = nullptr; p.mean_out = nullptr; p.peps = 0.f; p.prelu = 0;
-  p.rowptr = nullptr; p.spread = nullptr;
   p.R = (int)R; p.J = (int)J;
   size_t lds = (size_t)R * J * 4 + (size_t)J * 8;                        // weight image, then gamma / beta of the J columns
   if (lds < (size_t)kTgWaves * 2 * J * 4) lds = (size_t)kTgWaves * 2 * J * 4;   // ... re-used for the partials at the end
@@ -832,25 +794,8 @@ extern "C" int mlgnn_tallgemm_lnbwd(const float* go, const float* w, int w_trans
     p.a = go + r0 * R; p.rowmax = row_max ? row_max + r0 : nullptr; p.c = grad_h + r0 * J;
     p.rowmax_out = row_max_out + r0; p.xhat = xhat + r0 * J; p.rstd_in = rstd + r0;
     p.N = (int)n;
-    const int64_t tiles = (n + 31) / 32;
-    int grid = (int)((tiles + waves - 1) / waves);
-    if (grid > kTgLnBwdBlocks) grid = kTgLnBwdBlocks;
-    const dim3 g(grid), b(block);
-    bool launched = false;
-#define MLGNN_TG_LNBWD(JT_, KS_)                                                                      \
-  if (!launched && J == 32 * JT_ && R == 16 * KS_) {                                                  \
-    if (const hipError_t e_ = allow_dynamic_lds(&tallgemm_kernel<JT_, KS_, 3>, kTgMaxLds + 4096); e_ != hipSuccess) \
-      return (int)e_;                                                                                 \
-    hipLaunchKernelGGL((tallgemm_kernel<JT_, KS_, 3>), g, b, lds, s, p);                               \
-    launched = true;                                                                                  \
-  }
-    MLGNN_TG_LNBWD(2, 4) MLGNN_TG_LNBWD(2, 8) MLGNN_TG_LNBWD(2, 16)
-    MLGNN_TG_LNBWD(4, 4) MLGNN_TG_LNBWD(4, 8) MLGNN_TG_LNBWD(4, 16)
-    MLGNN_TG_LNBWD(8, 4) MLGNN_TG_LNBWD(8, 8)
-#undef MLGNN_TG_LNBWD
-    if (!launched) return MLGNN_E_SHAPE;
-    err = (int)hipGetLastError();
-    if (err) return err;
+    const int grid = tg_grid(n, waves, kTgLnBwdBlocks);
+    if (const int err = tg_launch<TgVariant<3>, TgLnJT, TgLnKS>(p, dim3(grid), dim3(block), lds, s)) return err;
     launch_reduce_partials(p.ws, grad_gamma_beta, grid, 2 * (int)J, s, r0 > 0);
   }
   return (int)hipGetLastError();

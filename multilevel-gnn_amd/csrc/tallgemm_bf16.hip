@@ -15,15 +15,12 @@
 // 64 u + 2 c + (0, 1) -- so that a lane packs its two results into one 4-byte store and a half wave writes 128
 // contiguous bytes of a row (2-byte stores of the natural layout would touch 64-byte pieces).  The permutation is
 // free: it only changes which weight row goes where in the LDS image.
-#include "common.h"
+#include "split_precision.h"
 #include "launch.h"
 #include "dense_bf16.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
-
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 constexpr int kTbBlock = 512;
 constexpr int kTbWaves = kTbBlock / kWave;
@@ -98,7 +95,7 @@ __global__ __launch_bounds__(kTbBlock) void tallgemm_bf16_kernel(const TbArgs p)
     if constexpr (kPrefetchLse) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = min(row0 + (r & 3) + 8 * (r >> 2) + 4 * h, p.N - 1);
+        const int row = min(row0 + mfma32_row(r, h), p.N - 1);
         const size_t base = (size_t)row * p.J + j0;
 #pragma unroll
         for (int u = 0; u < RP; ++u) lsew[u][r] = *reinterpret_cast<const float2*>(p.lse + base + 64 * u + 2 * r31);
@@ -107,7 +104,7 @@ __global__ __launch_bounds__(kTbBlock) void tallgemm_bf16_kernel(const TbArgs p)
     if (!SHIFT && kPrefetchRes && p.res) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = min(row0 + (r & 3) + 8 * (r >> 2) + 4 * h, p.N - 1);
+        const int row = min(row0 + mfma32_row(r, h), p.N - 1);
         const size_t base = (size_t)row * p.J + j0;
 #pragma unroll
         for (int u = 0; u < RP; ++u) {
@@ -146,7 +143,7 @@ __global__ __launch_bounds__(kTbBlock) void tallgemm_bf16_kernel(const TbArgs p)
     // C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int row = row0 + mfma32_row(r, h);
       if (row >= p.N) continue;
       const size_t base = (size_t)row * p.J + j0;
       if constexpr (JT == 1) {

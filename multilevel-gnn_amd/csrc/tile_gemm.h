@@ -2,12 +2,10 @@
 // small pooled-graph kernels (diffpool.hip, densesage.hip): lane l supplies A[i = l & 15][k = l >> 4]
 // and B[k = l >> 4][j = l & 15] per k-step of 4; C/D: col = l & 15, row = 4 * (l >> 4) + reg.
 #pragma once
-#include "common.h"
+#include "split_precision.h"
 #include "dispatch.h"
 
 namespace mlgnn {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // acc[i][j] = sum_k a_at(i, k) * b_at(k, j).  The accessors return 0 for every k at or past the end of
 // their operand (the loop runs in blocks of kTileUnroll k-steps: all operand loads of a block are issued

@@ -22,18 +22,15 @@
 // product at worst, rms far below), smaller ones lose them gradually down to 2^-38 of the maximum; half the MFMAs and
 // two LDS planes instead of three: 0.29 -> 0.21 ms at 640 000 x 128 x 256.
 #include <type_traits>
+#include <utility>
 
-#include "common.h"
+#include "split_precision.h"
+#include "wgrad_plan.h"
 #include "launch.h"
 #include "dense_bf16.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-constexpr int kTile = 32;
 
 struct WgradArgs {
   const float* a; const float* b; float* ws;
@@ -46,45 +43,11 @@ struct WgradArgs {
   int slot0;                              // workspace slot of workgroup 0
 };
 
-// Stage = 32 rows when the operand tiles fit the LDS budget (64 KB single buffered, 144 KB double buffered),
-// 16 rows for the widest layouts.
 constexpr int kSlabAlign = 32;          // the fast launch covers a multiple of this many rows (both stage sizes)
-constexpr int stage_rows(int W, bool db) { return db ? (W <= 384 ? 32 : 16) : (W <= 320 ? 32 : 16); }
-constexpr bool lds_fits(int W, bool db) { return (db ? 12 : 6) * stage_rows(W, db) * W <= 160 * 1024; }
-
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-
-// exact three-way split of 8 floats, two at a time (v_cvt_pk_bf16_f32 rounds to nearest even; the
-// widening back is a shift / mask of the packed word)
-__device__ __forceinline__ void split3(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-  u32x4 hw, mw, lw;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const f32x2 x = {v[2 * j], v[2 * j + 1]};
-    const uint32_t hp = __builtin_bit_cast(uint32_t, __builtin_convertvector(x, bf16x2));
-    const f32x2 r1 = {x[0] - __builtin_bit_cast(float, hp << 16), x[1] - __builtin_bit_cast(float, hp & 0xffff0000u)};
-    const uint32_t mp = __builtin_bit_cast(uint32_t, __builtin_convertvector(r1, bf16x2));
-    const f32x2 r2 = {r1[0] - __builtin_bit_cast(float, mp << 16), r1[1] - __builtin_bit_cast(float, mp & 0xffff0000u)};
-    const uint32_t lp = __builtin_bit_cast(uint32_t, __builtin_convertvector(r2, bf16x2));
-    hw[j] = hp; mw[j] = mp; lw[j] = lp;
-  }
-  h = __builtin_bit_cast(bf16x8, hw); m = __builtin_bit_cast(bf16x8, mw); l = __builtin_bit_cast(bf16x8, lw);
-}
-
-// power of two s with  max * s in [2^13, 2^14)  and its inverse; max = 0 or denormal -> 1  (as in tallgemm.hip)
-__device__ __forceinline__ void wg_pow2_scale(float max_abs, float& s, float& inv) {
-  int e = (int)((__builtin_bit_cast(uint32_t, max_abs) >> 23) & 0xff);       // biased exponent
-  e = min(max(e, 20), 234);
-  s = __builtin_bit_cast(float, (uint32_t)(254 + 13 - e) << 23);
-  inv = __builtin_bit_cast(float, (uint32_t)(e - 13) << 23);
-}
 
 // F16: the operands' global maxima come from the row maxima their producers wrote ([N] each): kMaxParts slices are
-// reduced by a small launch in front, every wave of the main kernel folds the partials itself (no atomics, no host
-// round trip, one launch instead of two library reductions)
-constexpr int kMaxParts = 256;
+// reduced by a small launch in front, every wave of the main kernel folds the partials itself (fold_max_parts: one
+// launch instead of two library reductions)
 __global__ __launch_bounds__(256) void rowmax_partials_kernel(const float* __restrict__ a_rm, const float* __restrict__ b_rm,
                                                               int n, float* __restrict__ part) {
   __shared__ float red[2][4];
@@ -99,26 +62,6 @@ __global__ __launch_bounds__(256) void rowmax_partials_kernel(const float* __res
   if (threadIdx.x == 0) {
     part[blockIdx.x] = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
     part[kMaxParts + blockIdx.x] = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
-  }
-}
-__device__ __forceinline__ float fold_max_parts(const float* part) {          // the same value in every lane
-  const int lane = threadIdx.x & (kWave - 1);
-  float m = 0.f;
-#pragma unroll
-  for (int i = 0; i < kMaxParts / kWave; ++i) m = fmaxf(m, part[lane + i * kWave]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-  return m;
-}
-
-// scaled two-way split of 8 floats: hi = fp16(x s), lo = fp16(x s - hi)
-__device__ __forceinline__ void split2(const float (&v)[8], float s, f16x8& h, f16x8& l) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float x = v[j] * s;
-    const _Float16 hh = (_Float16)x;
-    h[j] = hh;
-    l[j] = (_Float16)(x - (float)hh);
   }
 }
 
@@ -197,8 +140,8 @@ __global__ __launch_bounds__(NW * kWave) void linear_wgrad_kernel(const WgradArg
   float sa = 1.f, sb = 1.f, unscale = 1.f;        // F16: operand scales (exact powers of two) and their inverse product
   if constexpr (F16) {
     float ia, ib;
-    wg_pow2_scale(fold_max_parts(p.a_max), sa, ia);
-    wg_pow2_scale(fold_max_parts(p.b_max), sb, ib);
+    pow2_scale(fold_max_parts(p.a_max), sa, ia);
+    pow2_scale(fold_max_parts(p.b_max), sb, ib);
     unscale = ia * ib;
   }
   constexpr int kSets = DB ? 2 : 1;               // DB: two stages of loads in flight (register sets by stage parity)
@@ -369,7 +312,7 @@ __global__ __launch_bounds__(NW * kWave) void linear_wgrad_kernel(const WgradArg
       const int k = k_base + j * kTile + l31;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int m = m_base + i * kTile + (r & 3) + 8 * (r >> 2) + 4 * half;    // C/D layout of 32x32 MFMA
+        const int m = m_base + i * kTile + mfma32_row(r, half);
         if (m < p.M && k < p.K) out[(size_t)m * p.K + k] = F16 ? acc[i][j][r] * unscale : acc[i][j][r];
       }
     }
@@ -387,28 +330,6 @@ __global__ __launch_bounds__(NW * kWave) void linear_wgrad_kernel(const WgradArg
   }
 }
 
-struct WgradPlan { int nw, wm, wk, tm, tk; };
-
-// cheapest (wave layout) x (tiles per wave) that covers tiles_m x tiles_k with <= 4 tiles (64 accumulator
-// registers) per wave: 4 waves up to 16 tiles, 8 waves (double buffered, one workgroup per CU) up to 32
-static bool plan_wgrad(int tiles_m, int tiles_k, WgradPlan* out) {
-  static const int layouts[7][3] = {{4, 2, 2}, {4, 4, 1}, {4, 1, 4}, {8, 4, 2}, {8, 2, 4}, {8, 8, 1}, {8, 1, 8}};
-  static const int shapes[6][2] = {{1, 1}, {1, 2}, {2, 1}, {2, 2}, {1, 4}, {4, 1}};
-  int best = 1 << 30;
-  bool found = false;
-  for (auto& lay : layouts)
-    for (auto& sh : shapes) {
-      const int tm = sh[0], tk = sh[1];
-      if (lay[0] == 8 && tm * tk != 4) continue;                 // 8 waves only where 4 waves run out of registers
-      if (lay[1] * tm < tiles_m || lay[2] * tk < tiles_k) continue;
-      if (!lds_fits((lay[1] * tm + lay[2] * tk) * kTile, lay[0] == 8)) continue;
-      // padded MFMA work, then operand loads per wave, then prefer the smaller workgroup
-      const int cost = ((lay[1] * tm) * (lay[2] * tk) * 16 + (tm + tk)) * 2 + (lay[0] == 8);
-      if (cost < best) { best = cost; *out = {lay[0], lay[1], lay[2], tm, tk}; found = true; }
-    }
-  return found;
-}
-
 static int wgrad_blocks(int64_t N, const WgradPlan& pl) {
   int64_t b = (N + 511) / 512;            // at least 512 rows per slab
   const int64_t cap = pl.nw == 8 ? 256 : 512;     // one 8-wave or two 4-wave workgroups per CU
@@ -417,27 +338,20 @@ static int wgrad_blocks(int64_t N, const WgradPlan& pl) {
   return (int)b;
 }
 
-template <bool MASKED, bool F16>
-static bool launch_wgrad(const WgradPlan& pl, const WgradArgs& a, int nblk, hipStream_t s) {
-  const dim3 grid(nblk);
-  bool launched = false;
-#define MLGNN_WG_CASE(NW_, WM_, WK_, TM_, TK_)                                                       \
-  if (pl.nw == NW_ && pl.wm == WM_ && pl.wk == WK_ && pl.tm == TM_ && pl.tk == TK_) {                \
-    hipLaunchKernelGGL((linear_wgrad_kernel<NW_, WM_, WK_, TM_, TK_, NW_ == 8, MASKED, F16>), grid,  \
-                       dim3(NW_ * kWave), 0, s, a);                                                  \
-    launched = true;                                                                                 \
-  }
-#define MLGNN_WG_LAYOUT4(WM_, WK_)                                                                   \
-  MLGNN_WG_CASE(4, WM_, WK_, 1, 1) MLGNN_WG_CASE(4, WM_, WK_, 1, 2) MLGNN_WG_CASE(4, WM_, WK_, 2, 1) \
-  MLGNN_WG_CASE(4, WM_, WK_, 2, 2) MLGNN_WG_CASE(4, WM_, WK_, 1, 4) MLGNN_WG_CASE(4, WM_, WK_, 4, 1)
-  MLGNN_WG_LAYOUT4(2, 2) MLGNN_WG_LAYOUT4(4, 1) MLGNN_WG_LAYOUT4(1, 4)
-  MLGNN_WG_CASE(8, 4, 2, 2, 2) MLGNN_WG_CASE(8, 4, 2, 1, 4) MLGNN_WG_CASE(8, 4, 2, 4, 1)
-  MLGNN_WG_CASE(8, 2, 4, 2, 2) MLGNN_WG_CASE(8, 2, 4, 1, 4) MLGNN_WG_CASE(8, 2, 4, 4, 1)
-  MLGNN_WG_CASE(8, 8, 1, 2, 2) MLGNN_WG_CASE(8, 8, 1, 1, 4)          // (8,1,4,1) / (1,8,1,4): 1056-wide tiles exceed LDS
-  MLGNN_WG_CASE(8, 1, 8, 2, 2) MLGNN_WG_CASE(8, 1, 8, 4, 1)
-#undef MLGNN_WG_LAYOUT4
-#undef MLGNN_WG_CASE
-  return launched;
+// launch the instantiation of row `row` of kWgradTable (csrc/wgrad_plan.h); a row outside the table launches nothing
+template <bool MASKED, bool F16, size_t... I>
+static bool launch_wgrad_row(int row, const WgradArgs& a, int nblk, hipStream_t s, std::index_sequence<I...>) {
+  auto launch = [&](auto i) {
+    constexpr WgradPlan pl = kWgradTable.row[decltype(i)::value];
+    hipLaunchKernelGGL((linear_wgrad_kernel<pl.nw, pl.wm, pl.wk, pl.tm, pl.tk, pl.nw == 8, MASKED, F16>), dim3(nblk),
+                       dim3(pl.nw * kWave), 0, s, a);
+  };
+  return dispatch_int<(int)I...>(row, launch);
+}
+static bool launch_wgrad(int row, bool masked, bool f16, const WgradArgs& a, int nblk, hipStream_t s) {
+  constexpr auto rows = std::make_index_sequence<kWgradRows>{};
+  if (masked) return f16 ? launch_wgrad_row<true, true>(row, a, nblk, s, rows) : launch_wgrad_row<true, false>(row, a, nblk, s, rows);
+  return f16 ? launch_wgrad_row<false, true>(row, a, nblk, s, rows) : launch_wgrad_row<false, false>(row, a, nblk, s, rows);
 }
 
 }  // namespace mlgnn
@@ -452,9 +366,9 @@ extern "C" int64_t mlgnn_linear_wgrad_workspace_floats(int64_t N, int64_t M, int
     return slabs > 0 ? (int64_t)slabs * (M * K + M) : (int64_t)MLGNN_E_SHAPE;
   }
   if (dtype != MLGNN_DTYPE_F32) return MLGNN_E_DTYPE;
-  WgradPlan pl;
-  if (!plan_wgrad((int)((M + kTile - 1) / kTile), (int)((K + kTile - 1) / kTile), &pl)) return MLGNN_E_SHAPE;
-  return (int64_t)(wgrad_blocks(N, pl) + 1) * (M * K + M) + 2 * kMaxParts;      // partials per slab, then the operands' maxima
+  const int row = plan_wgrad((int)((M + kTile - 1) / kTile), (int)((K + kTile - 1) / kTile));
+  if (row < 0) return MLGNN_E_SHAPE;
+  return (int64_t)(wgrad_blocks(N, kWgradTable.row[row]) + 1) * (M * K + M) + 2 * kMaxParts;      // partials per slab, then the operands' maxima
 }
 
 extern "C" int mlgnn_linear_wgrad(const void* grad_out, const void* x, const float* x_gamma, const float* x_beta,
@@ -467,22 +381,23 @@ extern "C" int mlgnn_linear_wgrad(const void* grad_out, const void* x, const flo
     if (slabs <= 0) return MLGNN_E_SHAPE;
     if (x_gamma || x_beta) return MLGNN_E_MODE;
     if (!grad_w_b || !workspace) return MLGNN_E_NULL;
-    if (N == 0) return (int)hipMemsetAsync(grad_w_b, 0, (size_t)(M * K + M) * sizeof(float), (hipStream_t)stream);
+    if (N == 0) return (int)hipMemsetAsync(grad_w_b, 0, (size_t)(M * K + M) * sizeof(float), as_stream(stream));
     if (!grad_out || !x) return MLGNN_E_NULL;
     if (workspace_floats < (int64_t)slabs * (M * K + M)) return MLGNN_E_WORKSPACE;
     if (!aligned(grad_out, x)) return MLGNN_E_ALIGN;
-    return linear_wgrad_bf16(grad_out, x, grad_w_b, workspace, N, M, K, (hipStream_t)stream);
+    return linear_wgrad_bf16(grad_out, x, grad_w_b, workspace, N, M, K, as_stream(stream));
   }
   if (dtype != MLGNN_DTYPE_F32) return MLGNN_E_DTYPE;
   if (N < 0 || M <= 0 || K <= 0 || N > INT32_MAX || M * K > (1 << 24)) return MLGNN_E_SHAPE;
-  WgradPlan pl;
-  if (!plan_wgrad((int)((M + kTile - 1) / kTile), (int)((K + kTile - 1) / kTile), &pl)) return MLGNN_E_SHAPE;
+  const int row = plan_wgrad((int)((M + kTile - 1) / kTile), (int)((K + kTile - 1) / kTile));
+  if (row < 0) return MLGNN_E_SHAPE;
+  const WgradPlan& pl = kWgradTable.row[row];
   if (!grad_w_b || !workspace) return MLGNN_E_NULL;
   if (N > 0 && (!grad_out || !x)) return MLGNN_E_NULL;
   const int nblk = wgrad_blocks(N, pl);
   const int cols = (int)(M * K + M);
   if (workspace_floats < (int64_t)(nblk + 1) * cols + 2 * kMaxParts) return MLGNN_E_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = as_stream(stream);
   WgradArgs a;
   a.ws = workspace;
   a.b_gamma = x_gamma; a.b_beta = x_gamma ? x_beta : nullptr;
@@ -509,13 +424,13 @@ extern "C" int mlgnn_linear_wgrad(const void* grad_out, const void* x, const flo
     int slots = 0;
     if (main_rows > 0) {
       a.row0 = 0; a.rows = main_rows; a.slot0 = 0;
-      if (!(f16 ? launch_wgrad<false, true>(pl, a, nb_main, s) : launch_wgrad<false, false>(pl, a, nb_main, s))) return MLGNN_E_SHAPE;
+      if (!launch_wgrad(row, false, f16, a, nb_main, s)) return MLGNN_E_SHAPE;
       slots = nb_main;
     }
     if (main_rows < n || n == 0) {
       a.row0 = main_rows; a.rows = (int)n - main_rows; a.slot0 = slots;
       const int nb = padded ? nb_main : 1;
-      if (!(f16 ? launch_wgrad<true, true>(pl, a, nb, s) : launch_wgrad<true, false>(pl, a, nb, s))) return MLGNN_E_SHAPE;
+      if (!launch_wgrad(row, true, f16, a, nb, s)) return MLGNN_E_SHAPE;
       slots += nb;
     }
     int err = (int)hipGetLastError();

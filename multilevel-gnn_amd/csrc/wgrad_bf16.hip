@@ -16,15 +16,13 @@
 // stage s.  blockIdx = (slab, M block, K block); per-slab fp32 partials are summed in fixed order afterwards.
 // Traffic: every M block streams x once and every K block streams grad_out once -- 2 passes over one of them at
 // 512 x 256 -- against 2 N M K FLOP that take a fifth of that time on the bf16 matrix cores: HBM-bound.
-#include "common.h"
+#include "split_precision.h"
 #include "launch.h"
 #include "dense_bf16.h"
 #include "mlgnn.h"
 
 namespace mlgnn {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 typedef short short4_t __attribute__((ext_vector_type(4)));
 typedef short short8_t __attribute__((ext_vector_type(8)));
 
@@ -179,7 +177,9 @@ __global__ __launch_bounds__(kWbBlock) void linear_wgrad_bf16_kernel(const WbArg
   }
 }
 
-// tiles per wave along M (64 TM | M) and K (128 TK | K); 0 = shape not covered
+// tiles per wave along M (64 TM | M) and K (128 TK | K); 0 = shape not covered.  The launcher instantiates WbTM x WbTK.
+using WbTM = IntList<1, 2, 4>;
+using WbTK = IntList<1, 2>;
 static void wb_plan(int64_t M, int64_t K, int* tm, int* tk) {
   *tm = *tk = 0;
   if (M <= 0 || K <= 0 || M % 64 != 0 || K % 128 != 0 || M > 4096 || K > 4096) return;
@@ -209,16 +209,17 @@ int linear_wgrad_bf16(const void* grad_out, const void* x, float* grad_w_b, floa
   a.go = (const uint16_t*)grad_out; a.x = (const uint16_t*)x; a.ws = workspace;
   a.N = (int)N; a.M = (int)M; a.K = (int)K; a.out_cols = (int)(M * K + M);
   const dim3 grid(slabs, (unsigned)(M / (64 * tm)), (unsigned)(K / (128 * tk))), block(kWbBlock);
-#define MLGNN_WB_CASE(TM_, TK_)                                                                               \
-  if (tm == TM_ && tk == TK_) {                                                                               \
-    const int lds = 2 * kWbStage * (wb_stride(64 * TM_) + wb_stride(128 * TK_));                              \
-    if (const hipError_t e_ = allow_dynamic_lds(&linear_wgrad_bf16_kernel<TM_, TK_>, lds); e_ != hipSuccess)  \
-      return (int)e_;                                                                                         \
-    hipLaunchKernelGGL((linear_wgrad_bf16_kernel<TM_, TK_>), grid, block, lds, s, a);                         \
-  }
-  MLGNN_WB_CASE(4, 2) MLGNN_WB_CASE(4, 1) MLGNN_WB_CASE(2, 2) MLGNN_WB_CASE(2, 1) MLGNN_WB_CASE(1, 2) MLGNN_WB_CASE(1, 1)
-#undef MLGNN_WB_CASE
-  int err = (int)hipGetLastError();
+  int err = MLGNN_E_SHAPE;
+  WbTM::dispatch(tm, [&](auto tm_c) {
+    WbTK::dispatch(tk, [&](auto tk_c) {
+      constexpr int TM = decltype(tm_c)::value, TK = decltype(tk_c)::value;
+      constexpr int lds = 2 * kWbStage * (wb_stride(64 * TM) + wb_stride(128 * TK));
+      err = (int)allow_dynamic_lds(&linear_wgrad_bf16_kernel<TM, TK>, lds);
+      if (err) return;
+      hipLaunchKernelGGL((linear_wgrad_bf16_kernel<TM, TK>), grid, block, lds, s, a);
+      err = (int)hipGetLastError();
+    });
+  });
   if (err) return err;
   launch_reduce_partials(workspace, grad_w_b, slabs, a.out_cols, s);
   return (int)hipGetLastError();

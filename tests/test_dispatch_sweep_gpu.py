@@ -1,7 +1,9 @@
 """One case per label of every host-side value ladder (csrc/dispatch.h ``dispatch_int``): LayerNorm / MsgNorm lane layouts,
 the lanes-per-row streams of csrc/sage.hip, narrow linear (lanes x R), projection (storage x 16-byte / scalar x K), the
-short-row aggregation widths and the bf16 tall GEMM's tiles per slice.  Shapes are tiny; each case checks against the
-reference and the tolerance of the op's own test file (named at each test), which skips some of these labels."""
+short-row aggregation widths, the bf16 tall GEMM's tiles per slice, every (column tiles, k-steps) pair of the fp32 tall
+GEMM's families (csrc/tallgemm.hip) and every reachable row of the fp32 weight gradient's plan table
+(csrc/wgrad_plan.h).  Shapes are tiny; each case checks against the reference and the tolerance of the op's own test
+file (named at each test), which skips some of these labels."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -298,3 +300,179 @@ def test_bf16_tall_gemm_tiles_per_slice(R, J):
     res = torch.randint(-5, 6, (N, J), generator=gen).float()
     out = tall_matmul_nt(bf(a), bf(bt), bias.to(DEV), bf(res))
     assert float((ref + res).abs().max()) < 256 and torch.equal(out.float().cpu(), ref + res)
+
+
+# ---- csrc/tallgemm.hip: (J / 32 column tiles, R / 16 k-steps) of every family --------------------------------------
+# N = 65: two full 32-row tiles and a one-row tail
+
+TG_N = 65
+TG_PLAIN = [(R, J) for R in (16, 32, 64, 128, 256) for J in (32, 64, 128, 256) if (R, J) != (256, 256)]
+TG_LN = [(R, J) for R in (64, 128, 256) for J in (64, 128, 256) if (R, J) != (256, 256)]
+TG_EPI = [(R, J) for R in (64, 128, 256) for J in (64, 128)]
+TG_DUAL = [(R, J) for R in (32, 64, 128, 256) for J in (32, 64, 128)]
+
+
+@pytest.mark.parametrize("R,J", TG_PLAIN)
+def test_tall_gemm_plain_tiles(R, J):
+    """The 19 plain instantiations, each also with the weight read transposed in place.  Exact on small integers, as
+    tests/test_tallgemm_gpu.py::test_layout_is_exact_on_small_integers."""
+    from mlgnn.dense import tall_matmul_nt, tall_matmul_supported
+    assert tall_matmul_supported(TG_N, R, J)
+    gen = torch.Generator().manual_seed(R * 7 + J)
+    a = torch.randint(-4, 5, (TG_N, R), generator=gen).float()
+    bt = torch.randint(-3, 4, (J, R), generator=gen).float()
+    bt[:, 0] += torch.arange(J) % 5                              # asymmetric: a transposed tile cannot pass
+    bias = torch.randint(-2, 3, (J,), generator=gen).float()
+    ref = a @ bt.t() + bias
+    ad, btd, bd = a.to(DEV), bt.to(DEV), bias.to(DEV)
+    assert torch.equal(tall_matmul_nt(ad, btd, bd).cpu(), ref)
+    assert torch.equal(tall_matmul_nt(ad, btd.t().contiguous(), bd, bt_transposed=True).cpu(), ref)
+
+
+def _ln_operands(R, J, seed):
+    gen = torch.Generator().manual_seed(seed)
+    a = torch.randn(TG_N, R, generator=gen)
+    w = torch.randn(J, R, generator=gen) / R ** 0.5
+    bias = torch.randn(J, generator=gen) * 0.3
+    return gen, a, w, bias
+
+
+@pytest.mark.parametrize("R,J", TG_LN)
+def test_tall_gemm_layernorm_out_tiles(R, J):
+    """``ln = ("out", ...)``: normalised rows, 1 / sigma and max relu(gamma xhat + beta) per row against fp64; the bound of
+    the fused MLP that is built from this product (tests/test_norm_gpu.py, 1e-4, elementwise)."""
+    from mlgnn.dense import tall_matmul_nt
+    gen, a, w, bias = _ln_operands(R, J, R + 3 * J)
+    gamma, beta = torch.rand(J, generator=gen) + 0.5, torch.randn(J, generator=gen) * 0.3
+    v = a.double() @ w.double().t() + bias.double()
+    mu, var = v.mean(1, keepdim=True), v.var(1, unbiased=False, keepdim=True)
+    rstd_ref = 1.0 / torch.sqrt(var + 1e-5)
+    xhat_ref = (v - mu) * rstd_ref
+    xhat, rstd, rmax = tall_matmul_nt(a.to(DEV), w.to(DEV), bias.to(DEV), ln=("out", gamma.to(DEV), beta.to(DEV), 1e-5))
+    assert_close(xhat, xhat_ref, 1e-4, "xhat", elementwise=True)
+    assert_close(rstd, rstd_ref.squeeze(1), 1e-4, "rstd", elementwise=True)
+    assert_close(rmax, torch.relu(xhat_ref * gamma.double() + beta.double()).amax(1), 1e-4, "row max", elementwise=True)
+
+
+@pytest.mark.parametrize("R,J", TG_LN)
+def test_tall_gemm_layernorm_in_tiles(R, J):
+    """``ln = ("in", ...)``: relu(gamma a + beta) applied to the operand as it is loaded, against fp64; bound as above."""
+    from mlgnn.dense import tall_matmul_nt
+    gen, a, w, bias = _ln_operands(R, J, 5 * R + J)
+    gamma, beta = torch.rand(R, generator=gen) + 0.5, torch.randn(R, generator=gen) * 0.3
+    ref = torch.relu(a.double() * gamma.double() + beta.double()) @ w.double().t() + bias.double()
+    out = tall_matmul_nt(a.to(DEV), w.to(DEV), bias.to(DEV), ln=("in", gamma.to(DEV), beta.to(DEV)))
+    assert_close(out, ref, 1e-4, "out", elementwise=True)
+
+
+@pytest.mark.parametrize("R,J", TG_EPI)
+def test_tall_gemm_post_layernorm_tiles(R, J):
+    """POST: the LN-in product (+ bias + residual) and a second LayerNorm + ReLU of its rows, against fp64; bound of
+    tests/test_norm_gpu.py::test_fused_mlp2_with_the_next_norm_in_its_epilogue (1e-4, elementwise)."""
+    from mlgnn.dense import tall_matmul_lnin_postln
+    gen, a, w, bias = _ln_operands(R, J, 11 * R + J)
+    gamma, beta = torch.rand(R, generator=gen) + 0.5, torch.randn(R, generator=gen) * 0.3
+    g2, b2 = torch.rand(J, generator=gen) + 0.5, torch.randn(J, generator=gen) * 0.3
+    res = torch.randn(TG_N, J, generator=gen)
+    ref = torch.relu(a.double() * gamma.double() + beta.double()) @ w.double().t() + bias.double() + res.double()
+    y_ref = torch.relu(F.layer_norm(ref, (J,), g2.double(), b2.double(), 1e-5))
+    d = lambda t: t.to(DEV)
+    out, y, mean, rstd = tall_matmul_lnin_postln(d(a), d(w), d(bias), d(res), None, d(gamma), d(beta), (d(g2), d(b2), 1e-5, True))
+    assert_close(out, ref, 1e-4, "out", elementwise=True)
+    assert_close(y, y_ref, 1e-4, "y", elementwise=True)
+    assert_close(mean, ref.mean(1), 1e-4, "mean", elementwise=True)
+    assert_close(rstd, 1.0 / torch.sqrt(ref.var(1, unbiased=False) + 1e-5), 1e-4, "rstd", elementwise=True)
+
+
+@pytest.mark.parametrize("R,J", TG_EPI)
+def test_tall_gemm_shift_tiles(R, J):
+    """SHIFT: the input gradient ``a w`` and its copy rescaled by 2^(-lse) (rows without incoming edges: zero), against
+    fp64; bound as above (1e-4, elementwise).  The product itself is the plain kernel's, bit for bit."""
+    from mlgnn.dense import tall_matmul_nt, tall_matmul_nt_shift
+    gen = torch.Generator().manual_seed(13 * R + J)
+    a = torch.randn(TG_N, R, generator=gen)
+    w = torch.randn(R, J, generator=gen) / R ** 0.5
+    lse = torch.randn(TG_N, J, generator=gen) * 4
+    deg = torch.randint(0, 3, (TG_N,), generator=gen)                          # some rows without incoming edges
+    rowptr = torch.cat([torch.zeros(1, dtype=torch.long), deg.cumsum(0)]).int()
+    ref = a.double() @ w.double()
+    gx, gt, flag = tall_matmul_nt_shift(a.to(DEV), w.to(DEV), None, lse.to(DEV), rowptr.to(DEV))
+    assert_close(gx, ref, 1e-4, "gx", elementwise=True)
+    assert torch.equal(gx, tall_matmul_nt(a.to(DEV), w.to(DEV), bt_transposed=True))
+    assert_close(gt, ref * torch.exp2(-lse.double()) * (deg > 0)[:, None], 1e-4, "gt", elementwise=True)
+    assert int(flag[0]) == 0
+
+
+@pytest.mark.parametrize("split", [False, True])
+@pytest.mark.parametrize("R,J", TG_DUAL)
+def test_tall_gemm_dual_tiles(R, J, split):
+    """DUAL through the C ABI: leaky_relu([a | a2] W^T + b) * mask with one operand (R2 = 0) and with two of equal
+    width, the row maxima of the result and of the operand; bound of tests/test_sage_layer_gpu.py (1e-4, elementwise)."""
+    from mlgnn import _lib
+    R1 = R // 2 if split else R
+    R2 = R - R1
+    gen = torch.Generator().manual_seed(17 * R + J + split)
+    x = torch.randn(TG_N, R, generator=gen)
+    w = torch.randn(J, R, generator=gen) / R ** 0.5
+    bias = torch.randn(J, generator=gen) * 0.3
+    mask = (torch.rand(TG_N, generator=gen) < 0.8).float()
+    ref = F.leaky_relu(x.double() @ w.double().t() + bias.double(), 0.2) * mask.double()[:, None]
+    assert _lib.lib.mlgnn_tallgemm_dual_supported(TG_N, R1, R2, J)
+    a, a2 = x[:, :R1].contiguous().to(DEV), (x[:, R1:].contiguous().to(DEV) if split else None)
+    y = torch.empty(TG_N, J, device=DEV)
+    y_max, a_max = torch.empty(TG_N, device=DEV), torch.empty(TG_N, device=DEV)
+    ws, nbytes = _lib.workspace("mlgnn_tallgemm_workspace_bytes", R, J, 0, device=y.device)
+    _lib.call("mlgnn_tallgemm_dual", a, a2, w.to(DEV), bias.to(DEV), 0.2, mask.to(DEV), y, y_max, a_max, ws, nbytes,
+              TG_N, R1, R2, J, _lib.stream())
+    assert_close(y, ref, 1e-4, "y", elementwise=True)
+    assert torch.equal(y_max, y.abs().amax(1))
+    assert torch.equal(a_max.cpu(), x.abs().amax(1))
+
+
+@pytest.mark.parametrize("R,J", TG_LN)
+def test_tall_gemm_layernorm_backward_tiles(R, J):
+    """The 8 LN-backward instantiations at N = 65: reference and bounds of
+    tests/test_tallgemm_gpu.py::test_layernorm_backward_epilogue_vs_fp64 (its own body, at this size)."""
+    from test_tallgemm_gpu import test_layernorm_backward_epilogue_vs_fp64 as lnbwd_vs_fp64
+    lnbwd_vs_fp64(TG_N, R, J)
+
+
+# ---- csrc/wgrad_plan.h: one shape per reachable row of the launch table ---------------------------------------------
+# (M, K) = 32 x the fewest tiles that select the row -> (waves, wave layout, tiles per wave) of that row
+
+WG_ROWS = {(32, 32): (4, 2, 2, 1, 1), (64, 96): (4, 2, 2, 1, 2), (96, 64): (4, 2, 2, 2, 1), (96, 96): (4, 2, 2, 2, 2),
+           (96, 32): (4, 4, 1, 1, 1), (160, 32): (4, 4, 1, 2, 1), (160, 64): (4, 4, 1, 2, 2), (288, 32): (4, 4, 1, 4, 1),
+           (32, 96): (4, 1, 4, 1, 1), (32, 160): (4, 1, 4, 1, 2), (64, 160): (4, 1, 4, 2, 2), (32, 288): (4, 1, 4, 1, 4),
+           (160, 96): (8, 4, 2, 2, 2), (96, 160): (8, 2, 4, 2, 2), (288, 64): (8, 8, 1, 2, 2), (64, 288): (8, 1, 8, 2, 2)}
+WG_N = 100                    # 96 rows through the unmasked kernel, 4 through the masked one
+
+
+def test_wgrad_shapes_select_different_rows():
+    """What the workspace query shows of the plan: the sizes of any two shapes differ, and the number of row slabs of a
+    very tall input (one per workgroup) is 256 for the 8-wave rows and 512 for the 4-wave rows."""
+    from mlgnn import _lib
+    sizes = {mk: _lib.size("mlgnn_linear_wgrad_workspace_floats", WG_N, mk[0], mk[1], 0) for mk in WG_ROWS}
+    assert len(set(sizes.values())) == len(WG_ROWS)
+    assert len(set(WG_ROWS.values())) == len(WG_ROWS)
+    for (M, K), row in WG_ROWS.items():
+        tall = _lib.size("mlgnn_linear_wgrad_workspace_floats", 1 << 20, M, K, 0)
+        assert (tall - 512) // (M * K + M) - 1 == (256 if row[0] == 8 else 512), (M, K)
+
+
+@pytest.mark.parametrize("M,K", list(WG_ROWS) + [(37, 128)])
+def test_wgrad_plan_rows(M, K):
+    """Every reachable row of the plan table, and (37, 128) through the padded (masked-only) path: the exact three-term
+    split and the scaled fp16 split (both row maxima given) against fp64, bounds of
+    tests/test_wgrad_gpu.py::test_wgrad_scaled_split_every_layout (1e-6 of the summed magnitudes; bias 1e-5)."""
+    from mlgnn.dense import _wgrad
+    gen = torch.Generator().manual_seed(M * 3 + K)
+    go = torch.randn(WG_N, M, generator=gen)
+    x = torch.randn(WG_N, K, generator=gen)
+    ref_w, ref_b = go.double().t() @ x.double(), go.double().sum(0)
+    mag = go.double().abs().t() @ x.double().abs() + 1e-30
+    god, xd = go.to(DEV), x.to(DEV)
+    for maxima in ({}, dict(go_max=god.abs().amax(1), x_max=xd.abs().amax(1))):
+        w, b = _wgrad(god, xd, **maxima)
+        err = ((w.cpu().double() - ref_w).abs() / mag).max().item()
+        assert err < 1e-6, (err, sorted(maxima))
+        assert_close(b, ref_b, 1e-5, "bias grad")
