@@ -1187,6 +1187,44 @@ int mlgnn_mutual_info_cc(const double* x, const double* y, const double* psi, do
                          int32_t* ny, int64_t n, int64_t n_features, int k, void* stream);
 
 /*
+ * Batched PCA over ragged column segments (csrc/pathway_pca.hip), fp64: what sklearn.decomposition.PCA(svd_solver='full')
+ * gives for every (pathway, omics) segment of a fold, one workgroup per segment, one launch.
+ *   xt [F, N] feature-major (row f = column f of the data), cols [T] indices into [0, F) grouped by segment, seg_ptr
+ *   [S + 1] non-decreasing with seg_ptr[0] = 0 and seg_ptr[S] = T, k_seg [S] the components wanted per segment,
+ *   0 <= k_seg[s] <= min(k, N, g_s) (clamped to that), or NULL: min(k, N, g_s) everywhere.  Segment s with the g columns
+ *   c_0 .. c_{g-1} and k_s components:
+ *     mean [T]:           mean[seg_ptr[s] + t] = (1 / N) sum_i x[i, c_t]
+ *     Xc = x[:, c] - mean = U diag(sigma) V^T, sigma descending, ties to the lower working column; each v_j times the
+ *     sign that makes its entry of largest magnitude positive (the first such entry on ties)
+ *     components [T, k]:  components[seg_ptr[s] + t, j] = v_j[t]
+ *     scores [N, S, k]:   scores[i, s, j] = sum_t Xc[i, t] v_j[t]
+ *     variance [S, k]:    variance[s, j] = sigma_j^2 / (N - 1)                              for j < k_s
+ *   and EVERY element with k_s <= j < k is written as 0 (all of a segment with g = 0).  info [S, 2] int32 = {sweeps run,
+ *   or -1 when the cap of 60 was reached; number of sigma_j above N g 2^-52 sigma_0}.  A component whose sigma_j is not
+ *   above that bound has an unspecified direction (zero where sigma_j is 0 and g > N).
+ * One-sided (Hestenes) Jacobi on the columns of Xc when g <= N and of Xc^T otherwise, pairs in round-robin order, one
+ * wave per pair, a rotation when |a_i . a_j| > 1e-15 sqrt(|a_i|^2 |a_j|^2); the covariance is never formed.  No atomics,
+ * every sum in a fixed order: bitwise reproducible, and a segment's bits do not depend on the other segments.  The
+ * working matrices live in `workspace`: mlgnn_pathway_pca_workspace_bytes(N, T, S, max_cols) bytes, host arithmetic on
+ * its arguments (8 (N T + T min(N, max_cols)) rounded up to 256), 8-byte aligned; its contents on entry are ignored.
+ * max_cols is the caller's statement of max g_s: the workspace is sized by it and the kernel reads at most max_cols
+ * columns of a segment, so a wrong value cannot overrun.  Shapes (mlgnn_pathway_pca_supported): 2 <= N <= 2048,
+ * 0 <= max_cols <= 2048, min(N, max_cols) <= 512, 1 <= k <= 8, S >= 0, T >= 0, N T, N S k and T k doubles below 4 GiB
+ * (the entry point: also F >= 1 where T > 0, and F N doubles below 4 GiB).  MLGNN_E_NULL for a NULL operand other than
+ * k_seg, then MLGNN_E_SHAPE, then MLGNN_E_WORKSPACE (as in mlgnn_mutual_info_cd, NULL operands are reported before shape
+ * errors); all before anything is launched.  T = 0 or S = 0 is a no-op (nothing is read or written).  No trip count
+ * depends on a value beyond the sweep cap and no index depends on a value except the choice of the k_s largest sigma,
+ * which stays in range whatever the norms are: NaN or Inf input makes that segment's outputs non-finite or arbitrary,
+ * leaves every other segment's bits as they are and never causes an access out of bounds.
+ */
+int mlgnn_pathway_pca_supported(int64_t n, int64_t total_cols, int64_t n_segments, int64_t max_cols, int k);
+int64_t mlgnn_pathway_pca_workspace_bytes(int64_t n, int64_t total_cols, int64_t n_segments, int64_t max_cols);
+int mlgnn_pathway_pca(const double* xt, const int32_t* cols, const int64_t* seg_ptr, const int32_t* k_seg,
+                      double* components, double* scores, double* variance, double* mean, int32_t* info,
+                      void* workspace, int64_t workspace_bytes, int64_t n, int64_t n_features, int64_t total_cols,
+                      int64_t n_segments, int64_t max_cols, int k, void* stream);
+
+/*
  * PathwayConv's message + aggregation (csrc/pathway_conv.hip; the reference's torch_vertex.py:107-178): the second
  * message-passing step over the gene -> pathway-node membership edges, for MLGNN_AGGR_MAX and MLGNN_AGGR_SOFTMAX (add and
  * mean are two weighted sums of the existing aggregation by linearity; MLGNN_E_MODE here).  fp32, no atomics, every

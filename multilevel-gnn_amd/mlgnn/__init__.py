@@ -18,5 +18,6 @@ from .pathway_conv import PathwayTopology, pathway_aggregate, pathway_conv_suppo
 from .mutual_info import mutual_info_classif, mutual_info_supported, tree_path  # noqa: F401
 from .mutual_info import (mutual_info_cc, mutual_info_regression, mutual_info_regression_supported,  # noqa: F401
                           prepare_regression)
+from .pca import fold_pca, pathway_pca, pathway_pca_supported  # noqa: F401
 from .ops import (LowRankEdge, RankOneEdge, TableEdge, edge_type_embedding, gen_aggregate, share_edge_gradient,  # noqa: F401
                   weighted_mean_aggregate)

@@ -141,6 +141,9 @@ SIGNATURES = {
     "mlgnn_mutual_info_cd": (_INT, [_P, _P, _P, _c.c_double, _P, _P, _I64, _I64, _INT, _INT, _P]),
     "mlgnn_mutual_info_cc_supported": (_INT, [_I64, _I64, _INT]),
     "mlgnn_mutual_info_cc": (_INT, [_P, _P, _P, _c.c_double, _P, _P, _P, _I64, _I64, _INT, _P]),
+    "mlgnn_pathway_pca_supported": (_INT, [_I64] * 4 + [_INT]),
+    "mlgnn_pathway_pca_workspace_bytes": (_I64, [_I64] * 4),
+    "mlgnn_pathway_pca": (_INT, [_P] * 10 + [_I64] * 6 + [_INT, _P]),
     "mlgnn_pathway_conv_supported": (_INT, [_I64] * 3),
     "mlgnn_pathway_conv_fwd": (_INT, [_P] * 9 + [_I64] * 4 + [_INT, _F, _P, _P]),
     "mlgnn_pathway_conv_bwd_workspace_floats": (_I64, [_I64] * 4 + [_INT]),

@@ -145,9 +145,14 @@ class SyntheticTCGA(torch.utils.data.Dataset):
     a binary label that depends on a few pathway nodes (so that training can reduce the loss).
     ``with_raw_data=True``: a sample also carries ``raw_data [1, n_members]``, the value of every member's gene node (0
     for a member without a node) -- the field ``multiloader.py:83-86`` fills for the models without a gene graph
-    (PathCNN); drawn from the same tensors, so everything else is unchanged."""
+    (PathCNN); drawn from the same tensors, so everything else is unchanged.
+    The fold preparation of ``train.py:293-298``: :meth:`get_data_by_indice` hands out that member matrix for a set of
+    patients, :meth:`recalculate_pca_bo_selected_gene` runs :func:`mlgnn.pca.fold_pca` over the whole cohort (as the
+    reference does) and sets ``pca_components`` and the per-patient ``pathway_node_attr``, which is all zeros until
+    then.  ``pca_sim_dim`` (``None``: ``pca_dim``) and ``drop_irr_pathway`` are the reference's flags of that name."""
 
-    def __init__(self, n_patients, node_num=5135, n_edges=60000, n_members=25015, pca_dim=2, seed=0, with_raw_data=False):
+    def __init__(self, n_patients, node_num=5135, n_edges=60000, n_members=25015, pca_dim=2, seed=0, with_raw_data=False,
+                 pca_sim_dim=None, drop_irr_pathway=False):
         gen = torch.Generator().manual_seed(seed)
         self.node_num, self.NN = node_num, node_num * 3
         NN = self.NN
@@ -168,19 +173,42 @@ class SyntheticTCGA(torch.utils.data.Dataset):
         self.labels = (signal > signal.median()).long()
         self.age = torch.rand(n_patients, generator=gen)
         self.with_raw_data = bool(with_raw_data)
+        self.pca_sim_dim = pca_dim if pca_sim_dim is None else pca_sim_dim
+        self.drop_irr_pathway = bool(drop_irr_pathway)
+        self.pca_components = None                     # set by recalculate_pca_bo_selected_gene
+        self._pathway_image = None                     # [n_patients, 146, 3 * pca_dim] once it has run
 
     def __len__(self):
         return self.x.shape[0]
 
     def __getitem__(self, i):
         y = torch.tensor([1.0 - float(self.labels[i]), float(self.labels[i])])
+        image = torch.zeros(1, 146, 3 * self.pca_dim) if self._pathway_image is None else self._pathway_image[i][None]
         d = Data(x=self.x[i], edge_index=self.edge_index, edge_attr=self.edge_attr, y=y, age=float(self.age[i]),
                  gene_pca_match=self.gene_pca_match[None, :], raw_indice=self.raw_indice[None, :],
-                 node_size=self.NN, pathway_node_attr=torch.zeros(1, 146, 3 * self.pca_dim))
+                 node_size=self.NN, pathway_node_attr=image)
         if self.with_raw_data:
             present = self.gene_pca_match >= 0
             d.raw_data = (self.x[i, self.gene_pca_match.clamp(min=0), 0] * present)[None, :]
         return d
+
+    def raw_matrix(self, indexs=None):
+        """``[patients, n_members]``: the ``raw_data`` rows of ``indexs`` (``None``: the whole cohort).  No new draw."""
+        x = self.x if indexs is None else self.x[torch.as_tensor(indexs, dtype=torch.long)]
+        return x[:, self.gene_pca_match.clamp(min=0), 0] * (self.gene_pca_match >= 0)
+
+    def get_data_by_indice(self, indexs):
+        """``MyData.get_data_by_indice`` (multiloader.py:532-542): ``(member rows, labels)`` of the patients ``indexs``,
+        what ``generate_mutual_mask`` takes."""
+        return self.raw_matrix(indexs).numpy(), self.labels[torch.as_tensor(indexs, dtype=torch.long)].numpy()
+
+    def recalculate_pca_bo_selected_gene(self, mutual_info_mask):
+        """``MyData.recalculate_pca_bo_selected_gene`` (multiloader.py:568-579): the per-segment PCA over the members the
+        mask kept (``None``: all), fitted on the whole cohort; sets ``pca_components`` and every patient's
+        ``pathway_node_attr``."""
+        from .pca import fold_pca
+        self.pca_components, self._pathway_image = fold_pca(self.raw_matrix(), self.raw_indice, mutual_info_mask,
+                                                            self.pca_sim_dim, self.pca_dim, self.drop_irr_pathway)
 
     def get_weight_balance(self, indexs, batch_size, weight_power=1.0):
         """``MyData.get_weight_balance`` (multiloader.py:321-326): per-class weights repeated per batch row."""

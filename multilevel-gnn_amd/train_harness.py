@@ -51,7 +51,7 @@ DEFAULTS = dict(
     conv_channel_list=[32, 64], conv_kernel_list=[1, 1], embedding_init_type="xavier", emb_val=0.01,
     input_drop=None, input_emb_drop=None, gnn_dropout=0.0, device_num=1, edge_type="grnboost2",
     reduction_method="linear_projection", freeze_mutual_select_init=False, random_state=12345, remain_all_tf=False,
-    pathcnn_kernel_size=3, more_conv=False,
+    pathcnn_kernel_size=3, more_conv=False, pca_sim_dim=5, drop_irr_pathway=False, mutual_classif=False,
 )
 
 
@@ -60,6 +60,9 @@ def parse_opts(argv=None):
     ap.add_argument("--config", default=None)
     ap.add_argument("--patients", type=int, default=96, help="synthetic cohort size")
     ap.add_argument("--small", action="store_true", help="shrunken gene graph (tests)")
+    ap.add_argument("--fold_prep", action="store_true",
+                    help="prepare the fold as train.py:293-298 does: mutual-information mask, per-pathway PCA of the members "
+                         "it keeps, projection started from the principal axes, PCA image in pathway_node_attr")
     for k, v in DEFAULTS.items():
         if isinstance(v, bool):
             ap.add_argument("--" + k, action="store_true", default=v)
@@ -152,7 +155,8 @@ def run(args):
         if args.use_column is None:
             args.use_column = "weight"
     else:
-        data = SyntheticTCGA(args.patients, pca_dim=args.pca_dim, seed=args.seed, with_raw_data=(args.model == "pathcnn"), **small)
+        data = SyntheticTCGA(args.patients, pca_dim=args.pca_dim, seed=args.seed, with_raw_data=(args.model == "pathcnn"),
+                             pca_sim_dim=max(args.pca_sim_dim, args.pca_dim), drop_irr_pathway=args.drop_irr_pathway, **small)
     n_train = int(0.7 * len(data)) // (args.batch_size * world) * (args.batch_size * world)
     idx = torch.randperm(len(data), generator=torch.Generator().manual_seed(args.seed)).tolist()
     train_idx, valid_idx = idx[:n_train][rank::world], idx[n_train:]
@@ -161,7 +165,8 @@ def run(args):
     valid_loader = DataLoader(torch.utils.data.Subset(data, valid_idx), batch_size=args.batch_size, shuffle=False,
                               num_workers=args.num_workers)
 
-    if args.model == "pathcnn" and not args.learnable_pca:
+    fold_prep = getattr(args, "fold_prep", False) and args.model in ("multilevel_gnn", "pathcnn")
+    if args.model == "pathcnn" and not args.learnable_pca and not fold_prep:
         # the synthetic cohort has no precomputed PCA image (pathway_node_attr is all zeros): the image is the learnable
         # projection of raw_data
         logging.info("pathcnn on the synthetic cohort: learnable_pca switched on")
@@ -180,6 +185,14 @@ def run(args):
         model.set_pca_params(torch.randn(data.n_members, args.pca_dim) * 0.05, mask)
         model.set_info_mask(mask[:, None].clone())
         model.set_pathway_indexs((data.raw_indice // 3).to(device))
+    if fold_prep:
+        # train.py:293-298: the mask from the training patients, the PCA over the members it keeps (fitted on the whole
+        # cohort, as the reference does), the projection started from the principal axes.  Before the optimiser is built.
+        x, y = data.get_data_by_indice(train_idx)
+        mask = model.generate_mutual_mask(x, y, args.mutual_classif)[0]
+        model.set_info_mask(mask.to(torch.float32))
+        data.recalculate_pca_bo_selected_gene(mask)
+        model.set_pca_params(data.pca_components.to(device), mask)
     model.to(device)
     broadcast_parameters(model)
     # train.py:112-114 (Adam + StepLR) and :63-66 (clip_grad_norm_(20) + step) as ONE fused update of the flat buffer
