@@ -150,11 +150,7 @@ int mlgnn_csr_aggregate_fwd(const void* x, const int32_t* rowptr, const int32_t*
  *                   summed in place instead of by separate [E0,d] additions)
  *                   3 (MAX over fp32 rows with a TABLE read through eid): nothing per edge is produced, grad_efull is
  *                   NULL -- the table's gradient comes from the destination side (mlgnn_max_table_grad)
- *                   2 (MAX over fp32 rows with a TABLE read through eid): grad_efull is the fixed-point accumulator of
- *                   the TABLE's gradient prepared by mlgnn_table_grad_begin and geid_t names every edge's table row
- *                   (= eid_t): with max only the winning edge of (i, c) has a gradient, 1 / degree of the [E,d]
- *                   per-edge gradient is non-zero, and it is added to the table directly with integer atomics (sums
- *                   independent of arrival order: bitwise reproducible) -- no [E,d] gradient is written or re-read
+ *                   2 is reserved: MLGNN_E_MODE
  *   grad_uv  [edge_rank+1,d]  EDGE_RANK1: d loss / d eu (edge_rank rows), then d loss / d ev
  *   learn_t  non-zero: SOFTMAX weights carry gradient (torch_message.py:51-52)
  *   workspace: mlgnn_csr_aggregate_bwd_workspace_floats(N,d,dtype,edge_rank,aggr,learn_t) floats
@@ -177,48 +173,6 @@ int mlgnn_csr_aggregate_bwd(const void* grad_out, const void* x, const void* out
                             int aggr, int learn_t, float t, float p, const float* t_dev, const float* p_dev,
                             float eps, int add_root, int accumulate_efull, const mlgnn_hub_t* hub,
                             const void* grad_shifted, const int32_t* shift_flag, void* stream);
-
-/*
- * The same backward when x was  y = relu?(LayerNorm(h))  -- the res+ block's norm + ReLU in front of the conv,
- * models/deepergcn.py:236-241 -- and this aggregation (with add_root) is what consumes y: the row epilogue, which
- * holds the finished row of d loss / d y, takes it through that LayerNorm's backward, so
- *     grad_x [N,d]          receives  d loss / d h  (+ grad_extra)  instead of d loss / d y
- *     grad_gamma_beta [2,d] receives  d loss / d gamma, d loss / d beta of the LayerNorm
- *     row_max [N] or NULL   max |grad_x| per row (what the GEMMs that consume grad_x scale their operand by)
- * and the separate LayerNorm-backward pass over [N,d] (mlgnn_layernorm_act_bwd) does not run.
- *   h [N,d], mean [N], rstd [N], gamma [d], beta [d]: the LayerNorm's input, statistics and affine parameters
- *   grad_extra [N,d] or NULL: gradient arriving on h along the block's identity branch (deepergcn.py:241), added here
- *   workspace: mlgnn_csr_aggregate_bwd_ln_workspace_floats(N, d) floats
- * fp32, d = 4 * 2^k <= 256 (one channel chunk per lane group), no long-row split (hub NULL or cap 0), no learn_t:
- * MLGNN_E_MODE otherwise, and the caller runs the two passes.
- */
-typedef struct mlgnn_ln_fold {
-  const float* h;
-  const float* mean;
-  const float* rstd;
-  const float* gamma;
-  const float* beta;
-  const float* grad_extra;
-  float* row_max;
-  float* grad_gamma_beta;
-  float* workspace;
-  int64_t workspace_floats;
-  int32_t relu;
-} mlgnn_ln_fold_t;
-int64_t mlgnn_csr_aggregate_bwd_ln_workspace_floats(int64_t N, int64_t d);
-int mlgnn_csr_aggregate_bwd_ln(const void* grad_out, const void* x, const void* out, const float* aux,
-                               const int32_t* argmax,
-                               const int32_t* rowptr_t, const int32_t* col_t, const int32_t* pos_t,
-                               const int32_t* rowptr,
-                               const float* ew_t, const float* eu, const float* ev,
-                               const void* efull, const int32_t* eid_t, const int32_t* geid_t,
-                               void* grad_x, void* grad_efull, float* grad_uv,
-                               float* workspace, int64_t workspace_floats,
-                               int64_t N, int64_t d, int dtype, int msg, int edge_mode, int edge_rank,
-                               int aggr, int learn_t, float t, float p, const float* t_dev, const float* p_dev,
-                               float eps, int add_root, int accumulate_efull, const mlgnn_hub_t* hub,
-                               const void* grad_shifted, const int32_t* shift_flag, const mlgnn_ln_fold_t* ln,
-                               void* stream);
 
 /*
  * Backward prologue of the `power` aggregator (models/gcn_lib/sparse/torch_message.py:66-76): what
@@ -556,23 +510,10 @@ int mlgnn_embedding_bwd(const float* grad_e, const int32_t* perm, const int32_t*
                         int64_t T, int64_t d, int dtype, void* stream);
 
 /*
- * Table gradient through a fixed-point accumulator -- the max aggregator's way to the gradient of a table edge term
- * (deepergcn.py:103-104,189-190: nn.Embedding(pathway_edge_num, hidden) read by every GENConv layer; the reference's
- * DEFAULT flags gcn_aggr=max, global_edge=onehot):
- *   accumulator: mlgnn_table_grad_bytes(T, d) bytes, 16-byte aligned, ZEROED once by the caller;
- *   mlgnn_table_grad_begin(grad_out [rows,d] fp32 -- the cotangent mlgnn_csr_aggregate_bwd is about to receive)
- *     records max |grad_out| (and a non-finite flag) on the device: the power-of-two scale of the sums;
- *   mlgnn_csr_aggregate_bwd(..., grad_efull = accumulator, geid_t = table row per edge, accumulate_efull = 2);
- *   mlgnn_table_grad_finish: grad_table [T,d] = (accumulate ? grad_table : 0) + sums / scale, accumulator cleared for
- *     the next layer.  Resolution 2^-(61 - log2(rows)) of max |grad_out|; a non-finite cotangent gives an all-NaN table
- *     gradient (the per-edge path would confine it to the rows it touches).
- */
-int64_t mlgnn_table_grad_bytes(int64_t T, int64_t d);
-
-/*
- * The same gradient from the DESTINATION side, without atomics and without a per-edge buffer (the default for the
- * reference's default flags).  The forward's argmax [N,d] names the winning edge of (i, c) by its by-destination position,
- * or -1 where no gradient flows (no incoming edge, or the winner's relu is on its flat side), so
+ * Gradient of a table edge term under the max aggregator (deepergcn.py:103-104,189-190: nn.Embedding(pathway_edge_num,
+ * hidden) read by every GENConv layer; the reference's DEFAULT flags gcn_aggr=max, global_edge=onehot) from the
+ * DESTINATION side, without atomics and without a per-edge buffer.  The forward's argmax [N,d] names the winning
+ * edge of (i, c) by its by-destination position, or -1 where no gradient flows (no incoming edge, or the winner's relu is on its flat side), so
  *   grad_table[t][c] (+)= sum over { i : rows_by_dst[argmax[i][c]] = t } of grad_out[i][c]
  * is one streaming pass over grad_out and argmax (N d 8 bytes); rows_by_dst [E] int32: table row of every edge in
  * by-destination order.  The aggregation backward then runs with accumulate_efull = 3 and writes nothing per edge.
@@ -601,7 +542,6 @@ int mlgnn_max_table_grad_by_type(const float* grad_out, const int32_t* argmax, c
                                  const void* slots, float* grad_table, int64_t N, int64_t d, int64_t T, int accumulate,
                                  void* stream);
 int64_t mlgnn_csr_aggregate_bwd_slots_offset_floats(int64_t N, int64_t d, int edge_rank);
-int mlgnn_table_grad_begin(const float* grad_out, int64_t rows, int64_t d, void* accumulator, void* stream);
 
 /*
  * Backward of the MAX aggregator (the reference's default, opt.py:144; torch_message.py:46-47) from compact winner lists
@@ -626,7 +566,6 @@ int mlgnn_max_sparse_bwd(const void* records, const void* meta, const int32_t* r
                          const float* root, float* grad_x, int64_t N, int64_t d, void* stream);
 int mlgnn_max_sparse_table_grad(const void* records, const void* meta, const int32_t* pos_sorted, const int32_t* rowptr,
                                 float* grad_table, int64_t N, int64_t d, int64_t T, int accumulate, void* stream);
-int mlgnn_table_grad_finish(void* accumulator, float* grad_table, int64_t T, int64_t d, int accumulate, void* stream);
 
 /*
  * Large bf16 GEMM with fp32 accumulation on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16), both operands with the

@@ -21,11 +21,6 @@ struct BwdArgs {                      // go / x / out / efull / gx / ge are T; a
   int N; int d; int lpr_log2; int mean; int learn_t; int add_root; int ge_accumulate;
   float t; float p; float eps;
   int cap; const int* vrows; const int* vcount;             // long source rows, as in FwdArgs (csrc/hub.hip)
-  // LNB: x was y = relu?(LayerNorm(h)) -- the res+ block's pre-conv norm (deepergcn.py:236-241) -- and the row epilogue
-  // takes the finished grad_y row through that LayerNorm's backward: gx receives d loss / d h (+ ln_extra, the gradient
-  // arriving on h along the block's identity branch); per-workgroup [2, d] partials of d gamma / d beta go to ln_ws
-  const float* ln_h; const float* ln_mean; const float* ln_rstd; const float* ln_gamma; const float* ln_beta;
-  const float* ln_extra; float* ln_rowmax; float* ln_ws; int ln_relu;
 };
 
 // VEC one-byte winner slots -> ints
@@ -50,9 +45,8 @@ __device__ __forceinline__ void load_slots(int (&r)[VEC], const uint8_t* p) {
 // edge gathers ONE row (gt) instead of two (go, lse): half the gather traffic, and no per-edge scalar either.
 // SHIFT with max: the winning edge of (i, c) is looked up as a 1-byte slot inside row i (max_slot_kernel) instead of
 // the 4-byte by-destination position the forward wrote -- the second gathered row shrinks from 4 d to d bytes.
-template <typename T, int VEC, int MODE, int AGGR, bool LEARN_T, bool SHIFT, bool VIRT, bool LNB = false, bool WIDE = false>
+template <typename T, int VEC, int MODE, int AGGR, bool LEARN_T, bool SHIFT, bool VIRT, bool WIDE = false>
 __device__ __forceinline__ void csr_aggregate_bwd_body(const BwdArgs& a, float (*red)[kWave * VEC]) {
-  static_assert(!LNB || (sizeof(T) == 4 && !VIRT && !LEARN_T), "LayerNorm-backward epilogue: fp32 rows of the main launch");
   constexpr int RK = rank_of<MODE>();
   constexpr int ES = edge_scalars<MODE>();
   constexpr int ESA = ES > 0 ? ES : 1;
@@ -74,16 +68,10 @@ __device__ __forceinline__ void csr_aggregate_bwd_body(const BwdArgs& a, float (
   const Scalars sc = read_scalars(a.t_dev, a.p_dev, a.t, a.p);
   const float t_eps = sc.t_log2e * a.eps;
   const uint32_t row_bytes = (uint32_t)a.d * (uint32_t)sizeof(T);
-  // max with a TABLE edge term (ge_accumulate == 2): only the winning edge of (i, c) has a gradient -- 1 / degree of the
-  // [E, d] per-edge gradient is non-zero -- so it is added straight to the table's fixed-point accumulator (integer
-  // atomics: order-independent) instead of being written per edge and reduced later (csrc/embedding.hip)
-  constexpr bool kCanFix = MODE == M_GEN_FULL && AGGR == A_MAX && sizeof(T) == 4;
-  const bool fix = kCanFix && a.ge_accumulate == 2;
-  // ge_accumulate == 3: the table's gradient is taken from the destination side (mlgnn_max_table_grad, csrc/embedding.hip);
-  // nothing per edge leaves this kernel
-  const bool skip_ge = kCanFix && a.ge_accumulate == 3;
-  const float fix_scale = fix ? fix_scale_of(static_cast<const uint32_t*>(a.ge)) : 0.f;
-  unsigned long long* fix_tab = reinterpret_cast<unsigned long long*>(static_cast<unsigned char*>(a.ge) + kFixHeaderBytes);
+  // max with a TABLE edge term, ge_accumulate == 3: the table's gradient is taken from the destination side
+  // (mlgnn_max_table_grad, csrc/embedding.hip); nothing per edge leaves this kernel
+  constexpr bool kCanSkipGe = MODE == M_GEN_FULL && AGGR == A_MAX && sizeof(T) == 4;
+  const bool skip_ge = kCanSkipGe && a.ge_accumulate == 3;
 
   for (int cbase = 0; cbase < a.d; cbase += lpr * VEC) {
     const bool cact = cbase + cl * VEC < a.d;          // inactive lanes shadow the last chunk (see forward)
@@ -107,96 +95,6 @@ __device__ __forceinline__ void csr_aggregate_bwd_body(const BwdArgs& a, float (
       }
     }
 
-    // LNB (one channel chunk: d == lpr * VEC, checked on the host).  The epilogue's arithmetic is the same for every
-    // lane group, and after the merge below every group holds the finished row -- so a finished row is only PARKED with
-    // one group (group `slot`), and the epilogue runs once per `groups` rows with each group working on its own row:
-    // 1/groups of the instructions and shuffle trips per row (this kernel is bound by instruction issue; an epilogue
-    // per row cost as much as the LayerNorm pass it replaces).  Only the parked row stays in registers between rows
-    // (this kernel runs four waves per SIMD at <= 128 registers): the LayerNorm operands are requested at the flush,
-    // the d gamma / d beta sums of the rows a lane owned live in LDS (`red`, a slot per lane and channel).
-    const float inv_d = 1.0f / (float)a.d;
-    int slot = 0, keep_r = -1;
-    float keep[VEC];
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) keep[i] = 0.f;
-    float* lds_dg = &red[wave][0] + lane * VEC;                   // [kWave * VEC] per wave: this lane's d gamma ...
-    float* lds_db = lds_dg + kWavesPerBlock * kWave * VEC;        // ... and d beta sums (second half of `red`)
-    if constexpr (LNB) {
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) { lds_dg[i] = 0.f; lds_db[i] = 0.f; }
-    }
-    // the LayerNorm operands of the rows a flush will work on, requested when the LAST row of a group of `groups`
-    // starts (every lane group for the row parked with it, the last group for the row about to be walked), so that
-    // they arrive behind that row's edges
-    float lh[VEC], le[VEC], lroot[VEC], lmu = 0.f, lrs = 0.f;
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) { lh[i] = 0.f; le[i] = 0.f; lroot[i] = 0.f; }
-    // (read once, next to a gather that lives on its L2 hit rate: non-temporal)
-    auto stream4 = [](float (&dst)[VEC], const float* src) {
-      if constexpr (VEC == 4) {
-        using f4 = __attribute__((ext_vector_type(4))) float;
-        const f4 v = __builtin_nontemporal_load(reinterpret_cast<const f4*>(src));
-        dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
-      } else {
-        load_vec<VEC>(dst, src);
-      }
-    };
-    auto ln_request = [&](int kr) {
-      stream4(lh, a.ln_h + (size_t)kr * a.d + c0);
-      lmu = a.ln_mean[kr]; lrs = a.ln_rstd[kr];
-      if (a.ln_extra) stream4(le, a.ln_extra + (size_t)kr * a.d + c0);
-      if (a.add_root) stream4(lroot, reinterpret_cast<const float*>(GO) + (size_t)kr * a.d + c0);
-    };
-    auto ln_flush = [&](bool requested) {
-      const bool wr = keep_r >= 0;
-      const int kr = max(keep_r, 0);
-      if (!requested) ln_request(kr);
-      float lng[VEC], lnb[VEC], ldg[VEC], ldb[VEC];
-      load_vec<VEC>(lng, a.ln_gamma + c0);
-      load_vec<VEC>(lnb, a.ln_beta + c0);
-      load_vec<VEC>(ldg, lds_dg);
-      load_vec<VEC>(ldb, lds_db);
-      float xh[VEC], gg[VEC], s1 = 0.f, s2 = 0.f;
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) {
-        xh[i] = (lh[i] - lmu) * lrs;
-        const float y = fmaf(xh[i], lng[i], lnb[i]);
-        const float gy = (wr && !(a.ln_relu && !(y > 0.f))) ? keep[i] + lroot[i] : 0.f;
-        ldg[i] = fmaf(gy, xh[i], ldg[i]);
-        ldb[i] += gy;
-        gg[i] = gy * lng[i];
-        s1 += gg[i];
-        s2 = fmaf(gg[i], xh[i], s2);
-      }
-      store_vec<VEC>(lds_dg, ldg);
-      store_vec<VEC>(lds_db, ldb);
-      // d = 128: a lane group is a 32-lane half -- rotations inside the rows of 16 lanes as DPP modifiers, one
-      // crossbar trip for the last step (common.h); the shuffle ladder (five trips per sum) otherwise
-      if (a.lpr_log2 == 5) { s1 = half_sum(s1); s2 = half_sum(s2); }
-      else for (int off = 1; off < lpr; off <<= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
-      s1 *= inv_d; s2 *= inv_d;
-      float o[VEC], om = 0.f;
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) {
-        o[i] = wr ? fmaf(lrs, gg[i] - s1 - xh[i] * s2, le[i]) : 0.f;
-        om = fmaxf(om, fabsf(o[i]));
-      }
-      if (a.ln_rowmax) {
-        if (a.lpr_log2 == 5) om = half_max(om);
-        else for (int off = 1; off < lpr; off <<= 1) om = fmaxf(om, __shfl_xor(om, off));
-        if (wr && cl == 0) a.ln_rowmax[kr] = om;
-      }
-      if constexpr (VEC == 4) {
-        if (wr) {
-          using f4 = __attribute__((ext_vector_type(4))) float;
-          const f4 v = {o[0], o[1], o[2], o[3]};
-          __builtin_nontemporal_store(v, reinterpret_cast<f4*>(reinterpret_cast<float*>(GX) + (size_t)kr * a.d + c0));
-        }
-      }
-      keep_r = -1;
-      slot = 0;
-    };
-
     for (int r = walk.first; r < walk.r_end; r += walk.stride) {
       // xr: the source node whose features this row of edges belongs to (VIRT: a chunk of a long row, csrc/hub.hip)
       const int xr = VIRT ? a.vrows[3 * r] : r;
@@ -210,9 +108,6 @@ __device__ __forceinline__ void csr_aggregate_bwd_body(const BwdArgs& a, float (
       float xjv[VEC];
 #pragma unroll
       for (int i = 0; i < VEC; ++i) xjv[i] = xj[i] + ev[i];
-      if constexpr (LNB) {
-        if (slot == groups - 1) ln_request(sub == slot ? r : max(keep_r, 0));
-      }
       for (int base = beg; base < end; base += kWave) {
         const int cnt = min(kWave, end - base);
         uint32_t my_off = 0;
@@ -308,16 +203,7 @@ __device__ __forceinline__ void csr_aggregate_bwd_body(const BwdArgs& a, float (
                 for (int q = 0; q < RK; ++q) gu[i][q] = fmaf(wa[u][q], dz[i], gu[i][q]);
               }
             }
-            if constexpr (kCanFix) {
-              if (fix) {
-                if (valid[u] && cact) {
-                  unsigned long long* tp = fix_tab + (size_t)g0[u] * a.d + c0;
-#pragma unroll
-                  for (int i = 0; i < VEC; ++i)
-                    if (dz[i] != 0.f) atomicAdd(tp + i, (unsigned long long)__float2ll_rn(dz[i] * fix_scale));
-                }
-                continue;
-              }
+            if constexpr (kCanSkipGe) {
               if (skip_ge) continue;
             }
             if (MODE == M_GEN_FULL && valid[u] && cact) {
@@ -351,14 +237,6 @@ __device__ __forceinline__ void csr_aggregate_bwd_body(const BwdArgs& a, float (
       for (int off = lpr; off < kWave; off <<= 1)
 #pragma unroll
         for (int i = 0; i < VEC; ++i) gx[i] += __shfl_xor(gx[i], off);
-      if constexpr (LNB) {
-        if (sub == slot) {
-          keep_r = r;
-#pragma unroll
-          for (int i = 0; i < VEC; ++i) keep[i] = gx[i];
-        }
-        if (++slot == groups) ln_flush(true);
-      } else
       if (sub == 0 && cact) {
         if (a.add_root && !VIRT) {    // identity branch of h = x + m (once per real row: the main launch)
           float gr[VEC];
@@ -371,22 +249,6 @@ __device__ __forceinline__ void csr_aggregate_bwd_body(const BwdArgs& a, float (
       }
     }
 
-    if constexpr (LNB) {
-      if (slot > 0) ln_flush(false);               // rows still parked when the walk ends
-    }
-    if constexpr (LNB) {
-      // d gamma / d beta: every lane holds (in LDS) the sums of the rows its group owned -> groups -> waves -> one
-      // [2, d] partial per workgroup
-      __syncthreads();
-      for (int c = threadIdx.x; c < 2 * a.d; c += kBlock) {
-        const int which = c / a.d, ch = c % a.d;
-        const float* src = &red[0][0] + which * (kWavesPerBlock * kWave * VEC);
-        float sum = 0.f;
-        for (int w = 0; w < kWavesPerBlock; ++w)
-          for (int g2 = 0; g2 < groups; ++g2) sum += src[w * (kWave * VEC) + (g2 * lpr) * VEC + ch];
-        a.ln_ws[((size_t)blockIdx.x * 2 + which) * a.d + ch] = sum;
-      }
-    }
     if constexpr (RK > 0) {
       // per-workgroup partial of d loss/d U [RK,d] and d loss/d v [d]  ->  ws[block][RK+1][d]; summed by a second launch
       for (int off = lpr; off < kWave; off <<= 1)
@@ -416,23 +278,22 @@ __device__ __forceinline__ void csr_aggregate_bwd_body(const BwdArgs& a, float (
   }
 }
 
-// (LNB: four waves per SIMD asked for -- the parked row puts the softmax instantiation two registers past 128)
-template <typename T, int VEC, int MODE, int AGGR, bool LEARN_T, bool VIRT = false, bool LNB = false, bool WIDE = false>
-__global__ __launch_bounds__(kBlock, LNB ? 4 : 1) void csr_aggregate_bwd_kernel(const BwdArgs a) {
-  __shared__ float red[LNB ? 2 * kWavesPerBlock : kWavesPerBlock][kWave * VEC];     // LNB: + the d gamma / d beta slots
+template <typename T, int VEC, int MODE, int AGGR, bool LEARN_T, bool VIRT = false, bool WIDE = false>
+__global__ __launch_bounds__(kBlock, 1) void csr_aggregate_bwd_kernel(const BwdArgs a) {
+  __shared__ float red[kWavesPerBlock][kWave * VEC];
   if constexpr (AGGR == A_SOFTMAX && !LEARN_T) {
     // *a.spread != 0: softmax_shift_kernel met a node with |lse| > kMaxLse in some channel; the two-row path
     // stays as the fallback for such inputs (never seen in practice: lse = log2 sum_e 2^(t m_e))
     const bool shift_ok = a.gt != nullptr && *a.spread == 0;
-    if (shift_ok) csr_aggregate_bwd_body<T, VEC, MODE, AGGR, LEARN_T, true, VIRT, LNB, WIDE>(a, red);
-    else csr_aggregate_bwd_body<T, VEC, MODE, AGGR, LEARN_T, false, VIRT, LNB, WIDE>(a, red);
+    if (shift_ok) csr_aggregate_bwd_body<T, VEC, MODE, AGGR, LEARN_T, true, VIRT, WIDE>(a, red);
+    else csr_aggregate_bwd_body<T, VEC, MODE, AGGR, LEARN_T, false, VIRT, WIDE>(a, red);
   } else if constexpr (AGGR == A_MAX) {
     // *a.spread != 0: some node has more than 254 incoming edges, its slots do not fit a byte
     const bool slots_ok = a.slot8 != nullptr && *a.spread == 0;
-    if (slots_ok) csr_aggregate_bwd_body<T, VEC, MODE, AGGR, LEARN_T, true, VIRT, LNB, WIDE>(a, red);
-    else csr_aggregate_bwd_body<T, VEC, MODE, AGGR, LEARN_T, false, VIRT, LNB, WIDE>(a, red);
+    if (slots_ok) csr_aggregate_bwd_body<T, VEC, MODE, AGGR, LEARN_T, true, VIRT, WIDE>(a, red);
+    else csr_aggregate_bwd_body<T, VEC, MODE, AGGR, LEARN_T, false, VIRT, WIDE>(a, red);
   } else {
-    csr_aggregate_bwd_body<T, VEC, MODE, AGGR, LEARN_T, false, VIRT, LNB, WIDE>(a, red);
+    csr_aggregate_bwd_body<T, VEC, MODE, AGGR, LEARN_T, false, VIRT, WIDE>(a, red);
   }
 }
 
@@ -692,7 +553,7 @@ extern "C" int64_t mlgnn_csr_aggregate_bwd_slots_offset_floats(int64_t N, int64_
   return rk > 0 ? (int64_t)(grid_for_rows(N) + kHubBlocks) * (rk + 1) * d : 0;
 }
 
-static int csr_aggregate_bwd_impl(const void* grad_out, const void* x, const void* out, const float* aux,
+extern "C" int mlgnn_csr_aggregate_bwd(const void* grad_out, const void* x, const void* out, const float* aux,
                                        const int32_t* argmax,
                                        const int32_t* rowptr_t, const int32_t* col_t, const int32_t* pos_t,
                                        const int32_t* rowptr,
@@ -704,13 +565,14 @@ static int csr_aggregate_bwd_impl(const void* grad_out, const void* x, const voi
                                        int aggr, int learn_t, float t, float p, const float* t_dev,
                                        const float* p_dev, float eps, int add_root, int accumulate_efull,
                                        const mlgnn_hub_t* hub, const void* grad_shifted, const int32_t* shift_flag,
-                                       const mlgnn_ln_fold_t* ln, void* stream) {
+                                       void* stream) {
   if (dtype != MLGNN_DTYPE_F32 && dtype != MLGNN_DTYPE_BF16) return MLGNN_E_DTYPE;
   if (N < 0 || d <= 0 || N > INT32_MAX || d > INT32_MAX) return MLGNN_E_SHAPE;
   const int mode = pick_mode(msg, edge_mode, edge_rank);
   const int ag = pick_aggr(aggr);
   if (mode < 0 || ag < 0) return MLGNN_E_MODE;
   if (!is_gen_mode(mode) && ag != A_SUM) return MLGNN_E_MODE;
+  if (accumulate_efull == 2) return MLGNN_E_MODE;               // reserved (include/mlgnn.h)
   if (N == 0) return 0;
   if (!grad_out || !rowptr_t || !grad_x) return MLGNN_E_NULL;   // col_t may be NULL iff E == 0
   if (is_gen_mode(mode) && !x) return MLGNN_E_NULL;
@@ -746,10 +608,7 @@ static int csr_aggregate_bwd_impl(const void* grad_out, const void* x, const voi
   a.N = (int)N; a.d = (int)d; a.mean = (aggr == MLGNN_AGGR_MEAN); a.learn_t = learn_t;
   a.t = t; a.p = p; a.eps = eps; a.t_dev = t_dev; a.p_dev = p_dev; a.add_root = add_root;
   a.ge_accumulate = accumulate_efull;
-  // 2: grad_efull is the fixed-point accumulator of a TABLE gradient (mlgnn_table_grad_begin), geid_t names every
-  // edge's table row -- the max aggregator over fp32 rows only
   if (accumulate_efull == 3 && (ag != A_MAX || mode != M_GEN_FULL || bf16 || grad_efull)) return MLGNN_E_MODE;
-  if (accumulate_efull == 2 && (ag != A_MAX || mode != M_GEN_FULL || bf16 || !grad_efull || !geid_t)) return MLGNN_E_MODE;
   a.cap = split ? hub->cap : kNoCap; a.vrows = nullptr; a.vcount = nullptr;
   if (add_root && learn_t) return MLGNN_E_MODE;       // `out` must be the bare aggregate for d/dt
 
@@ -765,18 +624,6 @@ static int csr_aggregate_bwd_impl(const void* grad_out, const void* x, const voi
   a.lpr_log2 = lanes_per_row_log2(d, vec);
   const bool wide = needs_wide_rows(N, d) || force_wide_rows();      // 64-bit row addresses (aggregate_common.h)
   if (wide && vec == 1 && needs_wide_rows(N, d)) return MLGNN_E_SHAPE;
-  a.ln_h = nullptr; a.ln_mean = a.ln_rstd = a.ln_gamma = a.ln_beta = a.ln_extra = nullptr;
-  a.ln_rowmax = nullptr; a.ln_ws = nullptr; a.ln_relu = 0;
-  if (ln) {
-    // the epilogue holds whole fp32 rows in one lane group; long rows (whose gradient is finished by the combine
-    // launch) and the d/dt path keep the separate LayerNorm backward
-    if (bf16 || vec != 4 || d != ((int64_t)4 << a.lpr_log2) || split || learn_t || wide) return MLGNN_E_MODE;
-    if (!ln->h || !ln->mean || !ln->rstd || !ln->gamma || !ln->beta || !ln->grad_gamma_beta || !ln->workspace) return MLGNN_E_NULL;
-    if (ln->workspace_floats < (int64_t)nblk * 2 * d) return MLGNN_E_WORKSPACE;
-    if (!aligned(ln->h, ln->gamma, ln->beta, ln->grad_extra)) return MLGNN_E_ALIGN;
-    a.ln_h = ln->h; a.ln_mean = ln->mean; a.ln_rstd = ln->rstd; a.ln_gamma = ln->gamma; a.ln_beta = ln->beta;
-    a.ln_extra = ln->grad_extra; a.ln_rowmax = ln->row_max; a.ln_ws = ln->workspace; a.ln_relu = ln->relu;
-  }
   a.gt = nullptr; a.spread = nullptr;
   if (have_shift) {
     if (!aligned(grad_shifted) && vec != 1) return MLGNN_E_ALIGN;
@@ -846,17 +693,10 @@ static int csr_aggregate_bwd_impl(const void* grad_out, const void* x, const voi
           if (fixed_grid > 0) g = fixed_grid; else launched_blocks = g;
           hipLaunchKernelGGL(kernel, dim3(g), block, 0, s, args);
         };
-        if constexpr (std::is_same<T, float>::value && VEC == 4 && !VIRT) {
-          if (ln) {
-            if (wide) return;                                  // (refused below: the fold keeps 32-bit rows)
-            go(csr_aggregate_bwd_kernel<T, VEC, MODE, AGGR, false, VIRT, true>, IC<2>{});
-            return;
-          }
-        }
         if constexpr (VEC > 1) {
           if (wide) {
-            if (kCanLearn && lt) go(csr_aggregate_bwd_kernel<T, VEC, MODE, AGGR, kCanLearn, VIRT, false, true>, IC<3>{});
-            else go(csr_aggregate_bwd_kernel<T, VEC, MODE, AGGR, false, VIRT, false, true>, IC<4>{});
+            if (kCanLearn && lt) go(csr_aggregate_bwd_kernel<T, VEC, MODE, AGGR, kCanLearn, VIRT, true>, IC<3>{});
+            else go(csr_aggregate_bwd_kernel<T, VEC, MODE, AGGR, false, VIRT, true>, IC<4>{});
             return;
           }
         }
@@ -870,7 +710,7 @@ static int csr_aggregate_bwd_impl(const void* grad_out, const void* x, const voi
   // narrow fp32 rows, weighted sum / mean: one lane group per source row (aggregate_short.h)
   static const bool short_on = [] { const char* e = getenv("MLGNN_SHORT_ROWS"); return !(e && e[0] == '0'); }();
   if (short_on && !bf16 && vec == 4 && (mode == M_IDENTITY || mode == M_WEIGHTED) && ag == A_SUM && short_width_ok(d) &&
-      rk == 0 && !ln && !add_root && !wide && !grad_efull && (!a.mean || rowptr)) {
+      rk == 0 && !add_root && !wide && !grad_efull && (!a.mean || rowptr)) {
     if (!launch_short([](auto l, auto w) { return &csr_short_bwd_kernel<l(), w()>; }, d, mode == M_WEIGHTED, N, s,
                       static_cast<const float*>(grad_out), rowptr_t, col_t, ew_t, rowptr, static_cast<float*>(grad_x), (int)N,
                       a.mean, a.cap))
@@ -900,53 +740,5 @@ static int csr_aggregate_bwd_impl(const void* grad_out, const void* x, const voi
     launch_reduce_partials(workspace, grad_uv, total_blocks, (rk + 1) * (int)d, s);
     err = (int)hipGetLastError();
   }
-  if (ln && !err) {
-    launch_reduce_partials(ln->workspace, ln->grad_gamma_beta, launched_blocks, 2 * (int)d, s);
-    err = (int)hipGetLastError();
-  }
   return err;
-}
-
-extern "C" int mlgnn_csr_aggregate_bwd(const void* grad_out, const void* x, const void* out, const float* aux,
-                                       const int32_t* argmax,
-                                       const int32_t* rowptr_t, const int32_t* col_t, const int32_t* pos_t,
-                                       const int32_t* rowptr,
-                                       const float* ew_t, const float* eu, const float* ev,
-                                       const void* efull, const int32_t* eid_t, const int32_t* geid_t,
-                                       void* grad_x, void* grad_efull, float* grad_uv,
-                                       float* workspace, int64_t workspace_floats,
-                                       int64_t N, int64_t d, int dtype, int msg, int edge_mode, int edge_rank,
-                                       int aggr, int learn_t, float t, float p, const float* t_dev,
-                                       const float* p_dev, float eps, int add_root, int accumulate_efull,
-                                       const mlgnn_hub_t* hub, const void* grad_shifted, const int32_t* shift_flag,
-                                       void* stream) {
-  return csr_aggregate_bwd_impl(grad_out, x, out, aux, argmax, rowptr_t, col_t, pos_t, rowptr, ew_t, eu, ev, efull, eid_t,
-                                geid_t, grad_x, grad_efull, grad_uv, workspace, workspace_floats, N, d, dtype, msg, edge_mode,
-                                edge_rank, aggr, learn_t, t, p, t_dev, p_dev, eps, add_root, accumulate_efull, hub,
-                                grad_shifted, shift_flag, nullptr, stream);
-}
-
-extern "C" int64_t mlgnn_csr_aggregate_bwd_ln_workspace_floats(int64_t N, int64_t d) {
-  if (N < 0 || d <= 0 || N > INT32_MAX) return MLGNN_E_SHAPE;
-  return (int64_t)grid_for_rows(N) * 2 * d;
-}
-
-extern "C" int mlgnn_csr_aggregate_bwd_ln(const void* grad_out, const void* x, const void* out, const float* aux,
-                                          const int32_t* argmax,
-                                          const int32_t* rowptr_t, const int32_t* col_t, const int32_t* pos_t,
-                                          const int32_t* rowptr,
-                                          const float* ew_t, const float* eu, const float* ev,
-                                          const void* efull, const int32_t* eid_t, const int32_t* geid_t,
-                                          void* grad_x, void* grad_efull, float* grad_uv,
-                                          float* workspace, int64_t workspace_floats,
-                                          int64_t N, int64_t d, int dtype, int msg, int edge_mode, int edge_rank,
-                                          int aggr, int learn_t, float t, float p, const float* t_dev,
-                                          const float* p_dev, float eps, int add_root, int accumulate_efull,
-                                          const mlgnn_hub_t* hub, const void* grad_shifted, const int32_t* shift_flag,
-                                          const mlgnn_ln_fold_t* ln, void* stream) {
-  if (!ln) return MLGNN_E_NULL;
-  return csr_aggregate_bwd_impl(grad_out, x, out, aux, argmax, rowptr_t, col_t, pos_t, rowptr, ew_t, eu, ev, efull, eid_t,
-                                geid_t, grad_x, grad_efull, grad_uv, workspace, workspace_floats, N, d, dtype, msg, edge_mode,
-                                edge_rank, aggr, learn_t, t, p, t_dev, p_dev, eps, add_root, accumulate_efull, hub,
-                                grad_shifted, shift_flag, ln, stream);
 }

@@ -142,8 +142,8 @@ class CSRGraph:
         hit = self._hub.get(direction)
         if hit is None and not self._hub:
             # first use: both directions at once -- the backward's tables are then known hub-free (on the host, through
-            # the asynchronous count copy) by the time the backward asks, and its kernels may use the epilogues that
-            # need a row to be finished by ONE wavefront (mlgnn_csr_aggregate_bwd_ln)
+            # the asynchronous count copy) by the time the backward asks, and it skips the empty long-row launches
+            # from its first call on
             self._hub[direction] = None
             self.hub_tables("src" if direction == "dst" else "dst")
             del self._hub[direction]

@@ -3,16 +3,14 @@
 PyTorch owns memory and the autograd graph; every numeric step of the aggregation itself runs in
 libmlgnn.so.  All functions require CUDA(HIP) fp32 tensors and raise otherwise -- no CPU path.
 """
-import ctypes
-import functools
 import os
 
 import torch
 
 from . import _lib
 from .graph import CSRGraph, _same_view
-from .tags import (PostLN, drop_stale, f32_cached, invalidate_param_cache, row_max_of, shifted_of,  # noqa: F401
-                   softmax_lse_of, tag_post_ln, tag_row_max, tag_shifted, tag_softmax_lse)
+from .tags import (drop_stale, f32_cached, invalidate_param_cache, row_max_of, shifted_of,  # noqa: F401
+                   softmax_lse_of, tag_row_max, tag_shifted, tag_softmax_lse)
 
 MSG_IDENTITY, MSG_WEIGHTED, MSG_GEN = 0, 1, 2
 EDGE_NONE, EDGE_RANK1, EDGE_FULL = 0, 1, 2
@@ -116,12 +114,6 @@ def _dev_act(t, what, like=None):
     return _lib.aligned(t)
 
 
-# Off by default.  Measured at BASELINE configs[1] (same-box A/B, bench.py): the epilogue costs the aggregation backward
-# 0.13-0.27 ms per launch (per row / per pair of rows, operands prefetched or not, non-temporal or not) against the
-# 0.21 ms LayerNorm-backward launch it removes -- that kernel is bound by instruction issue and by the L2 hit rate of
-# its gather, and the epilogue adds to both; the step moved by -0.1 ... +0.1 ms.  MLGNN_LN_FOLD=1 turns it on.
-LN_FOLD = os.environ.get("MLGNN_LN_FOLD", "0") == "1"
-LN_FOLD_STATS = _lib.stats("ln_fold", folded=0, separate=0)
 SHIFT_STATS = {"given": 0, "computed": 0}     # softmax backwards whose rescaled cotangent came from the producer / a pre-pass
 
 
@@ -223,11 +215,6 @@ def edge_type_embedding(table, idx):
     return torch.nn.functional.embedding(idx, table)
 
 
-# max + TableEdge: the table gradient summed inside the backward kernel (fixed-point atomics) instead of through an [E, d]
-# per-edge gradient.  Saves that buffer (5.2 GB for a BASELINE configs[1] batch) but measured 3 % SLOWER per step with
-# the reference's default DeeperGCN flags (22.6 vs 21.9 ms, same box): 82 M sparse 8-byte atomics per layer execute at
-# the memory side, one 64-byte request each.  Off by default.
-TABLE_DIRECT = os.environ.get("MLGNN_TABLE_DIRECT", "0") == "1"
 # max + TableEdge, the default since round 4: the table gradient from the DESTINATION side -- the forward's argmax names
 # the winner of every (node, channel), so the gradient is one streaming pass over grad_out and argmax
 # (mlgnn_max_table_grad) and the aggregation backward writes nothing per edge.  MLGNN_TABLE_DEST=0: the per-edge buffer.
@@ -245,9 +232,8 @@ class _GradSink:
     def __init__(self):
         self.buf = None
         self.graph = None          # TableEdge: the graph whose by-source edge order the rows of buf follow
-        # TableEdge under the max aggregator: the table's gradient is summed directly (fixed-point accumulator,
-        # csrc/embedding.hip) -- `total` collects the layers of one backward
-        self.fix = None
+        # TableEdge under the max aggregator: the table's gradient is summed from the destination side
+        # (csrc/embedding.hip, csrc/max_sparse.hip) -- `total` collects the layers of one backward
         self.total = None
 
     def claim(self):
@@ -428,34 +414,24 @@ def _aggregate_fwd(x, graph, out, msg, aggr_id, hub, ew_pair=None, eu=None, ev=N
 def _aggregate_bwd(go, graph, gx, msg, aggr_id, hub, x=None, out=None, aux=None, argmax=None, ew_pair=None, eu=None, ev=None,
                    efull=None, eid_t=None, geid_t=None, ge=None, ge_accumulate=0, guv=None, ws=None, ws_n=0,
                    edge_mode=EDGE_NONE, rank=0, learn_t=False, t=1.0, p=1.0, t_dev=None, p_dev=None, eps=0.0,
-                   add_root=False, shifted=None, ln=None):
+                   add_root=False, shifted=None):
     """The launch of ``mlgnn_csr_aggregate_bwd`` (include/mlgnn.h): ``gx`` [N, d] from the cotangent ``go`` over the by-source
-    CSR of ``graph``; ``hub`` from ``graph.hub_arg("src", d)``.  ``ln`` (an ``_lib.LnFoldStruct``; ``hub`` must be None, it takes
-    no hub table): ``mlgnn_csr_aggregate_bwd_ln`` -- the LayerNorm backward in the row epilogue, the struct behind the arguments."""
+    CSR of ``graph``; ``hub`` from ``graph.hub_arg("src", d)``."""
     N, d = go.shape
     ew_t = ew_pair[1] if ew_pair is not None else None
-    args = (go, x, out, aux, argmax, graph.rowptr_t, graph.col_t, graph.pos_t, graph.rowptr,
-            ew_t, eu, ev, efull, eid_t, geid_t, gx, ge, guv, ws, ws_n,
-            N, d, _DTYPE_IDS[go.dtype], msg, edge_mode, rank, aggr_id, int(learn_t), t, p,
-            t_dev, p_dev, eps, int(add_root), ge_accumulate, hub,
-            shifted[0] if shifted else None, shifted[1] if shifted else None)
-    if ln is None:
-        _lib.call("mlgnn_csr_aggregate_bwd", *args, _lib.stream())
-    else:
-        _lib.call("mlgnn_csr_aggregate_bwd_ln", *args, ctypes.byref(ln), _lib.stream())
+    _lib.call("mlgnn_csr_aggregate_bwd", go, x, out, aux, argmax, graph.rowptr_t, graph.col_t, graph.pos_t, graph.rowptr,
+              ew_t, eu, ev, efull, eid_t, geid_t, gx, ge, guv, ws, ws_n,
+              N, d, _DTYPE_IDS[go.dtype], msg, edge_mode, rank, aggr_id, int(learn_t), t, p,
+              t_dev, p_dev, eps, int(add_root), ge_accumulate, hub,
+              shifted[0] if shifted else None, shifted[1] if shifted else None, _lib.stream())
 
 
 class _GenAggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, eu, ev, efull, t_par, p_par, graph, ew_pair, aggr_id, t, p, eps, learn_t, learn_p, add_root,
                 table_edge=None):
-        post_ln = getattr(x, "_mlgnn_post_ln", None)
         x = _dev_act(x, "x")
         N, d = x.shape
-        # x = relu?(LayerNorm(h)) written by the previous conv's GEMM: its backward can run in this op's row epilogue
-        ctx.post_ln = post_ln if (LN_FOLD and post_ln is not None and add_root and not learn_t and not learn_p
-                                  and x.dtype == torch.float32 and d in (16, 32, 64, 128, 256)
-                                  and aggr_id != AGGR_POWER and post_ln.h.shape == x.shape) else None
         if graph.num_nodes != N:
             raise ValueError("graph/feature size mismatch")
         edge_mode = EDGE_RANK1 if eu is not None else (EDGE_FULL if efull is not None else EDGE_NONE)
@@ -554,13 +530,12 @@ class _GenAggregate(torch.autograd.Function):
         if route == ROUTE_WINNERS:
             _max_winners_backward(go_k, argmax, g, gx, add_root, te, sink, ctx.winner_records)   # (no KERNEL_TIMER record)
         else:
-            gx, ge, guv = _gather_backward(ctx, saved, route, go_k, gx, shifted)
+            ge, guv = _gather_backward(ctx, saved, route, go_k, gx, shifted)
         geu, gev = (guv[:ctx.uv_rows].to(ctx.uv_dtype), guv[rank].to(ctx.uv_dtype)) if guv is not None else (None, None)
         return gx, geu, gev, ge, grad_t, grad_p, None, None, None, None, None, None, None, None, None, None
 
 
 # Where the gradient of the edge term goes in _GenAggregate.backward, in the order the routes are tried:
-ROUTE_TABLE_FIXED = "table_fixed"          # TABLE_DIRECT: max over a table, summed by fixed-point atomics inside the kernel
 ROUTE_WINNERS = "winners"                  # SPARSE_MAX: max without / over a table, from compact winner lists (no row gather)
 ROUTE_TABLE_STREAMED = "table_streamed"    # TABLE_DEST, a few table rows: one streaming pass over grad_out and argmax
 ROUTE_TABLE_BY_TYPE = "table_by_type"      # TABLE_DEST, many table rows: a pass per table row BEHIND the backward kernel
@@ -577,13 +552,9 @@ def _edge_grad_route(ctx, x, argmax, go_k):
     max_f32 = aggr_id == AGGR_MAX and x.dtype == torch.float32 and argmax is not None
     aligned = max_f32 and go_k.data_ptr() % 16 == 0 and argmax.data_ptr() % 16 == 0
     table_wants_grad = te is not None and sink is not None and edge_mode == EDGE_FULL
-    # max over a table edge term: only the winning edge of (i, c) has a gradient -- it goes straight to the table's
-    # fixed-point accumulator inside the kernel (no [E, d] gradient written, re-read and reduced)
-    if TABLE_DIRECT and table_wants_grad and max_f32 and d % 4 == 0 and ctx.post_ln is None:
-        return ROUTE_TABLE_FIXED
     # every (node, channel) has ONE winning edge: its cotangent goes to that edge's source -- and to the table row
     # the edge reads -- through compact per-edge runs of (value, channel) pairs instead of whole gathered rows
-    if (SPARSE_MAX and aligned and ctx.post_ln is None and g.num_edges > 0
+    if (SPARSE_MAX and aligned and g.num_edges > 0
             and (edge_mode == EDGE_NONE or (edge_mode == EDGE_FULL and te is not None and TABLE_DEST))
             and (records := _lib.size("mlgnn_max_sparse_records", N, d, g.num_edges, or_none=True))
             and g.known_short_rows()):
@@ -632,16 +603,6 @@ def _max_winners_backward(go_k, argmax, g, gx, add_root, te, sink, records):
     TABLE_DEST_STATS["calls"] += 1
 
 
-def _fixed_point_begin(go_k, te, sink):
-    """ROUTE_TABLE_FIXED, before the kernel: the fixed-point accumulator (kept on the sink), scaled for this cotangent."""
-    N, d = go_k.shape
-    nbytes = _lib.size("mlgnn_table_grad_bytes", te.table_rows, d)
-    if sink.fix is None or sink.fix.numel() != nbytes:
-        sink.fix = torch.zeros(nbytes, dtype=torch.uint8, device=go_k.device)
-    _lib.call("mlgnn_table_grad_begin", go_k, N, d, sink.fix, _lib.stream())
-    return sink.fix
-
-
 def _by_type_table_grad(go_k, argmax, g, te, sink, ws, ws_n, rank):
     """ROUTE_TABLE_BY_TYPE, behind the backward kernel (it reads that call's winner slots in ``ws``): one row per KEGG
     membership (tens of thousands) -- a wavefront per table row gathers its edges' winners."""
@@ -655,31 +616,9 @@ def _by_type_table_grad(go_k, argmax, g, te, sink, ws, ws_n, rank):
     TABLE_DEST_STATS["by_type"] += 1
 
 
-def _ln_fold_backward(tag, x, gx, launch):
-    """The backward kernel with the LayerNorm backward of ``x = y = relu?(LayerNorm(h))`` in its row epilogue: d loss / d y
-    goes through it as each row is finished; ``gx`` is then d loss / d h (+ the identity-branch gradient the block's MLP
-    left in ``tag.extra``) and is left in ``tag.folded`` -- nothing reaches y through autograd: see PostLN."""
-    tag.claim()
-    N, d = x.shape
-    f32 = dict(dtype=torch.float32, device=x.device)
-    ln_ws, ln_n = _lib.workspace("mlgnn_csr_aggregate_bwd_ln_workspace_floats", N, d, device=x.device)
-    ggb, row_max = torch.empty((2, d), **f32), torch.empty(N, **f32)
-    extra = tag.extra if (tag.extra is not None and tag.extra.dtype == torch.float32
-                          and tag.extra.shape == x.shape and tag.extra.is_contiguous()
-                          and tag.extra.data_ptr() % 16 == 0) else None
-    gamma, beta = f32_cached(tag.gamma), f32_cached(tag.beta)
-    st = _lib.LnFoldStruct(tag.h.data_ptr(), tag.mean.data_ptr(), tag.rstd.data_ptr(), gamma.data_ptr(),
-                           beta.data_ptr(), _lib.ptr(extra), row_max.data_ptr(), ggb.data_ptr(), ln_ws.data_ptr(),
-                           ln_n, int(tag.relu))
-    launch(hub=None, ln=st)
-    tag.folded = (gx, ggb[0], ggb[1], row_max)
-    tag.extra_used = extra is not None
-    LN_FOLD_STATS["folded"] += 1
-
-
 def _gather_backward(ctx, saved, route, go_k, gx, shifted):
     """Every route but ROUTE_WINNERS: the row-gather kernel (``mlgnn_csr_aggregate_bwd``) writes ``gx`` and puts the edge
-    term's gradient where ``route`` says.  -> ``(gx, ge, guv)`` as autograd gets them."""
+    term's gradient where ``route`` says.  -> ``(ge, guv)`` as autograd gets them."""
     x, out, aux, aux2, argmax, eu, ev, efull, t_dev, p_dev = saved
     aggr_id, edge_mode, rank, t, p, eps, learn_t, learn_p, add_root = ctx.cfg
     g, sink, te = ctx.graph, ctx.grad_sink, ctx.table_edge
@@ -688,9 +627,7 @@ def _gather_backward(ctx, saved, route, go_k, gx, shifted):
     if te is not None:                                   # read the table row, write the edge's own gradient row
         _, eid_t, geid_t = te.rows_for(g)                # (gradient rows in by-source order: a streamed write)
     ge, ge_accumulate = None, 0
-    if route == ROUTE_TABLE_FIXED:
-        ge, ge_accumulate, geid_t = _fixed_point_begin(go_k, te, sink), 2, eid_t
-    elif route in (ROUTE_TABLE_STREAMED, ROUTE_TABLE_BY_TYPE):
+    if route in (ROUTE_TABLE_STREAMED, ROUTE_TABLE_BY_TYPE):
         if route == ROUTE_TABLE_STREAMED:
             _streamed_table_grad(go_k, argmax, g, te, sink)
         TABLE_DEST_STATS["calls"] += 1
@@ -707,23 +644,13 @@ def _gather_backward(ctx, saved, route, go_k, gx, shifted):
     timer = KERNEL_TIMER
     t0 = timer.start() if timer is not None else None
     hub, hub_keep = g.hub_arg("src", d)
-    launch = functools.partial(
-        _aggregate_bwd, go_k, g, gx, MSG_GEN, aggr_id, x=x, out=out, aux=aux, argmax=argmax,
-        ew_pair=ctx.ew_pair, eu=eu, ev=ev, efull=efull, eid_t=eid_t, geid_t=geid_t,
-        ge=ge, ge_accumulate=ge_accumulate, guv=guv, ws=ws, ws_n=ws_n, edge_mode=edge_mode, rank=rank, learn_t=learn_t,
-        t=t, p=p, t_dev=t_dev, p_dev=p_dev, eps=eps, add_root=add_root, shifted=shifted)
-    if ctx.post_ln is not None and hub is None and ctx.needs_input_grad[0]:
-        _ln_fold_backward(ctx.post_ln, x, gx, launch)
-        gx = None
-    else:
-        LN_FOLD_STATS["separate"] += int(ctx.post_ln is not None)
-        launch(hub=hub)
+    _aggregate_bwd(go_k, g, gx, MSG_GEN, aggr_id, hub, x=x, out=out, aux=aux, argmax=argmax,
+                   ew_pair=ctx.ew_pair, eu=eu, ev=ev, efull=efull, eid_t=eid_t, geid_t=geid_t,
+                   ge=ge, ge_accumulate=ge_accumulate, guv=guv, ws=ws, ws_n=ws_n, edge_mode=edge_mode, rank=rank,
+                   learn_t=learn_t, t=t, p=p, t_dev=t_dev, p_dev=p_dev, eps=eps, add_root=add_root, shifted=shifted)
     del hub_keep
     if route == ROUTE_TABLE_BY_TYPE:
         _by_type_table_grad(go_k, argmax, g, te, sink, ws, ws_n, rank)
-    if route == ROUTE_TABLE_FIXED:
-        total, accumulate = sink.table_total(te.table_rows, d, x.device)
-        _lib.call("mlgnn_table_grad_finish", sink.fix, total, te.table_rows, d, accumulate, _lib.stream())
     SHIFT_STATS["given" if shifted else "computed"] += int(aggr_id == AGGR_SOFTMAX and not learn_t)
     if sink is not None or te is not None:
         ge = None                                        # reported once, by the fan-out node of the shared term
@@ -731,7 +658,7 @@ def _gather_backward(ctx, saved, route, go_k, gx, shifted):
         timer.stop("csr_aggregate_bwd/%s/%s" % (_AGGR_NAMES[aggr_id], _edge_name(edge_mode, rank)), t0,
                    algorithmic_bytes(N, g.num_edges, d, aggr_id, edge_mode, backward=True, learn_t=learn_t,
                                      s=x.element_size(), rank=max(rank, 1)))
-    return gx, ge, guv
+    return ge, guv
 
 
 def gen_aggregate(x, graph, edge=None, aggr="softmax", t=1.0, p=1.0, eps=1e-7, learn_t=False, learn_p=False,

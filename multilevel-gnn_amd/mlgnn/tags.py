@@ -1,5 +1,5 @@
 """Side channels between autograd nodes: values a kernel wrote next to its result, carried as attributes of the tensor
-they describe (row maxima, the softmax log-sum-exp, the rescaled cotangent, the post-LayerNorm record), the state that
+they describe (row maxima, the softmax log-sum-exp, the rescaled cotangent), the state that
 belongs to ONE backward, and the fp32 copies of non-fp32 parameters.  No kernel is launched from here."""
 import torch
 
@@ -67,34 +67,6 @@ def drop_stale(owner, **reset):
     if last is not None and last != task:
         owner.__dict__.update(reset)
     return owner
-
-
-class PostLN:
-    """Side channel between the three nodes around a res+ block's pre-conv ``y = relu?(LayerNorm(h))``
-    (deepergcn.py:236-241) when ``y`` was written by the previous conv's last GEMM (:class:`mlgnn.dense._FusedMLP2`):
-
-    * the aggregation that consumes ``y`` takes the finished ``d loss / d y`` rows through the LayerNorm's backward in
-      its own row epilogue (``mlgnn_csr_aggregate_bwd_ln``), returns NO gradient for ``y`` and leaves
-      ``folded = (d loss / d h, d gamma, d beta, row maxima)`` here;
-    * the op that adds ``h`` as its residual (the same block's MLP) leaves the gradient of that identity branch in
-      ``extra`` instead of returning it, so that the epilogue above adds it in the same pass (``extra_used``);
-    * the producer of ``(h, y)`` picks both up in its backward -- and still runs the separate LayerNorm backward on
-      whatever gradient reaches ``y`` from other consumers.
-    Every field is consumed (reset) by the backward that reads it."""
-
-    def __init__(self, h, mean, rstd, gamma, beta, relu):
-        self.h, self.mean, self.rstd, self.gamma, self.beta, self.relu = h, mean, rstd, gamma, beta, bool(relu)
-        self.extra, self.extra_used, self.folded = None, False, None
-
-    def claim(self):
-        """Before a backward reads or writes ``extra`` / ``folded``: see :func:`drop_stale`."""
-        return drop_stale(self, extra=None, extra_used=False, folded=None)
-
-
-def tag_post_ln(y, h, tag):
-    y._mlgnn_post_ln = tag
-    h._mlgnn_post_ln_of = tag
-    return y
 
 
 _PARAM_EPOCH = [0]          # bumped after every step of ANY torch.optim.Optimizer (global post-step hook below)

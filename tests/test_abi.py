@@ -150,8 +150,8 @@ def test_argument_errors_of_the_one_pass_linear_backward():
 
 
 def test_argument_errors_of_the_fp32_large_diffpool_and_table_gradient():
-    """mlgnn_diffpool_large_f32_* and mlgnn_table_grad_*: sizes, NULL operands and workspaces are checked before
-    anything is launched (no GPU needed)."""
+    """mlgnn_diffpool_large_f32_* and the table-gradient mode of mlgnn_csr_aggregate_bwd: sizes, NULL operands, workspaces
+    and modes are checked before anything is launched (no GPU needed)."""
     from mlgnn import _lib
     lib = _lib.lib
     N, K, C = 256, 128, 128
@@ -166,13 +166,10 @@ def test_argument_errors_of_the_fp32_large_diffpool_and_table_gradient():
     bwd = lambda n=N: lib.mlgnn_diffpool_large_f32_bwd(None, None, None, None, None, None, None, None, None, None, None, 0,
                                                        None, 1 << 40, n, K, C, 1, 0, None)
     assert bwd() == -1 and bwd(n=130) == -2
-    # fixed-point table gradient (max aggregator with a table edge term)
-    assert lib.mlgnn_table_grad_bytes(20000, 128) == 256 + 20000 * 128 * 8
-    assert lib.mlgnn_table_grad_bytes(10, 130) == -2 and lib.mlgnn_table_grad_bytes(0, 128) == -2
-    assert lib.mlgnn_table_grad_begin(None, 100, 128, None, None) == -1
-    assert lib.mlgnn_table_grad_begin(None, 0, 128, None, None) == -2 and lib.mlgnn_table_grad_begin(None, 10, 6, None, None) == -2
-    assert lib.mlgnn_table_grad_finish(None, None, 10, 128, 0, None) == -1
-    assert lib.mlgnn_table_grad_finish(None, None, 10, 127, 0, None) == -2
+    # max aggregator with a table edge term (MSG_GEN, EDGE_FULL, AGGR_MAX): accumulate_efull 2 is reserved, 3 goes on to the operands
+    agg = lambda acc: lib.mlgnn_csr_aggregate_bwd(*[None] * 19, 0, 10, 128, 0, 2, 2, 0, 2, 0, 1.0, 1.0, None, None, 1e-7,
+                                                  0, acc, None, None, None, None)
+    assert agg(2) == -3 and agg(3) == -1
 
 
 def test_supported_and_entry_points_agree_past_4_gib():

@@ -4,8 +4,8 @@ The kernel tests elsewhere run one forward and one plain backward over inputs th
 is also driven the other ways autograd can drive it: (a) only some inputs requiring grad, (b) one parameter used twice in
 one graph, (c) ``backward(retain_graph=True)`` twice and ``torch.autograd.grad`` for one input followed by a full
 backward, (d) a zero-stride / non-contiguous cotangent and outputs left unused.  Several Functions move gradients outside
-autograd (the flat-bucket slot of ``_SkinnyLinear``, the edge-gradient sinks of ``_EdgeFanout`` / ``_TableFanout``, the
-``PostLN`` side channel): a bit-exact kernel can still yield a wrong gradient there.  The bucket flows of the head's
+autograd (the flat-bucket slot of ``_SkinnyLinear``, the edge-gradient sinks of ``_EdgeFanout`` / ``_TableFanout``):
+a bit-exact kernel can still yield a wrong gradient there.  The bucket flows of the head's
 ``Linear(84 096, 512)`` -- (e) no alias after return, (f) micro-batch accumulation -- close the file."""
 from dataclasses import dataclass, field
 from typing import Callable
@@ -52,13 +52,9 @@ def _edges(g, n, e):
     return torch.stack([src, dst])
 
 
-def _csr(ei, n, fold=False):
+def _csr(ei, n):
     from mlgnn import CSRGraph
-    graph = CSRGraph(ei, n)
-    if fold:
-        graph.hub_tables("src")
-        torch.cuda.synchronize()            # known hub-free on the host: the LayerNorm fold needs it
-    return graph
+    return CSRGraph(ei, n)
 
 
 def _gen_ref(x, ei, e, aggr, add_root=False):
@@ -182,14 +178,14 @@ def _mlp_ref(t):
 
 
 def _mlp_post_call(t):
-    """``(out, y = relu(LayerNorm(out)))`` of the fused MLP, ``y`` read by an aggregation: with LN_FOLD the aggregation's
-    backward takes ``y``'s LayerNorm backward and leaves the result in the PostLN side channel."""
+    """``(out, y = relu(LayerNorm(out)))`` of the fused MLP, ``y`` read by an aggregation: the MLP's backward starts with
+    ``y``'s LayerNorm backward, which adds the gradient arriving on ``out`` in the same pass."""
     from mlgnn import gen_aggregate
     from mlgnn.dense import fused_mlp2, fused_mlp2_post_supported
     assert fused_mlp2_post_supported(t["x"], t["w1"], t["w2"], t["pg"])
     out, y = fused_mlp2(t["x"], t["w1"], t["b1"], t["g1"], t["be1"], 1e-5, t["w2"], t["b2"],
                         post_norm=(t["pg"], t["pb"], 1e-5, True))
-    a = gen_aggregate(y, _csr(t["ei"], y.shape[0], fold=True), None, aggr="softmax", add_root=True)
+    a = gen_aggregate(y, _csr(t["ei"], y.shape[0]), None, aggr="softmax", add_root=True)
     return (a, out), out
 
 
@@ -416,11 +412,10 @@ REGISTRY = {
     "tall_linear": Entry("_TallLinear", _lin_build(N_TALL, 64, 128), ("x", "w", "b"), _lin_call, _lin_ref, params=("w", "b")),
     "fused_mlp2": Entry("_FusedMLP2", _mlp_build(False), ("x", "w1", "b1", "g1", "be1", "w2", "b2"), _mlp_call,
                         lambda t: (_mlp_ref(t),), params=("w1", "b1", "g1", "be1", "w2", "b2")),
-    "fused_mlp2-post-ln-fold": Entry("_FusedMLP2", _mlp_build(True),
-                                     ("x", "w1", "b1", "g1", "be1", "w2", "b2", "pg", "pb"), _mlp_post_call, _mlp_post_ref,
-                                     patch={"LN_FOLD": True}),
+    "fused_mlp2-post": Entry("_FusedMLP2", _mlp_build(True),
+                             ("x", "w1", "b1", "g1", "be1", "w2", "b2", "pg", "pb"), _mlp_post_call, _mlp_post_ref),
     "fused_mlp2-post-y-only": Entry("_FusedMLP2", _mlp_build(True), ("x", "w1", "w2", "pg", "pb"), _mlp_post_call,
-                                    _mlp_post_ref, use=(0,), patch={"LN_FOLD": True}),
+                                    _mlp_post_ref, use=(0,)),
     "wide_linear_f32": Entry("_WideLinearF32", _lin_build(9000, 128, 640), ("x", "w", "b"), _lin_call, _lin_ref,
                              params=("w", "b")),
     "skinny_linear": Entry("_SkinnyLinear", _lin_build(8, 8192, 64), ("x", "w", "b"), _lin_call, _lin_ref,
@@ -699,7 +694,7 @@ def test_backward_twice_with_retain_graph(patched):
 @_params(NAMES)
 def test_partial_grad_then_full_backward(patched):
     """``torch.autograd.grad`` for the first input only (retain_graph), then ``backward()``: both equal a fresh pass --
-    nothing the partial pass left behind (edge-gradient sinks, PostLN side channel, bucket slots) may leak into it."""
+    nothing the partial pass left behind (edge-gradient sinks, bucket slots) may leak into it."""
     name = patched
     entry = REGISTRY[name]
     ref = _reference(name, (0,), "dense")

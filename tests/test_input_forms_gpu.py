@@ -595,7 +595,7 @@ def _lact_predicate(t):
     return linear_act_supported(t["x"], t["w"])
 
 
-PREDICATES = {"fused_mlp2": _mlp_predicate(False), "fused_mlp2-post-ln-fold": _mlp_predicate(True),
+PREDICATES = {"fused_mlp2": _mlp_predicate(False), "fused_mlp2-post": _mlp_predicate(True),
               "fused_mlp2-post-y-only": _mlp_predicate(True), "sage_layer": _sage_predicate, "node_embed": _embed_predicate,
               "linear_act": _lact_predicate}
 REFUSALS = {
