@@ -1126,6 +1126,38 @@ int mlgnn_mutual_info_cc(const double* x, const double* y, const double* psi, do
                          int32_t* ny, int64_t n, int64_t n_features, int k, void* stream);
 
 /*
+ * The --edge_select test of the fold preparation for many node pairs at once (csrc/edge_select.hip), fp64: what the
+ * reference's valid_pca_mutual_info computes per PPI edge with PCA(n_components=1) and mutual_info_classif, one workgroup
+ * per pair, one launch.
+ *   xt [n_nodes, N] node-major (row v = the values of node v on the N training patients), pairs [P, 2] int32 node indices
+ *   (clamped to [0, n_nodes) inside the kernel, so a wrong value cannot read outside xt), noise [N] the fold's standard
+ *   normal draws, labels [N] dense class ids in [0, n_labels) (anything else is read as 0; every label is expected to
+ *   occur at least twice), psi [N + 1] and base as in mlgnn_mutual_info_cd.  Pair (s, t) with the columns x = xt[s],
+ *   y = xt[t]:
+ *     dx = x - mean(x), dy = y - mean(y), a = sum dx^2, b = sum dx dy, c = sum dy^2
+ *     v = the leading eigenvector of [[a, b], [b, c]]: for b != 0 the longer of (b, l - a) and (l - c, b), normalised,
+ *         with l = (a + c) / 2 + hypot((a - c) / 2, b); for b = 0 the axis of the larger variance, axis 0 on equality;
+ *         times the sign that makes its component of larger magnitude positive (the first on a tie)
+ *     score_i = dx_i v0 + dy_i v1
+ *     z = score / std, std = the population standard deviation of the score, 1 where it is below 10 * 2^-52
+ *     value_i = z_i + (1e-10 max(1, mean|z|)) noise_i
+ *     mi [P] = the estimate of mlgnn_mutual_info_cd on the column `value`
+ *   t < 0 (single-column mode): score = x, uncentred; the rest as above.  score [P, N] = `value` in sample order, or NULL;
+ *   counts [P, N] int32 = m_i in sample order, or NULL (each on its own).
+ * No atomics, no fused multiply-add, every sum in a fixed order: bitwise reproducible, and a pair's bits do not depend on
+ * the other pairs.  Shapes (mlgnn_edge_mi_supported; with_score: whether `score` is wanted): 2 <= N <= 2048, k >= 1,
+ * 1 <= n_labels <= N, 0 <= P < 2^31, n_nodes >= 0 (>= 1 where P > 0) with n_nodes * N * 8 below 4 GiB, and P * N * 8
+ * below 4 GiB when `score` is wanted.  MLGNN_E_NULL for a NULL xt, pairs, noise, labels, psi or mi, then MLGNN_E_SHAPE
+ * for anything else (as in mlgnn_mutual_info_cd, NULL operands are reported before shape errors); both before anything is
+ * launched.  P = 0 is a no-op (nothing is read or written).  No workspace.  NaN input makes that pair's outputs NaN or
+ * arbitrary, never an access out of bounds.
+ */
+int mlgnn_edge_mi_supported(int64_t n, int64_t n_nodes, int64_t n_pairs, int k, int n_labels, int with_score);
+int mlgnn_edge_mi(const double* xt, const int32_t* pairs, const double* noise, const int32_t* labels, const double* psi,
+                  double base, double* mi, double* score, int32_t* counts, int64_t n, int64_t n_nodes, int64_t n_pairs,
+                  int k, int n_labels, void* stream);
+
+/*
  * Batched PCA over ragged column segments (csrc/pathway_pca.hip), fp64: what sklearn.decomposition.PCA(svd_solver='full')
  * gives for every (pathway, omics) segment of a fold, one workgroup per segment, one launch.
  *   xt [F, N] feature-major (row f = column f of the data), cols [T] indices into [0, F) grouped by segment, seg_ptr

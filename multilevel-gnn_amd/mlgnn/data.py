@@ -13,6 +13,7 @@ The reference batches per-patient ``torch_geometric.data.Data`` objects with PyG
 model offsets them itself (``multilevel_gnn.py:212``).  The collate step can also pre-sort the
 topology (``with_csr=True`` attaches ``batch.csr``, a host-built :class:`mlgnn.CSRGraph`).
 """
+import numpy as np
 import torch
 from torch.utils.data import DataLoader as _TorchLoader
 
@@ -149,7 +150,9 @@ class SyntheticTCGA(torch.utils.data.Dataset):
     The fold preparation of ``train.py:293-298``: :meth:`get_data_by_indice` hands out that member matrix for a set of
     patients, :meth:`recalculate_pca_bo_selected_gene` runs :func:`mlgnn.pca.fold_pca` over the whole cohort (as the
     reference does) and sets ``pca_components`` and the per-patient ``pathway_node_attr``, which is all zeros until
-    then.  ``pca_sim_dim`` (``None``: ``pca_dim``) and ``drop_irr_pathway`` are the reference's flags of that name."""
+    then.  ``pca_sim_dim`` (``None``: ``pca_dim``) and ``drop_irr_pathway`` are the reference's flags of that name.
+    ``train.py:299``: :meth:`recalculate_edge_bo_selected_gene` narrows the shared topology, always starting from the one
+    drawn here (``_base_edge_index``, ``_base_edge_attr``; its first ``n_cross`` edges are the cross-omics ones)."""
 
     def __init__(self, n_patients, node_num=5135, n_edges=60000, n_members=25015, pca_dim=2, seed=0, with_raw_data=False,
                  pca_sim_dim=None, drop_irr_pathway=False):
@@ -164,6 +167,8 @@ class SyntheticTCGA(torch.utils.data.Dataset):
         dst[:n_cross] = torch.arange(n_cross) + node_num                      # CNV -> mRNA of the same gene
         w[:n_cross] = torch.where(torch.rand(n_cross, 1, generator=gen) < 0.5, -1.0, 1.0)
         self.edge_index, self.edge_attr = torch.stack([src, dst]), w
+        # the drawn topology, which recalculate_edge_bo_selected_gene narrows per fold (the reference's self.edges)
+        self._base_edge_index, self._base_edge_attr, self.n_cross = self.edge_index, self.edge_attr, n_cross
         self.raw_indice = torch.sort(torch.randint(0, 438, (n_members,), generator=gen))[0]
         self.gene_pca_match = torch.randint(0, NN, (n_members,), generator=gen)
         self.gene_pca_match[torch.rand(n_members, generator=gen) < 0.02] = -1
@@ -209,6 +214,43 @@ class SyntheticTCGA(torch.utils.data.Dataset):
         from .pca import fold_pca
         self.pca_components, self._pathway_image = fold_pca(self.raw_matrix(), self.raw_indice, mutual_info_mask,
                                                             self.pca_sim_dim, self.pca_dim, self.drop_irr_pathway)
+
+    def recalculate_edge_bo_selected_gene(self, mutual_info_mask, indice=None, edge_select=False, edge_select_threshold=1.0,
+                                          n_neighbors=3, random_state=None, mutual_classif=True,
+                                          allow_no_edge_pretrain=False):
+        """``MyData.recalculate_edge_bo_selected_gene`` (multiloader.py:581-700) on the synthetic cohort: the topology
+        narrowed to what the mask kept.  A node is selected iff some member ``m`` with ``gene_pca_match[m] == node`` has
+        ``mask[m, 0] > 0`` (``None``: every node).  Every call starts from the topology drawn at construction: its first
+        ``n_cross`` edges, the -1/+1 cross-omics edges, survive iff both ends are selected; the others, the PPI
+        candidates, also have to pass :func:`mlgnn.edge_select.edge_select` on the patients ``indice`` when
+        ``edge_select`` is set (``valid_pca_mutual_info``).  Survivors keep their order and attributes and become the
+        shared ``edge_index`` / ``edge_attr``; with none, the topology becomes empty under ``allow_no_edge_pretrain`` and
+        stays as it was otherwise (:689-694).  -> ``(edge_index, edge_attr)``."""
+        base_index, base_attr = self._base_edge_index, self._base_edge_attr
+        n_edges = base_index.shape[1]
+        if mutual_info_mask is None:
+            selected = torch.ones(self.NN, dtype=torch.bool)
+        else:
+            kept = torch.as_tensor(mutual_info_mask).reshape(self.n_members, -1)[:, 0] > 0
+            selected = torch.zeros(self.NN, dtype=torch.bool)
+            selected[self.gene_pca_match[kept.cpu() & (self.gene_pca_match >= 0)]] = True
+        survive = selected[base_index[0]] & selected[base_index[1]]
+        if edge_select:
+            from .edge_select import edge_select as select
+            if indice is None:
+                raise ValueError("recalculate_edge_bo_selected_gene: edge_select needs the training patients (indice)")
+            rows = torch.as_tensor(indice, dtype=torch.long)
+            ppi = torch.nonzero(survive[self.n_cross:])[:, 0] + self.n_cross
+            keep, _, _ = select(self.x[rows, :, 0], self.labels[rows], base_index[:, ppi], edge_select_threshold,
+                                n_neighbors, random_state, mutual_classif)
+            survive = survive.clone()
+            survive[ppi] = torch.from_numpy(np.asarray(keep, dtype=bool))
+        assert survive.shape == (n_edges,)
+        if bool(survive.any()):
+            self.edge_index, self.edge_attr = base_index[:, survive], base_attr[survive]
+        elif allow_no_edge_pretrain:
+            self.edge_index, self.edge_attr = base_index[:, :0], base_attr[:0]
+        return self.edge_index, self.edge_attr
 
     def get_weight_balance(self, indexs, batch_size, weight_power=1.0):
         """``MyData.get_weight_balance`` (multiloader.py:321-326): per-class weights repeated per batch row."""

@@ -52,6 +52,7 @@ DEFAULTS = dict(
     input_drop=None, input_emb_drop=None, gnn_dropout=0.0, device_num=1, edge_type="grnboost2",
     reduction_method="linear_projection", freeze_mutual_select_init=False, random_state=12345, remain_all_tf=False,
     pathcnn_kernel_size=3, more_conv=False, pca_sim_dim=5, drop_irr_pathway=False, mutual_classif=False,
+    edge_select=False, edge_select_threshold=1.0, allow_no_edge_pretrain=False,
 )
 
 
@@ -61,8 +62,9 @@ def parse_opts(argv=None):
     ap.add_argument("--patients", type=int, default=96, help="synthetic cohort size")
     ap.add_argument("--small", action="store_true", help="shrunken gene graph (tests)")
     ap.add_argument("--fold_prep", action="store_true",
-                    help="prepare the fold as train.py:293-298 does: mutual-information mask, per-pathway PCA of the members "
-                         "it keeps, projection started from the principal axes, PCA image in pathway_node_attr")
+                    help="prepare the fold as train.py:293-299 does: mutual-information mask, per-pathway PCA of the members "
+                         "it keeps, projection started from the principal axes, PCA image in pathway_node_attr, topology "
+                         "narrowed to the kept nodes (and by --edge_select)")
     for k, v in DEFAULTS.items():
         if isinstance(v, bool):
             ap.add_argument("--" + k, action="store_true", default=v)
@@ -193,6 +195,13 @@ def run(args):
         model.set_info_mask(mask.to(torch.float32))
         data.recalculate_pca_bo_selected_gene(mask)
         model.set_pca_params(data.pca_components.to(device), mask)
+        # train.py:299: the topology narrowed to the nodes the mask kept; with --edge_select every remaining PPI edge
+        # also has to pass valid_pca_mutual_info on the training patients
+        edge_index, _ = data.recalculate_edge_bo_selected_gene(
+            mask, train_idx, edge_select=args.edge_select, edge_select_threshold=args.edge_select_threshold,
+            random_state=args.random_state if args.freeze_mutual_select_init else None,
+            mutual_classif=args.mutual_classif, allow_no_edge_pretrain=args.allow_no_edge_pretrain)
+        logging.info("fold topology: %d of %d edges", edge_index.shape[1], data._base_edge_index.shape[1])
     model.to(device)
     broadcast_parameters(model)
     # train.py:112-114 (Adam + StepLR) and :63-66 (clip_grad_norm_(20) + step) as ONE fused update of the flat buffer
