@@ -1158,6 +1158,36 @@ int mlgnn_edge_mi(const double* xt, const int32_t* pairs, const double* noise, c
                   int k, int n_labels, void* stream);
 
 /*
+ * The --knn_mutual_info form of that test for many node pairs at once (csrc/kraskov_mi.hip), fp64: what the reference's
+ * utils/knnie.py::kraskov_mi (Kraskov, Stoegbauer, Grassberger 2004, on three KD-trees) gives for the two raw end columns
+ * of a PPI edge against the label, one workgroup per pair, one launch.  No PCA, no scaling, no noise.
+ *   xt [n_nodes, N] node-major, pairs [P, 2] int32 node indices (clamped to [0, n_nodes) inside the kernel), y [N] the
+ *   label as a double column, psi [N + 1] with psi[m] = digamma(m) for m >= 1, base = digamma(k) + digamma(N).  Pair
+ *   (s, t) with the columns a = xt[s], b = xt[t]:
+ *     d_ij = max(|a_i - a_j|, |b_i - b_j|, |y_i - y_j|)
+ *     kd_i = the (k + 1)-th smallest d_ij over all j, self included, duplicates counted
+ *     r_i  = kd_i - 1e-15                                           one fp64 subtraction, as the reference writes it
+ *     nx_i = #{ j : max(|a_i - a_j|, |b_i - b_j|) <= r_i },  ny_i = #{ j : |y_i - y_j| <= r_i }     self included
+ *     mi [P] = base - (1 / N) sum_i psi(nx_i) - (1 / N) sum_i psi(ny_i)
+ *   (the reference's sums of log kd_i cancel identically); NaN where some kd_i is 0 or not finite, where the reference
+ *   takes log(0).  t < 0 (single-column mode): b is left out.  kd [P, N] fp64, nx [P, N] and ny [P, N] int32 in sample
+ *   order, or NULL (each on its own).  Every element of every output handed in is written.
+ * No atomics, no fused multiply-add, every sum in a fixed order: bitwise reproducible, and a pair's bits do not depend on
+ * the other pairs.  Shapes (mlgnn_kraskov_mi_supported; with_details: whether kd, nx or ny is wanted):
+ * 1 <= k <= MLGNN_KRASKOV_MAX_NEIGHBORS (the list of the k + 1 nearest distances lives in registers),
+ * k + 1 <= N <= 2048, 0 <= P < 2^31, n_nodes >= 0 (>= 1 where P > 0) with n_nodes * N * 8 below 4 GiB, and P * N * 8
+ * below 4 GiB when a detail is wanted.  MLGNN_E_NULL for a NULL xt, pairs, y, psi or mi, then MLGNN_E_SHAPE for anything
+ * else (as in mlgnn_edge_mi, NULL operands are reported before shape errors); both before anything is launched.  P = 0 is
+ * a no-op (nothing is read or written).  No workspace.  NaN input makes that pair's outputs NaN or arbitrary, never an
+ * access out of bounds.
+ */
+#define MLGNN_KRASKOV_MAX_NEIGHBORS 16
+int mlgnn_kraskov_mi_supported(int64_t n, int64_t n_nodes, int64_t n_pairs, int k, int with_details);
+int mlgnn_kraskov_mi(const double* xt, const int32_t* pairs, const double* y, const double* psi, double base, double* mi,
+                     double* kd, int32_t* nx, int32_t* ny, int64_t n, int64_t n_nodes, int64_t n_pairs, int k,
+                     void* stream);
+
+/*
  * Batched PCA over ragged column segments (csrc/pathway_pca.hip), fp64: what sklearn.decomposition.PCA(svd_solver='full')
  * gives for every (pathway, omics) segment of a fold, one workgroup per segment, one launch.
  *   xt [F, N] feature-major (row f = column f of the data), cols [T] indices into [0, F) grouped by segment, seg_ptr

@@ -29,6 +29,7 @@
 // centred sums) + 3 (mean, deviation, mean magnitude of the score) before the estimator's own.
 #include <math.h>
 
+#include "block_sums.h"
 #include "common.h"
 #include "launch.h"
 #include "mlgnn.h"
@@ -45,25 +46,6 @@ bool shape_ok(int64_t n, int64_t n_nodes, int64_t P, int64_t k, int64_t n_labels
   if (n_nodes < 0 || n_nodes > most || P < 0 || P >= ((int64_t)1 << 31)) return false;
   if (P > 0 && n_nodes < 1) return false;
   return !with_score || P <= most;
-}
-
-// The sums of V values over the workgroup in the fixed order, in every lane.  `scratch`: V * kWavesPerBlock doubles of
-// LDS that no other reduction of the kernel uses (so one barrier suffices).
-template <int V>
-__device__ __forceinline__ void block_sums(double (&v)[V], double* scratch) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int q = 0; q < V; ++q) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v[q] += __shfl_xor(v[q], o);
-    if ((tid & (kWave - 1)) == 0) scratch[q * kWavesPerBlock + tid / kWave] = v[q];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < V; ++q) {
-    const double* r = scratch + q * kWavesPerBlock;
-    v[q] = ((r[0] + r[1]) + r[2]) + r[3];
-  }
 }
 
 constexpr int kScratchDoubles = (2 + 3 + 1 + 1 + 1) * kWavesPerBlock;   // means, centred sums, mean, deviation, magnitude

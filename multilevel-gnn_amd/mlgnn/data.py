@@ -217,7 +217,8 @@ class SyntheticTCGA(torch.utils.data.Dataset):
 
     def recalculate_edge_bo_selected_gene(self, mutual_info_mask, indice=None, edge_select=False, edge_select_threshold=1.0,
                                           n_neighbors=3, random_state=None, mutual_classif=True,
-                                          allow_no_edge_pretrain=False):
+                                          allow_no_edge_pretrain=False, knn_mutual_info=False, bidir_edge=False,
+                                          mute_edge=""):
         """``MyData.recalculate_edge_bo_selected_gene`` (multiloader.py:581-700) on the synthetic cohort: the topology
         narrowed to what the mask kept.  A node is selected iff some member ``m`` with ``gene_pca_match[m] == node`` has
         ``mask[m, 0] > 0`` (``None``: every node).  Every call starts from the topology drawn at construction: its first
@@ -225,9 +226,17 @@ class SyntheticTCGA(torch.utils.data.Dataset):
         candidates, also have to pass :func:`mlgnn.edge_select.edge_select` on the patients ``indice`` when
         ``edge_select`` is set (``valid_pca_mutual_info``).  Survivors keep their order and attributes and become the
         shared ``edge_index`` / ``edge_attr``; with none, the topology becomes empty under ``allow_no_edge_pretrain`` and
-        stays as it was otherwise (:689-694).  -> ``(edge_index, edge_attr)``."""
+        stays as it was otherwise (:689-694).  -> ``(edge_index, edge_attr)``.
+        The omics of a PPI candidate is that of its source node, ``v // node_num`` (the layout of the cross-omics edges).
+        ``mute_edge``: a string of omics digits whose PPI candidates are dropped before any estimator runs (:642).
+        ``knn_mutual_info`` (with ``edge_select``): the candidates whose omics is not 1 go through
+        :func:`mlgnn.kraskov.edge_select_knn`, those of omics 1 through ``edge_select`` as before (:838); each call keeps
+        its own end-node values.  ``bidir_edge``: every surviving PPI edge ``(s, t)`` is directly followed by ``(t, s)``
+        with the same attribute (:652-654); the cross-omics edges are not mirrored."""
         base_index, base_attr = self._base_edge_index, self._base_edge_attr
         n_edges = base_index.shape[1]
+        is_ppi = torch.arange(n_edges) >= self.n_cross
+        omics = base_index[0] // self.node_num
         if mutual_info_mask is None:
             selected = torch.ones(self.NN, dtype=torch.bool)
         else:
@@ -235,19 +244,40 @@ class SyntheticTCGA(torch.utils.data.Dataset):
             selected = torch.zeros(self.NN, dtype=torch.bool)
             selected[self.gene_pca_match[kept.cpu() & (self.gene_pca_match >= 0)]] = True
         survive = selected[base_index[0]] & selected[base_index[1]]
+        for digit in str(mute_edge):
+            if digit.isdigit():
+                survive = survive & ~(is_ppi & (omics == int(digit)))
         if edge_select:
-            from .edge_select import edge_select as select
             if indice is None:
                 raise ValueError("recalculate_edge_bo_selected_gene: edge_select needs the training patients (indice)")
             rows = torch.as_tensor(indice, dtype=torch.long)
             ppi = torch.nonzero(survive[self.n_cross:])[:, 0] + self.n_cross
-            keep, _, _ = select(self.x[rows, :, 0], self.labels[rows], base_index[:, ppi], edge_select_threshold,
-                                n_neighbors, random_state, mutual_classif)
             survive = survive.clone()
-            survive[ppi] = torch.from_numpy(np.asarray(keep, dtype=bool))
+            if knn_mutual_info:
+                from . import kraskov
+                knn, pca = ppi[omics[ppi] != 1], ppi[omics[ppi] == 1]
+                if knn.numel():
+                    keep, _, _ = kraskov.edge_select_knn(self.x[rows, :, 0], self.labels[rows].to(torch.float64),
+                                                         base_index[:, knn], edge_select_threshold)
+                    survive[knn] = torch.from_numpy(np.asarray(keep, dtype=bool))
+                ppi = pca
+            if not knn_mutual_info or ppi.numel():
+                from .edge_select import edge_select as select
+                keep, _, _ = select(self.x[rows, :, 0], self.labels[rows], base_index[:, ppi], edge_select_threshold,
+                                    n_neighbors, random_state, mutual_classif)
+                survive[ppi] = torch.from_numpy(np.asarray(keep, dtype=bool))
         assert survive.shape == (n_edges,)
         if bool(survive.any()):
-            self.edge_index, self.edge_attr = base_index[:, survive], base_attr[survive]
+            if bidir_edge:
+                # the survivors in order, every PPI one twice: as drawn, then reversed
+                at = torch.repeat_interleave(torch.nonzero(survive)[:, 0], 1 + is_ppi[survive].long())
+                second = torch.zeros_like(at, dtype=torch.bool)
+                second[1:] = at[1:] == at[:-1]
+                index = base_index[:, at]
+                self.edge_index = torch.where(second[None, :], index.flip(0), index)
+                self.edge_attr = base_attr[at]
+            else:
+                self.edge_index, self.edge_attr = base_index[:, survive], base_attr[survive]
         elif allow_no_edge_pretrain:
             self.edge_index, self.edge_attr = base_index[:, :0], base_attr[:0]
         return self.edge_index, self.edge_attr

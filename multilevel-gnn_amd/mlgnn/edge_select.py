@@ -173,7 +173,8 @@ def edge_select(values, y, edge_index, threshold=1.0, n_neighbors=3, random_stat
     runs (it also serves ``mutual_classif=False``).  With ``random_state=None`` the kernel leg draws one unseeded noise
     vector per call where the reference draws one per scikit-learn call.  ``EDGE_SELECT_STATS`` counts the leg."""
     if knn_mutual_info:
-        raise NotImplementedError("knn_mutual_info (the reference's kraskov_mi) is not served")
+        raise NotImplementedError("knn_mutual_info (the reference's kraskov_mi) is not served by edge_select: call "
+                                  "mlgnn.kraskov.edge_select_knn for the edges whose omics is not 1")
     ei = _host(edge_index)
     if ei.ndim != 2 or ei.shape[0] != 2:
         raise ValueError("edge_select: edge_index must be [2, E], got %s" % (ei.shape,))

@@ -52,7 +52,8 @@ DEFAULTS = dict(
     input_drop=None, input_emb_drop=None, gnn_dropout=0.0, device_num=1, edge_type="grnboost2",
     reduction_method="linear_projection", freeze_mutual_select_init=False, random_state=12345, remain_all_tf=False,
     pathcnn_kernel_size=3, more_conv=False, pca_sim_dim=5, drop_irr_pathway=False, mutual_classif=False,
-    edge_select=False, edge_select_threshold=1.0, allow_no_edge_pretrain=False,
+    edge_select=False, edge_select_threshold=1.0, allow_no_edge_pretrain=False, knn_mutual_info=False, bidir_edge=False,
+    mute_edge="",
 )
 
 
@@ -200,7 +201,8 @@ def run(args):
         edge_index, _ = data.recalculate_edge_bo_selected_gene(
             mask, train_idx, edge_select=args.edge_select, edge_select_threshold=args.edge_select_threshold,
             random_state=args.random_state if args.freeze_mutual_select_init else None,
-            mutual_classif=args.mutual_classif, allow_no_edge_pretrain=args.allow_no_edge_pretrain)
+            mutual_classif=args.mutual_classif, allow_no_edge_pretrain=args.allow_no_edge_pretrain,
+            knn_mutual_info=args.knn_mutual_info, bidir_edge=args.bidir_edge, mute_edge=str(args.mute_edge))
         logging.info("fold topology: %d of %d edges", edge_index.shape[1], data._base_edge_index.shape[1])
     model.to(device)
     broadcast_parameters(model)
