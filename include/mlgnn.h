@@ -1158,6 +1158,30 @@ int mlgnn_edge_mi(const double* xt, const int32_t* pairs, const double* noise, c
                   int k, int n_labels, void* stream);
 
 /*
+ * That test under mutual_info_regression -- the reference's default, mutual_classif false -- for many node pairs at once
+ * (csrc/edge_select_cc.hip), fp64: PCA(n_components=1) on the two end columns, then mutual_info_regression of its score
+ * against the label, one workgroup per pair, one launch.
+ *   xt, pairs as in mlgnn_edge_mi; noise_x [N] the launch's standard normal draws for the feature; y_prepared [N] the
+ *   target as mutual_info_regression prepares it (scaled, its own noise added; the host's work, the same for every pair);
+ *   psi [N + 1] and base = digamma(N) + digamma(k) as in mlgnn_mutual_info_cc.  Pair (s, t):
+ *     value_i = z_i + (1e-10 max(1, mean|z|)) noise_x[i]          z: the scaled score of mlgnn_edge_mi, same operations
+ *     mi [P] = the estimate of mlgnn_mutual_info_cc on the column `value` against y_prepared
+ *   t < 0 (single-column mode): score = xt[s], uncentred; the rest as above.  score [P, N] = `value` in sample order, or
+ *   NULL; nx, ny [P, N] int32 = the counts of mlgnn_mutual_info_cc in sample order, or NULL (each on its own).
+ * No atomics, no fused multiply-add, every sum in a fixed order: bitwise reproducible, and a pair's bits do not depend on
+ * the other pairs.  Shapes (mlgnn_edge_mi_cc_supported; with_score: whether `score` is wanted): 2 <= N <= 2048,
+ * 1 <= k <= min(N - 1, MLGNN_MI_CC_MAX_NEIGHBORS), 0 <= P < 2^31, n_nodes >= 0 (>= 1 where P > 0) with n_nodes * N * 8
+ * below 4 GiB, and P * N * 8 below 4 GiB when `score` is wanted.  MLGNN_E_NULL for a NULL xt, pairs, noise_x, y_prepared,
+ * psi or mi, then MLGNN_E_SHAPE for anything else (NULL operands are reported before shape errors); both before anything
+ * is launched.  P = 0 is a no-op (nothing is read or written).  No workspace.  NaN input makes that pair's outputs NaN or
+ * arbitrary, never an access out of bounds.
+ */
+int mlgnn_edge_mi_cc_supported(int64_t n, int64_t n_nodes, int64_t n_pairs, int k, int with_score);
+int mlgnn_edge_mi_cc(const double* xt, const int32_t* pairs, const double* noise_x, const double* y_prepared,
+                     const double* psi, double base, double* mi, double* score, int32_t* nx, int32_t* ny, int64_t n,
+                     int64_t n_nodes, int64_t n_pairs, int k, void* stream);
+
+/*
  * The --knn_mutual_info form of that test for many node pairs at once (csrc/kraskov_mi.hip), fp64: what the reference's
  * utils/knnie.py::kraskov_mi (Kraskov, Stoegbauer, Grassberger 2004, on three KD-trees) gives for the two raw end columns
  * of a PPI edge against the label, one workgroup per pair, one launch.  No PCA, no scaling, no noise.

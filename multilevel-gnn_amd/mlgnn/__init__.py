@@ -20,6 +20,8 @@ from .mutual_info import (mutual_info_cc, mutual_info_regression, mutual_info_re
                           prepare_regression)
 from .pca import fold_pca, pathway_pca, pathway_pca_supported  # noqa: F401
 from .edge_select import edge_select, edge_select_supported, pair_mutual_info  # noqa: F401
+from .edge_select_reg import (edge_select_regression, edge_select_regression_supported,  # noqa: F401
+                              pair_mutual_info_regression)
 from .kraskov import edge_select_knn, kraskov_mi, kraskov_mi_host, kraskov_mi_supported  # noqa: F401
 from .ops import (LowRankEdge, RankOneEdge, TableEdge, edge_type_embedding, gen_aggregate, share_edge_gradient,  # noqa: F401
                   weighted_mean_aggregate)

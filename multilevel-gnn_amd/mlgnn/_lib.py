@@ -135,6 +135,8 @@ SIGNATURES = {
     "mlgnn_mutual_info_cc": (_INT, [_P, _P, _P, _c.c_double, _P, _P, _P, _I64, _I64, _INT, _P]),
     "mlgnn_edge_mi_supported": (_INT, [_I64, _I64, _I64, _INT, _INT, _INT]),
     "mlgnn_edge_mi": (_INT, [_P, _P, _P, _P, _P, _c.c_double, _P, _P, _P, _I64, _I64, _I64, _INT, _INT, _P]),
+    "mlgnn_edge_mi_cc_supported": (_INT, [_I64, _I64, _I64, _INT, _INT]),
+    "mlgnn_edge_mi_cc": (_INT, [_P, _P, _P, _P, _P, _c.c_double, _P, _P, _P, _P, _I64, _I64, _I64, _INT, _P]),
     "mlgnn_kraskov_mi_supported": (_INT, [_I64, _I64, _I64, _INT, _INT]),
     "mlgnn_kraskov_mi": (_INT, [_P, _P, _P, _P, _c.c_double, _P, _P, _P, _P, _I64, _I64, _I64, _INT, _P]),
     "mlgnn_pathway_pca_supported": (_INT, [_I64] * 4 + [_INT]),

@@ -224,7 +224,9 @@ class SyntheticTCGA(torch.utils.data.Dataset):
         ``mask[m, 0] > 0`` (``None``: every node).  Every call starts from the topology drawn at construction: its first
         ``n_cross`` edges, the -1/+1 cross-omics edges, survive iff both ends are selected; the others, the PPI
         candidates, also have to pass :func:`mlgnn.edge_select.edge_select` on the patients ``indice`` when
-        ``edge_select`` is set (``valid_pca_mutual_info``).  Survivors keep their order and attributes and become the
+        ``edge_select`` is set (``valid_pca_mutual_info``; with ``mutual_classif`` false,
+        :func:`mlgnn.edge_select_reg.edge_select_regression` on the labels as float64, the pair calls unseeded as in
+        the reference).  Survivors keep their order and attributes and become the
         shared ``edge_index`` / ``edge_attr``; with none, the topology becomes empty under ``allow_no_edge_pretrain`` and
         stays as it was otherwise (:689-694).  -> ``(edge_index, edge_attr)``.
         The omics of a PPI candidate is that of its source node, ``v // node_num`` (the layout of the cross-omics edges).
@@ -262,9 +264,15 @@ class SyntheticTCGA(torch.utils.data.Dataset):
                     survive[knn] = torch.from_numpy(np.asarray(keep, dtype=bool))
                 ppi = pca
             if not knn_mutual_info or ppi.numel():
-                from .edge_select import edge_select as select
-                keep, _, _ = select(self.x[rows, :, 0], self.labels[rows], base_index[:, ppi], edge_select_threshold,
-                                    n_neighbors, random_state, mutual_classif)
+                if mutual_classif:
+                    from .edge_select import edge_select as select
+                    keep, _, _ = select(self.x[rows, :, 0], self.labels[rows], base_index[:, ppi], edge_select_threshold,
+                                        n_neighbors, random_state, mutual_classif)
+                else:
+                    from .edge_select_reg import edge_select_regression
+                    keep, _, _ = edge_select_regression(self.x[rows, :, 0], self.labels[rows].to(torch.float64),
+                                                        base_index[:, ppi], edge_select_threshold, n_neighbors,
+                                                        random_state)
                 survive[ppi] = torch.from_numpy(np.asarray(keep, dtype=bool))
         assert survive.shape == (n_edges,)
         if bool(survive.any()):

@@ -11,7 +11,8 @@ mutual_info_cd` prepares them.
 
 :func:`edge_select` runs the reference's own loop of scikit-learn calls on the host where the kernel does not apply
 (switch off, no GPU, ``mutual_classif`` false, a label that occurs once, small classes, more than 2048 patients); that
-leg is the reference's arithmetic, not a stand-in for a missing kernel.
+leg is the reference's arithmetic, not a stand-in for a missing kernel.  The fold preparation sends ``mutual_classif`` false
+to :func:`mlgnn.edge_select_reg.edge_select_regression` instead, which has a kernel of its own.
 
 Allocation: every device output is ``torch.zeros`` (as in :mod:`mlgnn.pca`, for the reason its docstring gives); that the
 kernel writes every output element whatever they held before is tested against the entry point directly
@@ -124,10 +125,12 @@ def pair_mutual_info(values, y, pairs, n_neighbors=3, random_state=None, return_
     return out if len(out) > 1 else out[0]
 
 
-def sklearn_edge_select(values, y, edge_index, threshold=1.0, n_neighbors=3, random_state=None, mutual_classif=True):
+def sklearn_edge_select(values, y, edge_index, threshold=1.0, n_neighbors=3, random_state=None, mutual_classif=True,
+                        pair_random_state=None):
     """The reference's loop (``valid_pca_mutual_info``), call for call: per edge ``PCA(n_components=1)`` on the two end
     columns and the mutual information of its score, the end columns' own cached per node.  As in the reference the
-    regression path's pair call passes no ``random_state``.  (``n_neighbors`` is the reference's default of 3 there.)"""
+    regression path's pair call passes no ``random_state``: it takes ``pair_random_state``, whose default is the
+    reference's.  (``n_neighbors`` is the reference's default of 3 there.)"""
     from sklearn.decomposition import PCA
     from sklearn.feature_selection import mutual_info_classif, mutual_info_regression
     x = _host(values).astype(np.float64, copy=False)
@@ -150,7 +153,7 @@ def sklearn_edge_select(values, y, edge_index, threshold=1.0, n_neighbors=3, ran
         if mutual_classif:
             mi_pair[e] = mutual_info_classif(pca_data, y, n_neighbors=n_neighbors, random_state=random_state)[0]
         else:
-            mi_pair[e] = mutual_info_regression(pca_data, y, n_neighbors=n_neighbors)[0]
+            mi_pair[e] = mutual_info_regression(pca_data, y, n_neighbors=n_neighbors, random_state=pair_random_state)[0]
         keep[e] = mi_pair[e] > threshold * max(node(s), node(t))
     return keep, mi_pair, mi_node
 
