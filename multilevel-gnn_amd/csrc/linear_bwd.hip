@@ -37,6 +37,7 @@
 
 namespace mlgnn {
 
+using f32x2 = __attribute__((ext_vector_type(2))) float;
 constexpr int kLbThreads = 512, kLbWaves = 8, kLbStage = 32;
 enum { LB_LN = 0, LB_PLAIN = 1, LB_SHIFT = 2 };
 
@@ -65,10 +66,20 @@ __device__ __forceinline__ i32x4 lds_read_b128(uint32_t addr) {
   return v;
 }
 template <int OFF>
+__device__ __forceinline__ i32x2 lds_read_b64(uint32_t addr) {
+  i32x2 v;
+  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
+  return v;
+}
+template <int OFF>
 __device__ __forceinline__ i32x2 lds_read_tr16(uint32_t addr) {
   i32x2 v;
   asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
   return v;
+}
+// (an LDS write the asm reads above are ordered behind: both are volatile, and the LDS serves a wave in issue order)
+__device__ __forceinline__ void lds_write_f32(uint32_t addr, float v) {
+  asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory");
 }
 #define LB_WAIT_LGKM(N) asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory")
 // The results of the asm reads / loads are tied to the wait that makes them valid ("+v"): without the tie the compiler
@@ -78,8 +89,8 @@ __device__ __forceinline__ void lgkm_landed(i32x4& a, i32x4& b) {
   asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
 }
 template <int N>
-__device__ __forceinline__ void lgkm_landed(i32x4& a, i32x4& b, i32x4& c, i32x4& d) {
-  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N) : "memory");
+__device__ __forceinline__ void lgkm_landed(i32x2& a, i32x2& b, i32x2& c) {
+  asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(a), "+v"(b), "+v"(c) : "n"(N) : "memory");
 }
 template <int N>
 __device__ __forceinline__ void lgkm_landed(i32x2& a, i32x2& b, i32x2& c, i32x2& d) {
@@ -122,6 +133,17 @@ __device__ __forceinline__ void lb_wait_vm() {
 // rho(r, h) = mfma32_row(r, h) = (r & 3) + 8 (r >> 2) + 4 h.  Row group G = 2 kk + h (kk = 16-deep k-step of the dW
 // product) holds rho(8 kk + j, h), j = 0..7: rows 16 kk + 4 h + {0..3} and + 8 + {0..3}.
 
+// LDS of a workgroup: two go stages (hi + lo planes), three x stages, the exchange area in two parities, and for the
+// LayerNorm shape (M = 128) the rstd copies
+template <int M>
+constexpr int lb_exchange_floats() { return kLbWaves * (M == 256 ? 512 : 64); }
+template <int M, int K>
+constexpr int lb_lds_bytes() {
+  return 2 * (2 * 4 * (M + 4) * 16) + 3 * (kLbStage * K * 4) + 2 * lb_exchange_floats<M>() * 4 +
+         (M == 256 ? 0 : 3 * kLbWaves * 256);
+}
+static_assert(lb_lds_bytes<128, 256>() <= 160 * 1024 && lb_lds_bytes<256, 128>() <= 160 * 1024, "160 KiB of LDS per CU");
+
 template <int M, int K, int EPI>
 __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) {
   constexpr int NC = K / 32, NM = kLbWaves / NC, MW = M / NM;     // column strips of dX, splits of the m range, m per wave
@@ -136,9 +158,14 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
   constexpr int UPT = M * 4 / kLbThreads;     // go units (column, row group) per thread
   constexpr int DMA = kXStageB / 1024 / kLbWaves;      // LDS-DMA instructions per wave and stage
   constexpr int kExB = 2 * kBufB + 3 * kXStageB;       // exchange area behind the stages
-  constexpr int kTotOff = 4 * M + 64;                  // LB_LN: the per-wave totals of the row sums, [8 waves][64]
-  constexpr int kExFloats = 4 * M + 64 + (NM == 2 ? kLbWaves * 512 : kLbWaves * 64);
+  // the exchange area has two parities (stage i uses parity i & 1): with ONE workgroup barrier per stage a wave may
+  // write the partials of stage i + 1 while a slower one still reads those of stage i.  It cannot reach stage i + 2's
+  // before the slow wave has passed the barrier of stage i + 1, which lies behind that wave's reads of stage i.
+  constexpr int kParFloats = lb_exchange_floats<M>();  // per wave: 64 row-sum partials (LB_LN) or 8 x 64 partner values
+  constexpr int kExFloats = 2 * kParFloats;
+  static_assert(kExFloats >= 4 * M + kLbWaves, "the tail of the kernel folds the bias sums and the maxima in this area");
   constexpr int kRsB = kExB + kExFloats * 4;           // LB_LN: rstd of a stage's rows, [3 stages][8 waves][64] floats
+  static_assert(kRsB + (EPI == LB_LN ? 3 * kLbWaves * 256 : 0) == lb_lds_bytes<M, K>(), "lb_lds_bytes() is this layout");
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
   float* ex = reinterpret_cast<float*>(smem + kExB);
@@ -281,9 +308,22 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
   }
   const uint32_t a_x = lds0 + 2 * kBufB + (uint32_t)((4 * h) * K + col) * 4u;  // x[rho(r, h)][col] of a stage
 
-  constexpr int E_L = EPI == LB_LN ? 1 : (EPI == LB_SHIFT ? 8 : 0);        // vector-memory operations per iteration
-  constexpr int E_S = EPI == LB_SHIFT ? 16 : (EPI == LB_LN ? 16 : 8);
-  constexpr int kVmPerIter = E_L + 8 * UPT + DMA + E_S;
+  // One iteration = one stage, ONE workgroup barrier:
+  //   loads of the stages ahead | the two products | go of stage i + 1 into the other plane buffer | epilogue part 1
+  //   (partials into the exchange area) | BARRIER | epilogue part 2 (partner's partials, stores).
+  // Vector-memory operations of a wave in issue order (vmcnt retires them in this order), the same in every iteration,
+  // ragged stage or not:
+  //   [epilogue operands of stage i: 1 rstd LDS-DMA (LB_LN) or 8 lse loads] [8 UPT go loads of stage i + 1]
+  //   [DMA LDS-DMAs of x stage i + 2] ... [the stores of stage i, behind the barrier]
+  // so the ONE counted wait of the loop, vmcnt(DMA) between the products and the commit, leaves only x stage i + 2
+  // in flight: go of stage i + 1, this stage's epilogue operands, this wave's pieces of x stage i + 1 (requested one
+  // iteration ago) and the stores of stage i - 1 are all older.  Why the one barrier orders every LDS region:
+  //   * go plane buf ^ 1 was last read by the products of stage i - 1, which every wave finished in front of the
+  //     barrier of stage i - 1; it is written here in front of the barrier of stage i and read behind it.
+  //   * x buffer (i + 2) % 3 held stage i - 1: every wave took its xv[16] from it in front of the barrier of stage
+  //     i - 1, and the LDS-DMAs into it are issued behind that barrier.  x stage i + 1 is read behind the barrier of
+  //     stage i; every wave has waited for its own pieces in front of it.
+  //   * the exchange area: see kParFloats.
 
   if (n > 0) {
     // ---- prologue: stage 0 committed, x stages 0 and 1 on their way -------------------------------------------------
@@ -422,7 +462,16 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
       }
 
       __builtin_amdgcn_sched_barrier(0);
+      // ---- the next stage of go into the other plane buffer ----------------------------------------------------------
+      // vmcnt(DMA): behind the go loads of this iteration's top only its DMA LDS-DMAs were issued (see the issue order
+      // above); everything older has landed with them, this wave's pieces of x stage i + 1 included
+      if constexpr (EPI == LB_SHIFT) vm_landed<DMA>(lse8);
+#pragma unroll
+      for (int q = 0; q < UPT; ++q) vm_landed<DMA>(gr[q]);
+      commit_go(buf ^ 1, row_of(i + 1), i + 1 < n);
+      __builtin_amdgcn_sched_barrier(0);
       // ---- epilogue ---------------------------------------------------------------------------------------------------
+      float* expar = ex + buf * kParFloats;          // this stage's parity of the exchange area
       if constexpr (EPI == LB_LN) {
         float g[16];
         const bool odd_row = (lane & 16) != 0;
@@ -448,38 +497,57 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
           mine = (r_mine == r) ? u : mine;
         }
         // value index = lane: row16 = lane >> 4 is (sum g, h = 0), (sum g xhat, h = 0), (sum g, h = 1), (sum g xhat, h = 1)
-        ex[wave * 64 + lane] = mine;
-        // (the rstd copy of this stage was requested at the top of the iteration, before the loads of the stages ahead)
-        lb_wait_vm<8 * UPT + DMA>();                   // (only the loads of the stages ahead may still be out)
-        const uint32_t ars = lds0 + kRsB + (uint32_t)(((i % 3) * kLbWaves + wave) * 256 + 16 * h);
-        i32x4 rs0_ = lds_read_b128<0>(ars), rs1_ = lds_read_b128<32>(ars), rs2_ = lds_read_b128<64>(ars),
-              rs3_ = lds_read_b128<96>(ars);          // (tied to the wait below as they are: a copy could be read early)
-        lgkm_landed<0>(rs0_, rs1_, rs2_, rs3_);      // (and the partial sums above are in LDS)
-        float rs[16];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          rs[q] = __builtin_bit_cast(f32x4, rs0_)[q]; rs[4 + q] = __builtin_bit_cast(f32x4, rs1_)[q];
-          rs[8 + q] = __builtin_bit_cast(f32x4, rs2_)[q]; rs[12 + q] = __builtin_bit_cast(f32x4, rs3_)[q];
-        }
-        // (bare barrier: __syncthreads() would also drain the loads and LDS-DMAs of the stages ahead)
+        expar[wave * 64 + lane] = mine;
+        LB_WAIT_LGKM(0);                              // (the partial sums and the go planes above are in LDS)
+        // (bare barrier: __syncthreads() would also drain the LDS-DMAs of the stage ahead)
         __builtin_amdgcn_s_barrier();
         float tot;
         {
-          const uint32_t ae = lds0 + kExB + (uint32_t)lane * 4u;
+          const uint32_t ae = lds0 + kExB + (uint32_t)(buf * kParFloats + lane) * 4u;
           float e[8] = {lds_read_f32<0>(ae), lds_read_f32<256>(ae), lds_read_f32<512>(ae), lds_read_f32<768>(ae),
                         lds_read_f32<1024>(ae), lds_read_f32<1280>(ae), lds_read_f32<1536>(ae), lds_read_f32<1792>(ae)};
           lgkm_landed<0>(e);
           tot = ((((((e[0] + e[1]) + e[2]) + e[3]) + e[4]) + e[5]) + e[6]) + e[7];     // the 8 column strips, in order
         }
+        // every lane needs the 16 + 16 totals of its half: the wave hands its 64 totals round through a slot of its own
+        // (one write, then reads at addresses the whole half shares: broadcasts, no bank conflict).  The slot is
+        // where this wave's partials of the OTHER parity lie: every wave has read those of stage i - 1 in front of the
+        // barrier above, and the next to write there is this wave, in part 1 of stage i + 1.
+        const uint32_t slot = lds0 + kExB + (uint32_t)((buf ^ 1) * kParFloats + wave * 64) * 4u;
+        lds_write_f32(slot + (uint32_t)lane * 4u, tot);
+        const uint32_t as = slot + 128u * (uint32_t)h;       // [0..15] sum g, [16..31] sum g xhat of rows rho(r, h)
+        // (the rstd copy of this stage was requested at the top of the iteration, before the go loads: it has landed
+        // with the wait in front of the commit)
+        const uint32_t ars = lds0 + kRsB + (uint32_t)(((i % 3) * kLbWaves + wave) * 256 + 16 * h);
         constexpr float inv_k = 1.0f / K;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float s1 = __shfl(tot, 32 * h + r) * inv_k;
-          const float s2 = __shfl(tot, 32 * h + 16 + r) * inv_k;
-          g[r] = rs[r] * (g[r] - s1 - xv[r] * s2);
-          if (!full && r0 + mfma32_row(r, h) >= p.N) g[r] = 0.f;              // (rows past the end: rstd is not theirs)
-          om = fmaxf(om, fabsf(g[r]));
+        // registers 2 P, 2 P + 1 per step -- sum g, sum g xhat, rstd: three 8-byte reads -- one step ahead of their use
+        // (wider steps do not fit: eight more registers live here spill loop invariants to scratch.  The pair is bit-cast
+        // as a whole and then indexed: an int element bit-cast to float in the unrolled loop reads element 0 twice)
+        i32x2 tp[2][3];
+#define LB_TOT_READ(SLOT, P)                                                                           \
+        tp[SLOT][0] = lds_read_b64<8 * (P)>(as); tp[SLOT][1] = lds_read_b64<64 + 8 * (P)>(as);         \
+        tp[SLOT][2] = lds_read_b64<32 * ((P) >> 1) + 8 * ((P) & 1)>(ars);
+#define LB_TOT_USE(SLOT, P, CNT)                                                                       \
+        lgkm_landed<CNT>(tp[SLOT][0], tp[SLOT][1], tp[SLOT][2]);                                       \
+        _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                \
+          const int r = 2 * (P) + j;                                                                   \
+          const float s1 = __builtin_bit_cast(f32x2, tp[SLOT][0])[j] * inv_k;                          \
+          const float s2 = __builtin_bit_cast(f32x2, tp[SLOT][1])[j] * inv_k;                          \
+          g[r] = __builtin_bit_cast(f32x2, tp[SLOT][2])[j] * (g[r] - s1 - xv[r] * s2);                 \
+          if (!full && r0 + mfma32_row(r, h) >= p.N) g[r] = 0.f; /* (rows past the end: rstd is not theirs) */ \
+          om = fmaxf(om, fabsf(g[r]));                                                                 \
         }
+        LB_TOT_READ(0, 0)
+        LB_TOT_READ(1, 1) LB_TOT_USE(0, 0, 3)
+        LB_TOT_READ(0, 2) LB_TOT_USE(1, 1, 3)
+        LB_TOT_READ(1, 3) LB_TOT_USE(0, 2, 3)
+        LB_TOT_READ(0, 4) LB_TOT_USE(1, 3, 3)
+        LB_TOT_READ(1, 5) LB_TOT_USE(0, 4, 3)
+        LB_TOT_READ(0, 6) LB_TOT_USE(1, 5, 3)
+        LB_TOT_READ(1, 7) LB_TOT_USE(0, 6, 3)
+        LB_TOT_USE(1, 7, 0)
+#undef LB_TOT_READ
+#undef LB_TOT_USE
         // (uniform base + 32-bit lane offset: one address register for the 16 stores)
         char* out = reinterpret_cast<char*>(p.dx + (size_t)r0 * K);
         const uint32_t o0 = (uint32_t)(4 * h * K + col) * 4u;
@@ -498,15 +566,15 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
         // 8 mh .. 8 mh + 7 and hands the others to its partner through LDS
         float keep[8];
         if constexpr (NM == 2) {
-          float* mine = ex + wave * 512 + lane;
+          float* mine = expar + wave * 512 + lane;
 #pragma unroll
           for (int q = 0; q < 8; ++q) {
             keep[q] = mh ? accx[8 + q] : accx[q];
             mine[q * 64] = mh ? accx[q] : accx[8 + q];
           }
-          LB_WAIT_LGKM(0);
+          LB_WAIT_LGKM(0);                          // (these and the go planes above are in LDS)
           __builtin_amdgcn_s_barrier();             // (bare: see the LayerNorm epilogue)
-          const uint32_t ae = lds0 + kExB + (uint32_t)((wave ^ NC) * 512 + lane) * 4u;
+          const uint32_t ae = lds0 + kExB + (uint32_t)(buf * kParFloats + (wave ^ NC) * 512 + lane) * 4u;
           float e[8] = {lds_read_f32<0>(ae), lds_read_f32<256>(ae), lds_read_f32<512>(ae), lds_read_f32<768>(ae),
                         lds_read_f32<1024>(ae), lds_read_f32<1280>(ae), lds_read_f32<1536>(ae), lds_read_f32<1792>(ae)};
           lgkm_landed<0>(e);
@@ -516,9 +584,7 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
 #pragma unroll
           for (int q = 0; q < 8; ++q) keep[q] = 0.f;          // (not instantiated: every plain shape splits the m range)
         }
-        if constexpr (EPI == LB_SHIFT) vm_landed<8 * UPT + DMA>(lse8);      // (only this iteration's loads ahead may be out)
-        else asm volatile("" : "+v"(keep[0]), "+v"(keep[1]), "+v"(keep[2]), "+v"(keep[3]), "+v"(keep[4]), "+v"(keep[5]),
-                          "+v"(keep[6]), "+v"(keep[7])::"memory");        // (the same fence for the scheduler)
+        // (lse8 has landed with the wait in front of the commit)
         float v[8], gt[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
@@ -554,27 +620,7 @@ __global__ __launch_bounds__(kLbThreads) void linear_bwd_kernel(const LbArgs p) 
         }
       }
 
-      // ---- the next stage of go into the other plane buffer; x of the next stage has to have landed ------------------
       __builtin_amdgcn_sched_barrier(0);
-      // the go registers of stage i + 1: behind them only this iteration's LDS-DMAs and stores (a ragged stage may
-      // have skipped stores: it waits for everything)
-      if (full && shift) {
-#pragma unroll
-        for (int q = 0; q < UPT; ++q) vm_landed<DMA + E_S>(gr[q]);
-      } else if (full) {
-#pragma unroll
-        for (int q = 0; q < UPT; ++q) vm_landed<DMA + (EPI == LB_SHIFT ? 8 : E_S)>(gr[q]);      // (no gt stores)
-      } else {
-#pragma unroll
-        for (int q = 0; q < UPT; ++q) vm_landed<0>(gr[q]);
-      }
-      commit_go(buf ^ 1, row_of(i + 1), i + 1 < n);
-      // x of stage i + 1 (requested one iteration ago): everything older than this iteration's own operations
-      if (full && shift) lb_wait_vm<kVmPerIter>();
-      else if (full) lb_wait_vm<kVmPerIter - (EPI == LB_SHIFT ? 8 : 0)>();
-      else lb_wait_vm<0>();
-      LB_WAIT_LGKM(0);                              // (the plane writes above)
-      __builtin_amdgcn_s_barrier();
     }
   }
   lb_wait_vm<0>();
@@ -635,13 +681,6 @@ __global__ __launch_bounds__(256) void lb_rowmax_parts_kernel(const float* __res
     if (a) pa[blockIdx.x] = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
     if (b) pb[blockIdx.x] = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
   }
-}
-
-template <int M, int K>
-constexpr int lb_lds_bytes() {
-  return 2 * (2 * 4 * (M + 4) * 16) + 3 * (kLbStage * K * 4) + (4 * M + 64) * 4 +
-         (M == 256 ? kLbWaves * 512 * 4 : kLbWaves * 64 * 4) +
-         3 * kLbWaves * 256;
 }
 
 }  // namespace mlgnn

@@ -13,7 +13,8 @@ for grp in "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VALU_MFMA_MOPS_F16" "SQ_WAVE_CYC
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_ANY" "GRBM_GUI_ACTIVE SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" \
            "SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_WAIT_INST_LDS"; do
   tag=$(echo $grp | tr ' ' '_')
-  rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/$tag -- python3 $R/tools/bench_dense.py --iters 3 > $OUT/$tag.log 2>&1 || echo "FAILED $grp"
+  # (a pass that fails or runs away ends the run: nothing more is started on a device that may have faulted)
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/$tag -- python3 $R/tools/bench_dense.py --iters 3 > $OUT/$tag.log 2>&1 || { echo "FAILED $grp"; exit 1; }
 done
 cd $R
 python3 - "$OUT" "$TAG" "$COMMIT" <<'PY'
