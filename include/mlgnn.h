@@ -1250,6 +1250,41 @@ int mlgnn_pathway_pca(const double* xt, const int32_t* cols, const int64_t* seg_
                       int64_t n_segments, int64_t max_cols, int k, void* stream);
 
 /*
+ * Pathway reordering (csrc/pathway_order.hip), fp64: the reference's dataloader/multiloader.py:512-528 -- np.corrcoef of
+ * R rows minus the identity, and the greedy chain over it -- in three launches on the caller's stream with no host step
+ * between them.
+ *   x [rows, outer, inner]: element (r, a, b) at x[r row_stride + a outer_stride + b] (strides in doubles, >= 0); the
+ *   L = outer inner values of a row are one variable's observations in the order l = a inner + b.  The scores
+ *   [N, 3 R, k] of mlgnn_pathway_pca are R rows with outer = N, inner = 3 k, row_stride = 3 k, outer_stride = 3 R k; a
+ *   plain [R, L] matrix is outer = 1.
+ *     mean_r = (sum_l x[r, l]) / L                              a fixed-order sum
+ *     c_ij   = (sum_l (x[i, l] - mean_i)(x[j, l] - mean_j)) / (L - 1)        centred first, then multiplied, on
+ *              v_mfma_f64_16x16x4_f64 over chunks of 256 columns, the chunks added in chunk order
+ *     s_i    = sqrt(c_ii)
+ *     corr [rows, rows]: corr[i, j] = corr[j, i] = clip((c_ij / s_i) / s_j, -1, 1) for i < j (one value stored twice:
+ *              the mirror is bit for bit; a NaN stays a NaN), corr[i, i] = c_ii / s_i / s_i - 1
+ *     info [1] int32: the number of rows whose c_ii is not a positive finite number
+ *     order [rows] int32: order[0], order[1] = the pair i < j with the largest corr[i, j], the first in row-major order
+ *              among equal values; then rows - 2 times the not-yet-used t with the largest corr[order[-1], t], the
+ *              highest t among equal values (a stable ascending sort read backwards).  A NaN ranks as -inf in both, so
+ *              `order` is a permutation of [0, rows) whatever x holds; with info[0] > 0 it is not what numpy gives
+ *              (NaN first in argmax and in the reversed argsort): the caller takes that case to the host.
+ *   EVERY element of corr, order and info is written, whatever they and the workspace held before.  No float atomics,
+ *   every sum in a fixed order: bitwise reproducible.
+ * Shapes (mlgnn_pathway_order_supported): 2 <= rows <= 256, outer >= 1, inner >= 1, L >= 2, rows L doubles and the
+ * workspace below 4 GiB (the entry point: also the span of x, (rows - 1) row_stride + (outer - 1) outer_stride + inner
+ * doubles, below 4 GiB).  workspace: mlgnn_pathway_order_workspace_bytes(rows, outer, inner) bytes, host arithmetic on
+ * its arguments, MLGNN_E_SHAPE for a shape outside the above; 8-byte aligned, contents on entry ignored.  MLGNN_E_NULL
+ * for a NULL operand, then MLGNN_E_SHAPE, MLGNN_E_ALIGN (x, corr, workspace: 8 bytes; order, info: 4), then
+ * MLGNN_E_WORKSPACE; all before anything is launched.  No trip count and no address depends on a value of x.
+ */
+int mlgnn_pathway_order_supported(int64_t rows, int64_t outer, int64_t inner);
+int64_t mlgnn_pathway_order_workspace_bytes(int64_t rows, int64_t outer, int64_t inner);
+int mlgnn_pathway_order(const double* x, int64_t rows, int64_t outer, int64_t inner, int64_t row_stride,
+                        int64_t outer_stride, double* corr, int32_t* order, int32_t* info, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+
+/*
  * PathwayConv's message + aggregation (csrc/pathway_conv.hip; the reference's torch_vertex.py:107-178): the second
  * message-passing step over the gene -> pathway-node membership edges, for MLGNN_AGGR_MAX and MLGNN_AGGR_SOFTMAX (add and
  * mean are two weighted sums of the existing aggregation by linearity; MLGNN_E_MODE here).  fp32, no atomics, every

@@ -142,6 +142,9 @@ SIGNATURES = {
     "mlgnn_pathway_pca_supported": (_INT, [_I64] * 4 + [_INT]),
     "mlgnn_pathway_pca_workspace_bytes": (_I64, [_I64] * 4),
     "mlgnn_pathway_pca": (_INT, [_P] * 10 + [_I64] * 6 + [_INT, _P]),
+    "mlgnn_pathway_order_supported": (_INT, [_I64] * 3),
+    "mlgnn_pathway_order_workspace_bytes": (_I64, [_I64] * 3),
+    "mlgnn_pathway_order": (_INT, [_P] + [_I64] * 5 + [_P] * 4 + [_I64, _P]),
     "mlgnn_pathway_conv_supported": (_INT, [_I64] * 3),
     "mlgnn_pathway_conv_fwd": (_INT, [_P] * 9 + [_I64] * 4 + [_INT, _F, _P, _P]),
     "mlgnn_pathway_conv_bwd_workspace_floats": (_I64, [_I64] * 4 + [_INT]),

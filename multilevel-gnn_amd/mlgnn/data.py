@@ -182,6 +182,7 @@ class SyntheticTCGA(torch.utils.data.Dataset):
         self.drop_irr_pathway = bool(drop_irr_pathway)
         self.pca_components = None                     # set by recalculate_pca_bo_selected_gene
         self._pathway_image = None                     # [n_patients, 146, 3 * pca_dim] once it has run
+        self.reorder_idxs = None                       # set under reorder_pathway (get_reorder_idxs)
 
     def __len__(self):
         return self.x.shape[0]
@@ -207,13 +208,35 @@ class SyntheticTCGA(torch.utils.data.Dataset):
         what ``generate_mutual_mask`` takes."""
         return self.raw_matrix(indexs).numpy(), self.labels[torch.as_tensor(indexs, dtype=torch.long)].numpy()
 
-    def recalculate_pca_bo_selected_gene(self, mutual_info_mask):
+    def recalculate_pca_bo_selected_gene(self, mutual_info_mask, reorder_pathway=False, selected_similarity=False):
         """``MyData.recalculate_pca_bo_selected_gene`` (multiloader.py:568-579): the per-segment PCA over the members the
         mask kept (``None``: all), fitted on the whole cohort; sets ``pca_components`` and every patient's
-        ``pathway_node_attr``."""
-        from .pca import fold_pca
-        self.pca_components, self._pathway_image = fold_pca(self.raw_matrix(), self.raw_indice, mutual_info_mask,
-                                                            self.pca_sim_dim, self.pca_dim, self.drop_irr_pathway)
+        ``pathway_node_attr``.  ``reorder_pathway`` and ``selected_similarity`` are the reference's flags of that name
+        (:512): with ``reorder_pathway and (selected_similarity or mask is None)`` the pathway order of these scores
+        (:func:`mlgnn.reorder.fold_reorder`) becomes ``reorder_idxs``; otherwise it stays what it was."""
+        from .pca import fold_pca, fold_pca_scores
+        if not (reorder_pathway and (selected_similarity or mutual_info_mask is None)):
+            self.pca_components, self._pathway_image = fold_pca(self.raw_matrix(), self.raw_indice, mutual_info_mask,
+                                                                self.pca_sim_dim, self.pca_dim, self.drop_irr_pathway)
+            return
+        from .reorder import fold_reorder
+        self.pca_components, self._pathway_image, scores = fold_pca_scores(
+            self.raw_matrix(), self.raw_indice, mutual_info_mask, self.pca_sim_dim, self.pca_dim, self.drop_irr_pathway)
+        self.reorder_idxs = fold_reorder(scores)
+
+    def prepare_reorder_idxs(self):
+        """The order the reference has from construction (``init_data``: ``prepare_pca_result`` with no mask, under
+        ``reorder_pathway``): the unmasked scores' order becomes ``reorder_idxs``.  The image and ``pca_components`` stay
+        as they are (the synthetic cohort's image is all zeros until a fold is prepared)."""
+        from .pca import fold_pca_scores
+        from .reorder import fold_reorder
+        scores = fold_pca_scores(self.raw_matrix(), self.raw_indice, None, self.pca_sim_dim, self.pca_dim,
+                                 self.drop_irr_pathway)[2]
+        self.reorder_idxs = fold_reorder(scores)
+
+    def get_reorder_idxs(self):
+        """``MyData.get_reorder_idxs`` (multiloader.py): the stored order, or ``list(range(146))`` if none was computed."""
+        return list(range(146)) if self.reorder_idxs is None else self.reorder_idxs
 
     def recalculate_edge_bo_selected_gene(self, mutual_info_mask, indice=None, edge_select=False, edge_select_threshold=1.0,
                                           n_neighbors=3, random_state=None, mutual_classif=True,

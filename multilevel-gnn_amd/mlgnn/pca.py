@@ -204,7 +204,7 @@ def _kernel_fold(raw, plan, pca_sim_dim, pca_dim, drop_irr_pathway):
         components = components[torch.from_numpy(plan.take).to(dev)][:, :pca_dim]
         if drop_irr_pathway:
             components = components * torch.from_numpy(~plan.take_small).to(dev)[:, None]
-    return components.cpu(), scores.cpu()
+    return components.cpu(), scores                              # (the scores stay on the device: fold_pca_scores)
 
 
 def fold_pca(raw, raw_indice, mask, pca_sim_dim, pca_dim, drop_irr_pathway=False, pathway_num=146):
@@ -214,8 +214,17 @@ def fold_pca(raw, raw_indice, mask, pca_sim_dim, pca_dim, drop_irr_pathway=False
 
     -> ``pca_components`` (fp64, on the host: ``[sum n_sel, pca_dim]`` with a mask, ``[G, pca_sim_dim]`` without -- what
     ``set_pca_params`` takes) and ``pathway_node_attr [P, pathway_num, 3 * pca_dim]`` (fp32, on the host) with
-    ``[p, w, o * pca_dim + j] = scores[p, 3 w + o, j]``.  ``reorder_pathway``, ``z_score``, ``lag_pca``, ``precise_order``
-    and ``mean_pca_init`` are not part of this."""
+    ``[p, w, o * pca_dim + j] = scores[p, 3 w + o, j]``.  ``z_score``, ``lag_pca``, ``precise_order`` and
+    ``mean_pca_init`` are not part of this; ``reorder_pathway`` is :func:`mlgnn.reorder.fold_reorder` on the scores that
+    :func:`fold_pca_scores` hands back."""
+    return fold_pca_scores(raw, raw_indice, mask, pca_sim_dim, pca_dim, drop_irr_pathway, pathway_num)[:2]
+
+
+def fold_pca_scores(raw, raw_indice, mask, pca_sim_dim, pca_dim, drop_irr_pathway=False, pathway_num=146):
+    """:func:`fold_pca` plus the scores it projects the image from: -> ``(pca_components, pathway_node_attr, scores)``,
+    ``scores [P, 3 * pathway_num, pca_sim_dim]`` fp64 where the leg that ran left them -- on the device after the kernel
+    (so that :func:`mlgnn.reorder.fold_reorder` reads them with no trip to the host), on the host after the
+    scikit-learn loop."""
     pca_sim_dim, pca_dim = int(pca_sim_dim), int(pca_dim)
     if not 1 <= pca_dim <= pca_sim_dim:
         raise ValueError("fold_pca: 1 <= pca_dim <= pca_sim_dim, got %d and %d" % (pca_dim, pca_sim_dim))
@@ -231,5 +240,5 @@ def fold_pca(raw, raw_indice, mask, pca_sim_dim, pca_dim, drop_irr_pathway=False
     else:
         PCA_STATS["sklearn"] += 1
         components, scores = _sklearn_fold(raw, plan, pca_sim_dim, pca_dim, drop_irr_pathway)
-    image = scores[:, :, :pca_dim].reshape(n, int(pathway_num), 3 * pca_dim).to(torch.float32)
-    return components, image
+    image = scores.cpu()[:, :, :pca_dim].reshape(n, int(pathway_num), 3 * pca_dim).to(torch.float32)
+    return components, image, scores

@@ -236,7 +236,7 @@ class MultilevelGNN(nn.Module):
                                 N_PATHWAYS * N_OMICS, match_mask=args.pca_match_mask)
             x = x.reshape(x.shape[0], x.shape[1], N_PATHWAYS, self.pca_dim * N_OMICS)
             if args.reorder_pathway and self.reorder_idxs is not None:
-                x = x[:, :, self.reorder_idxs, :]
+                x = x[:, :, self.reorder_index(x.device), :]
 
         pca_feature = x
         return self._apply_head(x, age), pca_feature
@@ -264,6 +264,16 @@ class MultilevelGNN(nn.Module):
 
     def set_reorder_idxs(self, reorder_idx):
         self.reorder_idxs = torch.tensor(reorder_idx)
+        self._reorder_on = {}
+
+    def reorder_index(self, device):
+        """``reorder_idxs`` on ``device`` for the gather, copied there once per device (indexing a device tensor with a
+        host index uploads it on every step).  The values are those ``set_reorder_idxs`` stored."""
+        cache = self.__dict__.setdefault("_reorder_on", {})
+        held = cache.get(device)
+        if held is None or held[0] is not self.reorder_idxs:         # (also after a direct assignment of reorder_idxs)
+            held = cache[device] = (self.reorder_idxs, torch.as_tensor(self.reorder_idxs).to(device))
+        return held[1]
 
     def get_feature_loss(self, pca_feature):
         """``pca_loss``: -coef * log(mean(std over batch)); ``pca_indep_loss``: mean |cos| between

@@ -216,7 +216,7 @@ class VAE(_PretrainBase):
         else:
             h = h[:, :, :keep].permute(0, 2, 1).reshape(b, keep, N_PATHWAYS, N_OMICS)
         if self.args.reorder_pathway and self.reorder_idxs is not None:
-            h = h[:, :, self.reorder_idxs, :]
+            h = h[:, :, self.reorder_index(h.device), :]
         return h
 
     def train_step(self, input_batch, require_grad=True):

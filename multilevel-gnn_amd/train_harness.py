@@ -53,7 +53,7 @@ DEFAULTS = dict(
     reduction_method="linear_projection", freeze_mutual_select_init=False, random_state=12345, remain_all_tf=False,
     pathcnn_kernel_size=3, more_conv=False, pca_sim_dim=5, drop_irr_pathway=False, mutual_classif=False,
     edge_select=False, edge_select_threshold=1.0, allow_no_edge_pretrain=False, knn_mutual_info=False, bidir_edge=False,
-    mute_edge="",
+    mute_edge="", selected_similarity=False,
 )
 
 
@@ -160,6 +160,9 @@ def run(args):
     else:
         data = SyntheticTCGA(args.patients, pca_dim=args.pca_dim, seed=args.seed, with_raw_data=(args.model == "pathcnn"),
                              pca_sim_dim=max(args.pca_sim_dim, args.pca_dim), drop_irr_pathway=args.drop_irr_pathway, **small)
+        if args.reorder_pathway:
+            # the reference's dataset computes the order of the unmasked scores when it is built (init_data)
+            data.prepare_reorder_idxs()
     n_train = int(0.7 * len(data)) // (args.batch_size * world) * (args.batch_size * world)
     idx = torch.randperm(len(data), generator=torch.Generator().manual_seed(args.seed)).tolist()
     train_idx, valid_idx = idx[:n_train][rank::world], idx[n_train:]
@@ -194,7 +197,11 @@ def run(args):
         x, y = data.get_data_by_indice(train_idx)
         mask = model.generate_mutual_mask(x, y, args.mutual_classif)[0]
         model.set_info_mask(mask.to(torch.float32))
-        data.recalculate_pca_bo_selected_gene(mask)
+        if args.reorder_pathway:                # under --selected_similarity the order follows the fold's scores
+            data.recalculate_pca_bo_selected_gene(mask, reorder_pathway=True,
+                                                  selected_similarity=args.selected_similarity)
+        else:
+            data.recalculate_pca_bo_selected_gene(mask)
         model.set_pca_params(data.pca_components.to(device), mask)
         # train.py:299: the topology narrowed to the nodes the mask kept; with --edge_select every remaining PPI edge
         # also has to pass valid_pca_mutual_info on the training patients
@@ -204,6 +211,8 @@ def run(args):
             mutual_classif=args.mutual_classif, allow_no_edge_pretrain=args.allow_no_edge_pretrain,
             knn_mutual_info=args.knn_mutual_info, bidir_edge=args.bidir_edge, mute_edge=str(args.mute_edge))
         logging.info("fold topology: %d of %d edges", edge_index.shape[1], data._base_edge_index.shape[1])
+    if args.reorder_pathway and hasattr(model, "set_reorder_idxs") and hasattr(data, "get_reorder_idxs"):
+        model.set_reorder_idxs(data.get_reorder_idxs())             # train.py:300-301
     model.to(device)
     broadcast_parameters(model)
     # train.py:112-114 (Adam + StepLR) and :63-66 (clip_grad_norm_(20) + step) as ONE fused update of the flat buffer

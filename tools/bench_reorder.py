@@ -1,0 +1,192 @@
+#!/usr/bin/env python3
+"""The pathway reordering of a fold (``reorder_pathway``: np.corrcoef of the 146 pathways' PCA scores and the greedy chain
+over it) on the ``fold_pca`` scores of ``SyntheticTCGA`` -- 25 015 members, 438 segments -- at
+
+  N = 200, 300, 470 patients;  ``pca_sim_dim`` 3 and 5;  unmasked and under the mean-threshold mask of the cohort's
+  planted signal (``mutual_info_classif`` of the members against the label, threshold at the mean).
+
+Times ``mlgnn.reorder.fold_reorder`` on the kernels of csrc/pathway_order.hip against the numpy leg in one process.  The
+kernel leg starts from the scores where the PCA kernel left them, on the device; the numpy leg starts from host scores
+and, since the PCA ran on the kernel, is also charged the download it needs (reported apart as well).  Per shape:
+
+  * one untimed call of each leg, then the two legs alternating over ``--repeats`` repeats, wall clock with a device
+    synchronise, the garbage collector held off;
+  * the three launches alone, by device events (mean of ``--iters`` calls of the entry point after ``--warmup``);
+  * that both legs give the same order.
+
+Every shape runs in a child process of its own under a time limit (``--step-timeout``); the first one that fails ends
+the run.  Results are written after every shape.  Writes profiles/pathway_order.json, whose ``ships_enabled`` is the rule
+for the default of ``MLGNN_REORDER_FUSED``: the kernel leg beats the numpy leg by more than that leg's spread at every
+shape measured.  Development tool; run it under a time limit of its own."""
+import argparse
+import gc
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
+
+PATIENTS = (200, 300, 470)
+SIMS = (3, 5)
+REPEATS = 3
+SEED = 0
+
+
+def shapes():
+    return [(n, masked, sim) for n in PATIENTS for masked in (False, True) for sim in SIMS]
+
+
+def shape_name(n, masked, sim):
+    return "N%d_%s_sim%d" % (n, "masked" if masked else "unmasked", sim)
+
+
+def wall(fn):
+    import torch
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, out
+
+
+def kernel_ms(scores, warmup, iters):
+    """The three launches of mlgnn_pathway_order alone, everything resident on the device."""
+    import torch
+    from mlgnn import _lib
+    n, segments, sim = scores.shape
+    rows = segments // 3
+    x = scores.view(n, rows, 3 * sim).permute(1, 0, 2)
+    dev = scores.device
+    corr = torch.zeros((rows, rows), dtype=torch.float64, device=dev)
+    order = torch.zeros(rows, dtype=torch.int32, device=dev)
+    info = torch.zeros(1, dtype=torch.int32, device=dev)
+    need = _lib.size("mlgnn_pathway_order_workspace_bytes", rows, n, 3 * sim)
+    work = torch.zeros(max(need, 1), dtype=torch.uint8, device=dev)
+
+    def launch():
+        _lib.call("mlgnn_pathway_order", x, rows, n, 3 * sim, x.stride(0), x.stride(1), corr, order, info, work, need,
+                  _lib.stream())
+
+    for _ in range(warmup):
+        launch()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    s.record()
+    for _ in range(iters):
+        launch()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / iters, int(info[0])
+
+
+def run_shape(n, masked, sim, repeats, warmup, iters):
+    import numpy as np
+    import torch
+    import mlgnn
+    from mlgnn import pca as P
+    from mlgnn import reorder as R
+    from mlgnn.data import SyntheticTCGA
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_reorder.py needs the GPU: there is no CPU path of the op to time")
+    data = SyntheticTCGA(n, seed=SEED)
+    raw = data.raw_matrix()
+    mask = None
+    if masked:
+        mi = mlgnn.mutual_info_classif(raw.numpy(), data.labels.numpy(), n_neighbors=3, random_state=12345)
+        mask = torch.from_numpy((mi >= mi.mean()).astype(np.float32))[:, None]
+    P.ENABLED = True
+    scores = P.fold_pca_scores(raw, data.raw_indice, mask, sim, 2)[2]
+    assert scores.is_cuda and scores.dtype == torch.float64
+    host_scores = scores.cpu()
+
+    def leg(enabled, source):
+        R.ENABLED = enabled
+        return R.fold_reorder(source)
+
+    leg(True, scores)                                              # discarded: the code object loads
+    leg(False, scores)                                             # discarded: the first download sets up its staging
+    before = dict(R.REORDER_STATS)
+    out = {"hip_ms": [], "host_ms": [], "host_with_download_ms": []}
+    orders = []
+    gc.collect()
+    gc.disable()                                                   # (as timeit does: no collection inside a timed call)
+    for _ in range(repeats):
+        ms, got = wall(lambda: leg(True, scores))
+        out["hip_ms"].append(ms)
+        ms, want = wall(lambda: leg(False, host_scores))
+        out["host_ms"].append(ms)
+        ms, want2 = wall(lambda: leg(False, scores))               # the download the host leg needs after the PCA kernel
+        out["host_with_download_ms"].append(ms)
+        orders.append((got, want, want2))
+    gc.enable()
+    assert R.REORDER_STATS == dict(hip=before["hip"] + repeats, host=before["host"] + 2 * repeats), R.REORDER_STATS
+    k_ms, degenerate = kernel_ms(scores, warmup, iters)
+    out.update(kernel_ms=k_ms, degenerate_rows=degenerate, observations_per_row=int(n * 3 * sim),
+               same_order=all(g == w == w2 for g, w, w2 in orders),
+               start_pair_upper_triangular=bool(orders[0][1][0] < orders[0][1][1]),
+               device=torch.cuda.get_device_name(0), host_threads=torch.get_num_threads())
+    return out
+
+
+def summarise(entry):
+    hip, ref = entry["hip_ms"], entry["host_with_download_ms"]
+    r = len(hip)
+    entry["summary"] = {"hip_mean_ms": sum(hip) / r, "hip_spread_ms": max(hip) - min(hip),
+                        "host_mean_ms": sum(entry["host_ms"]) / r,
+                        "host_with_download_mean_ms": sum(ref) / r, "host_with_download_spread_ms": max(ref) - min(ref),
+                        "speedup_over_host": sum(ref) / sum(hip),
+                        "beats_host_by_more_than_its_spread": sum(ref) / r - sum(hip) / r > max(ref) - min(ref)}
+    return entry
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=REPEATS)
+    ap.add_argument("--step-timeout", type=float, default=120.0, help="seconds, per shape")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pathway_order.json"))
+    ap.add_argument("--step", default=None, help="(internal) N,masked,sim: run one shape and print its JSON line")
+    a = ap.parse_args()
+    if a.step:
+        n, masked, sim = (int(v) for v in a.step.split(","))
+        print("STEP " + json.dumps(run_shape(n, bool(masked), sim, a.repeats, a.warmup, a.iters)), flush=True)
+        return
+    import numpy as np
+    result = {"workload": "fold_reorder (np.corrcoef of the 146 pathways' PCA scores minus I and the greedy chain, fp64) on "
+                          "the fold_pca scores of SyntheticTCGA: the kernels of csrc/pathway_order.hip from device scores "
+                          "against the numpy leg (MLGNN_REORDER_FUSED=0) from host scores plus the download",
+              "timing": "wall clock around each call with a device synchronise, the legs alternating over %d repeats, one "
+                        "untimed call of each leg first, no garbage collection inside; every shape a fresh process under a limit of %g s; the three "
+                        "launches alone by device events, mean of %d calls after %d"
+                        % (a.repeats, a.step_timeout, a.iters, a.warmup),
+              "versions": {"numpy": np.__version__}, "shapes": []}
+    for n, masked, sim in shapes():
+        entry = {"shape": shape_name(n, masked, sim), "N": n, "masked": masked, "pca_sim_dim": sim}
+        cmd = [sys.executable, os.path.abspath(__file__), "--step", "%d,%d,%d" % (n, int(masked), sim),
+               "--warmup", str(a.warmup), "--iters", str(a.iters), "--repeats", str(a.repeats)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=a.step_timeout)
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("STEP ")]
+        if out.returncode != 0 or len(lines) != 1:
+            sys.stderr.write(out.stdout + out.stderr)
+            raise SystemExit("shape %s failed with status %d: nothing more is started" % (entry["shape"], out.returncode))
+        step = json.loads(lines[0][5:])
+        for key in ("device", "host_threads"):
+            result[key] = step.pop(key)
+        entry.update(step)
+        result["shapes"].append(summarise(entry))
+        print(json.dumps(entry), flush=True)
+        result["ships_enabled"] = len(result["shapes"]) == len(shapes()) and all(
+            e["summary"]["beats_host_by_more_than_its_spread"] and (e["same_order"] or not e["start_pair_upper_triangular"])
+            for e in result["shapes"])                            # (numpy starting [j, i], j > i: DESIGN section 7)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            json.dump(result, fh, indent=1)
+            fh.write("\n")
+
+
+if __name__ == "__main__":
+    main()
