@@ -17,13 +17,14 @@
 //
 // Every sum in the fixed order of block_sums.h, each with LDS scratch of its own (one barrier each).  No fused
 // multiply-add: contraction is off inside the function, whatever the including file says (a product and the sum that takes
-// it round separately, as in the numpy restatement of the tests).  Node indices are clamped to [0, n_nodes), so a wrong
-// value cannot read outside xt.  Barriers: 2 in pair mode (means, centred sums) + 3 (mean, deviation, mean magnitude).
+// it round separately, as in the numpy restatement of the tests).  Node indices are clamped to [0, n_nodes) (pair_list.h),
+// so a wrong value cannot read outside xt.  Barriers: 2 in pair mode (means, centred sums) + 3 (mean, deviation, mean magnitude).
 #pragma once
 #include <math.h>
 
 #include "block_sums.h"
 #include "common.h"
+#include "pair_list.h"
 
 namespace mlgnn {
 
@@ -40,12 +41,8 @@ __device__ __forceinline__ double edge_prepare_column(const double* __restrict__
 #pragma clang fp contract(off)
   const int tid = threadIdx.x;
   const double n_d = (double)N;
-  int s = pairs[2 * pair], t = pairs[2 * pair + 1];
-  const bool single = t < 0;                                            // uniform over the workgroup
-  s = min(max(s, 0), n_nodes - 1);
-  t = single ? s : min(t, n_nodes - 1);
-  const double* xs = xt + (size_t)s * N;
-  const double* xq = xt + (size_t)t * N;
+  const double *xs, *xq;
+  const bool single = pair_rows(xt, pairs, pair, N, n_nodes, xs, xq);   // uniform over the workgroup
 
   // steps 1-3: key[i] = score_i
   if (single) {

@@ -27,6 +27,7 @@
 #include "launch.h"
 #include "mlgnn.h"
 #include "mutual_info_cd.h"
+#include "pair_list.h"
 
 #pragma clang fp contract(off)
 
@@ -35,10 +36,7 @@ namespace {
 
 bool shape_ok(int64_t n, int64_t n_nodes, int64_t P, int64_t k, int64_t n_labels, bool with_score) {
   if (n < 2 || n > kMiMaxSamples || k < 1 || n_labels < 1 || n_labels > n) return false;
-  const int64_t most = (((int64_t)1 << 29) - 1) / n;                    // rows of N doubles below 4 GiB
-  if (n_nodes < 0 || n_nodes > most || P < 0 || P >= ((int64_t)1 << 31)) return false;
-  if (P > 0 && n_nodes < 1) return false;
-  return !with_score || P <= most;
+  return pair_list_shape_ok(n, n_nodes, P, with_score);
 }
 
 __global__ __launch_bounds__(kBlock) void edge_mi_kernel(const double* __restrict__ xt, const int32_t* __restrict__ pairs,

@@ -36,6 +36,7 @@
 #include "common.h"
 #include "launch.h"
 #include "mlgnn.h"
+#include "pair_list.h"
 
 #pragma clang fp contract(off)
 
@@ -47,10 +48,7 @@ constexpr int kKsgMaxNeighbors = MLGNN_KRASKOV_MAX_NEIGHBORS;
 
 bool ksg_shape_ok(int64_t n, int64_t n_nodes, int64_t P, int64_t k, bool with_details) {
   if (k < 1 || k > kKsgMaxNeighbors || n < k + 1 || n > kKsgMaxSamples) return false;
-  const int64_t most = (((int64_t)1 << 29) - 1) / n;                    // rows of N doubles below 4 GiB
-  if (n_nodes < 0 || n_nodes > most || P < 0 || P >= ((int64_t)1 << 31)) return false;
-  if (P > 0 && n_nodes < 1) return false;
-  return !with_details || P <= most;
+  return pair_list_shape_ok(n, n_nodes, P, with_details);
 }
 
 __device__ __forceinline__ double larger(double a, double b) { return a > b ? a : b; }
@@ -116,12 +114,8 @@ __global__ __launch_bounds__(kBlock) void kraskov_mi_kernel(const double* __rest
   double* ys = lds + 2 * N;                                             // [N] the label
   const int tid = threadIdx.x;
   const size_t pair = blockIdx.x;
-  int s = pairs[2 * pair], t = pairs[2 * pair + 1];
-  const bool single = t < 0;                                            // uniform over the workgroup
-  s = min(max(s, 0), n_nodes - 1);
-  t = single ? s : min(t, n_nodes - 1);
-  const double* gs = xt + (size_t)s * N;
-  const double* gq = xt + (size_t)t * N;
+  const double *gs, *gq;
+  const bool single = pair_rows(xt, pairs, pair, N, n_nodes, gs, gq);   // uniform over the workgroup
   for (int i = tid; i < N; i += kBlock) {
     xs[i] = gs[i];
     if (!single) xq[i] = gq[i];

@@ -22,7 +22,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _pairs
 from .mutual_info import MAX_SAMPLES, tree_path
 
 # MLGNN_EDGE_SELECT_FUSED=0: edge_select always runs the loop of scikit-learn calls (same-box A/B runs).  The default
@@ -36,14 +36,9 @@ ENABLED = os.environ.get("MLGNN_EDGE_SELECT_FUSED", "1" if DEFAULT_ENABLED else 
 EDGE_SELECT_STATS = {"hip": 0, "sklearn": 0}
 
 
-def _host(v):
-    return v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
-
-
 def _labels(y):
-    y = _host(y).reshape(-1)
-    _, dense, counts = np.unique(y, return_inverse=True, return_counts=True)
-    return y, dense, counts
+    _, dense, counts = np.unique(_pairs.host(y).reshape(-1), return_inverse=True, return_counts=True)
+    return dense, counts
 
 
 def edge_select_supported(n, n_nodes, n_pairs, n_neighbors, counts_per_label, mutual_classif=True, return_scores=False):
@@ -60,18 +55,6 @@ def edge_select_supported(n, n_nodes, n_pairs, n_neighbors, counts_per_label, mu
     return bool(_lib.lib.mlgnn_edge_mi_supported(int(n), int(n_nodes), int(n_pairs), k, len(counts), int(return_scores)))
 
 
-def _check_pairs(pairs, n_nodes):
-    p = _host(pairs)
-    if p.size == 0:
-        p = p.reshape(0, 2)
-    if p.ndim != 2 or p.shape[1] != 2:
-        raise ValueError("pair_mutual_info: pairs must be [P, 2], got %s" % (p.shape,))
-    p = np.ascontiguousarray(p, dtype=np.int64)
-    if p.shape[0] and (p[:, 0].min() < 0 or p[:, 0].max() >= n_nodes or p[:, 1].min() < -1 or p[:, 1].max() >= n_nodes):
-        raise ValueError("pair_mutual_info: node indices outside [0, %d) (-1 in column 1: a single column)" % n_nodes)
-    return p
-
-
 def pair_mutual_info(values, y, pairs, n_neighbors=3, random_state=None, return_scores=False, return_counts=False):
     """``mutual_info_classif(PCA(n_components=1).fit_transform(values[:, [s, t]]), y, n_neighbors=..., random_state=...)``
     for every row ``(s, t)`` of ``pairs [P, 2]``, and ``mutual_info_classif(values[:, [s]], y, ...)`` for a row
@@ -81,48 +64,26 @@ def pair_mutual_info(values, y, pairs, n_neighbors=3, random_state=None, return_
     ``return_scores``: also the prepared columns ``[P, n]`` as handed to the estimator; ``return_counts``: also ``m_i``
     as int32 ``[P, n]`` in sample order.  The values are scikit-learn's where :func:`edge_select_supported` holds; the
     caller checks that first."""
-    from scipy.special import digamma
-    from sklearn.utils import check_random_state
-    x = values if torch.is_tensor(values) else torch.from_numpy(np.asarray(values))
-    if x.dim() != 2 or x.dtype not in (torch.float32, torch.float64):
-        raise ValueError("pair_mutual_info: values must be [n, n_nodes] fp32 or fp64, got %s %s" % (tuple(x.shape), x.dtype))
-    n, n_nodes = int(x.shape[0]), int(x.shape[1])
-    y, dense, count = _labels(y)
-    if y.shape != (n,):
-        raise ValueError("pair_mutual_info: y has %d entries for %d samples" % (y.size, n))
-    p = _check_pairs(pairs, n_nodes)
-    n_pairs, k = int(p.shape[0]), int(n_neighbors)
-    noise = check_random_state(random_state).standard_normal(n)       # (drawn whatever P is: the generator moves as it would)
-    if count.min() < 2:
-        raise ValueError("pair_mutual_info: a label occurs once (scikit-learn drops such samples after its preparation; "
-                         "the kernel does not imitate that)")
-    if not _lib.lib.mlgnn_edge_mi_supported(n, n_nodes, n_pairs, k if -(1 << 31) <= k < 1 << 31 else 0, len(count),
-                                            int(return_scores)):
-        raise ValueError("pair_mutual_info: unsupported shape (%d samples, %d nodes, %d pairs, k = %d; 2 <= n <= %d, "
-                         "k >= 1, below 4 GiB)" % (n, n_nodes, n_pairs, k, MAX_SAMPLES))
-    if not torch.cuda.is_available():
-        raise RuntimeError("mlgnn.edge_select.pair_mutual_info has no CPU path (the kernel is HIP only)")
-    dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    mi = torch.zeros(n_pairs, dtype=torch.float64, device=dev)
-    score = torch.zeros((n_pairs, n), dtype=torch.float64, device=dev) if return_scores else None
-    counts = torch.zeros((n_pairs, n), dtype=torch.int32, device=dev) if return_counts else None
-    if n_pairs:
+    k = int(n_neighbors)
+
+    def prepare(y, n, n_nodes, n_pairs):
+        from scipy.special import digamma
+        from sklearn.utils import check_random_state
+        dense, count = _labels(y)
+        noise = check_random_state(random_state).standard_normal(n)
+        if count.min() < 2:
+            raise ValueError("pair_mutual_info: a label occurs once (scikit-learn drops such samples after its "
+                             "preparation; the kernel does not imitate that)")
+        if not _lib.lib.mlgnn_edge_mi_supported(n, n_nodes, n_pairs, k if -(1 << 31) <= k < 1 << 31 else 0, len(count),
+                                                int(return_scores)):
+            raise ValueError("pair_mutual_info: unsupported shape (%d samples, %d nodes, %d pairs, k = %d; 2 <= n <= %d, "
+                             "k >= 1, below 4 GiB)" % (n, n_nodes, n_pairs, k, MAX_SAMPLES))
         count_i = count[dense]
-        k_i = np.minimum(k, count_i - 1)
-        base = float(digamma(n) + np.mean(digamma(k_i)) - np.mean(digamma(count_i)))
-        psi = np.zeros(n + 1, dtype=np.float64)
-        psi[1:] = digamma(np.arange(1, n + 1))
-        xt = x.detach().to(dev).to(torch.float64).t().contiguous()    # [n_nodes, n]: upcast and transpose on the device
-        with torch.cuda.device(dev):
-            _lib.call("mlgnn_edge_mi", xt, torch.from_numpy(p.astype(np.int32)).to(dev), torch.from_numpy(noise).to(dev),
-                      torch.from_numpy(dense.astype(np.int32)).to(dev), torch.from_numpy(psi).to(dev), base, mi, score,
-                      counts, n, n_nodes, n_pairs, k, len(count), _lib.stream())
-    out = (mi.cpu().numpy(),)
-    if return_scores:
-        out += (score.cpu().numpy(),)
-    if return_counts:
-        out += (counts.cpu().numpy(),)
-    return out if len(out) > 1 else out[0]
+        base = digamma(n) + np.mean(digamma(np.minimum(k, count_i - 1))) - np.mean(digamma(count_i))
+        return (noise, dense.astype(np.int32)), base, (len(count),)
+
+    return _pairs.pair_op("mlgnn.edge_select.pair_mutual_info", "mlgnn_edge_mi", values, y, None, pairs, prepare,
+                          (torch.float64 if return_scores else None, torch.int32 if return_counts else None), k)
 
 
 def sklearn_edge_select(values, y, edge_index, threshold=1.0, n_neighbors=3, random_state=None, mutual_classif=True,
@@ -133,9 +94,9 @@ def sklearn_edge_select(values, y, edge_index, threshold=1.0, n_neighbors=3, ran
     reference's.  (``n_neighbors`` is the reference's default of 3 there.)"""
     from sklearn.decomposition import PCA
     from sklearn.feature_selection import mutual_info_classif, mutual_info_regression
-    x = _host(values).astype(np.float64, copy=False)
-    y = _host(y).reshape(-1)
-    ei = _host(edge_index).reshape(2, -1)
+    x = _pairs.host(values).astype(np.float64, copy=False)
+    y = _pairs.host(y).reshape(-1)
+    ei = _pairs.host(edge_index).reshape(2, -1)
     keep = np.zeros(ei.shape[1], dtype=bool)
     mi_pair = np.zeros(ei.shape[1], dtype=np.float64)
     mi_node = {}
@@ -161,10 +122,8 @@ def sklearn_edge_select(values, y, edge_index, threshold=1.0, n_neighbors=3, ran
 def use_kernel(n, n_nodes, n_edges, n_neighbors, counts_per_label, mutual_classif):
     """:func:`edge_select`'s dispatch rule: the kernel when ``MLGNN_EDGE_SELECT_FUSED`` is on, a GPU is present and
     :func:`edge_select_supported` holds for the ``E`` pairs and at most ``min(2 E, n_nodes)`` singles of the launch."""
-    if not (ENABLED and torch.cuda.is_available()):
-        return False
-    return edge_select_supported(n, n_nodes, n_edges + min(2 * n_edges, n_nodes), n_neighbors, counts_per_label,
-                                 mutual_classif)
+    return bool(ENABLED and torch.cuda.is_available()) and edge_select_supported(
+        n, n_nodes, _pairs.kernel_budget(n_edges, n_nodes), n_neighbors, counts_per_label, mutual_classif)
 
 
 def edge_select(values, y, edge_index, threshold=1.0, n_neighbors=3, random_state=None, mutual_classif=True,
@@ -178,24 +137,10 @@ def edge_select(values, y, edge_index, threshold=1.0, n_neighbors=3, random_stat
     if knn_mutual_info:
         raise NotImplementedError("knn_mutual_info (the reference's kraskov_mi) is not served by edge_select: call "
                                   "mlgnn.kraskov.edge_select_knn for the edges whose omics is not 1")
-    ei = _host(edge_index)
-    if ei.ndim != 2 or ei.shape[0] != 2:
-        raise ValueError("edge_select: edge_index must be [2, E], got %s" % (ei.shape,))
-    ei = ei.astype(np.int64)
-    if getattr(values, "ndim", 0) != 2:
-        raise ValueError("edge_select: values must be [n, n_nodes]")
-    n, n_nodes, n_edges = int(values.shape[0]), int(values.shape[1]), int(ei.shape[1])
-    if n_edges and (ei.min() < 0 or ei.max() >= n_nodes):
-        raise ValueError("edge_select: node indices outside [0, %d)" % n_nodes)
-    counts = _labels(y)[2]
-    if use_kernel(n, n_nodes, n_edges, n_neighbors, counts, mutual_classif):
+    ei, n, n_nodes, n_edges = _pairs.check_edges(values, edge_index, "edge_select")
+    if use_kernel(n, n_nodes, n_edges, n_neighbors, _labels(y)[1], mutual_classif):
         EDGE_SELECT_STATS["hip"] += 1
-        nodes = np.unique(ei)
-        singles = np.stack([nodes, np.full_like(nodes, -1)], axis=1)
-        mi = pair_mutual_info(values, y, np.concatenate([ei.T, singles], axis=0), n_neighbors, random_state)
-        mi_pair, single = mi[:n_edges], mi[n_edges:]
-        at = np.searchsorted(nodes, ei)
-        keep = mi_pair > threshold * np.maximum(single[at[0]], single[at[1]])
-        return keep, mi_pair, {int(v): float(m) for v, m in zip(nodes, single)}
+        nodes, pairs = _pairs.launch_list(ei)
+        return _pairs.decide(pair_mutual_info(values, y, pairs, n_neighbors, random_state), nodes, ei, threshold)
     EDGE_SELECT_STATS["sklearn"] += 1
     return sklearn_edge_select(values, y, ei, threshold, n_neighbors, random_state, mutual_classif)

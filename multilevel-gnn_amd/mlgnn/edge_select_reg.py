@@ -29,8 +29,8 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
-from .edge_select import _check_pairs, _host, sklearn_edge_select
+from . import _lib, _pairs
+from .edge_select import sklearn_edge_select
 from .mutual_info import MAX_NEIGHBORS_CC, MAX_SAMPLES
 
 # MLGNN_EDGE_REG_FUSED=0: edge_select_regression always runs the loop of scikit-learn calls (same-box A/B runs).  The
@@ -76,52 +76,27 @@ def pair_mutual_info_regression(values, y, pairs, n_neighbors=3, random_state=No
     real column.  The noise is drawn on the host (:func:`prepare_target`), the same for every pair.  ``return_scores``:
     also the prepared columns ``[P, n]`` as handed to the estimator; ``return_counts``: also ``nx_i`` and ``ny_i`` as
     int32 ``[P, n]`` in sample order.  The caller checks :func:`edge_select_regression_supported` first."""
-    from scipy.special import digamma
-    x = values if torch.is_tensor(values) else torch.from_numpy(np.asarray(values))
-    if x.dim() != 2 or x.dtype not in (torch.float32, torch.float64):
-        raise ValueError("pair_mutual_info_regression: values must be [n, n_nodes] fp32 or fp64, got %s %s"
-                         % (tuple(x.shape), x.dtype))
-    n, n_nodes = int(x.shape[0]), int(x.shape[1])
-    target = np.ascontiguousarray(_host(y).reshape(-1), dtype=np.float64)
-    if target.shape != (n,):
-        raise ValueError("pair_mutual_info_regression: y has %d entries for %d samples" % (target.size, n))
-    p = _check_pairs(pairs, n_nodes)
-    n_pairs, k = int(p.shape[0]), int(n_neighbors)
-    noise_x, y_prepared = prepare_target(target, random_state)    # (drawn whatever P is: the generator moves as it would)
-    if not edge_select_regression_supported(n, n_nodes, n_pairs, k, return_scores):
-        raise ValueError("pair_mutual_info_regression: unsupported shape (%d samples, %d nodes, %d pairs, k = %d; "
-                         "2 <= n <= %d, 1 <= k <= min(n - 1, %d), below 4 GiB)"
-                         % (n, n_nodes, n_pairs, k, MAX_SAMPLES, MAX_NEIGHBORS_CC))
-    if not torch.cuda.is_available():
-        raise RuntimeError("mlgnn.edge_select_reg.pair_mutual_info_regression has no CPU path (the kernel is HIP only)")
-    dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    mi = torch.zeros(n_pairs, dtype=torch.float64, device=dev)
-    score = torch.zeros((n_pairs, n), dtype=torch.float64, device=dev) if return_scores else None
-    nx = torch.zeros((n_pairs, n), dtype=torch.int32, device=dev) if return_counts else None
-    ny = torch.zeros((n_pairs, n), dtype=torch.int32, device=dev) if return_counts else None
-    if n_pairs:
-        base = float(digamma(n) + digamma(k))
-        psi = np.zeros(n + 1, dtype=np.float64)
-        psi[1:] = digamma(np.arange(1, n + 1))
-        xt = x.detach().to(dev).to(torch.float64).t().contiguous()    # [n_nodes, n]: upcast and transpose on the device
-        with torch.cuda.device(dev):
-            _lib.call("mlgnn_edge_mi_cc", xt, torch.from_numpy(p.astype(np.int32)).to(dev),
-                      torch.from_numpy(noise_x).to(dev), torch.from_numpy(y_prepared).to(dev),
-                      torch.from_numpy(psi).to(dev), base, mi, score, nx, ny, n, n_nodes, n_pairs, k, _lib.stream())
-    out = (mi.cpu().numpy(),)
-    if return_scores:
-        out += (score.cpu().numpy(),)
-    if return_counts:
-        out += (nx.cpu().numpy(), ny.cpu().numpy())
-    return out if len(out) > 1 else out[0]
+    k = int(n_neighbors)
+
+    def prepare(target, n, n_nodes, n_pairs):
+        from scipy.special import digamma
+        noise_x, y_prepared = prepare_target(target, random_state)
+        if not edge_select_regression_supported(n, n_nodes, n_pairs, k, return_scores):
+            raise ValueError("pair_mutual_info_regression: unsupported shape (%d samples, %d nodes, %d pairs, k = %d; "
+                             "2 <= n <= %d, 1 <= k <= min(n - 1, %d), below 4 GiB)"
+                             % (n, n_nodes, n_pairs, k, MAX_SAMPLES, MAX_NEIGHBORS_CC))
+        return (noise_x, y_prepared), digamma(n) + digamma(k), ()
+
+    counts = torch.int32 if return_counts else None
+    return _pairs.pair_op("mlgnn.edge_select_reg.pair_mutual_info_regression", "mlgnn_edge_mi_cc", values, y, np.float64,
+                          pairs, prepare, (torch.float64 if return_scores else None, counts, counts), k)
 
 
 def use_kernel(n, n_nodes, n_edges, n_neighbors):
     """:func:`edge_select_regression`'s dispatch rule: the kernel when ``MLGNN_EDGE_REG_FUSED`` is on, a GPU is present
     and :func:`edge_select_regression_supported` holds for the ``E`` pairs and at most ``min(2 E, n_nodes)`` singles."""
-    if not (ENABLED and torch.cuda.is_available()):
-        return False
-    return edge_select_regression_supported(n, n_nodes, n_edges + min(2 * n_edges, n_nodes), n_neighbors)
+    return bool(ENABLED and torch.cuda.is_available()) and edge_select_regression_supported(
+        n, n_nodes, _pairs.kernel_budget(n_edges, n_nodes), n_neighbors)
 
 
 def _one_launch(random_state, pair_random_state):
@@ -139,28 +114,16 @@ def edge_select_regression(values, y, edge_index, threshold=1.0, n_neighbors=3, 
     end nodes when both states are the same integer, otherwise two launches (pairs, then singles); a launch whose state
     is ``None`` draws one unseeded noise pair where the reference draws one per scikit-learn call.  Otherwise the loop
     of scikit-learn calls runs.  ``EDGE_SELECT_REG_STATS`` counts the leg."""
-    ei = _host(edge_index)
-    if ei.ndim != 2 or ei.shape[0] != 2:
-        raise ValueError("edge_select_regression: edge_index must be [2, E], got %s" % (ei.shape,))
-    ei = ei.astype(np.int64)
-    if getattr(values, "ndim", 0) != 2:
-        raise ValueError("edge_select_regression: values must be [n, n_nodes]")
-    n, n_nodes, n_edges = int(values.shape[0]), int(values.shape[1]), int(ei.shape[1])
-    if n_edges and (ei.min() < 0 or ei.max() >= n_nodes):
-        raise ValueError("edge_select_regression: node indices outside [0, %d)" % n_nodes)
+    ei, n, n_nodes, n_edges = _pairs.check_edges(values, edge_index, "edge_select_regression")
     if not use_kernel(n, n_nodes, n_edges, n_neighbors):
         EDGE_SELECT_REG_STATS["sklearn"] += 1
         return sklearn_edge_select(values, y, ei, threshold, n_neighbors, random_state, mutual_classif=False,
                                    pair_random_state=pair_random_state)
     EDGE_SELECT_REG_STATS["hip"] += 1
-    nodes = np.unique(ei)
-    singles = np.stack([nodes, np.full_like(nodes, -1)], axis=1)
+    nodes, pairs = _pairs.launch_list(ei)
     if _one_launch(random_state, pair_random_state):
-        mi = pair_mutual_info_regression(values, y, np.concatenate([ei.T, singles], axis=0), n_neighbors, random_state)
-        mi_pair, single = mi[:n_edges], mi[n_edges:]
+        mi = pair_mutual_info_regression(values, y, pairs, n_neighbors, random_state)
     else:
-        mi_pair = pair_mutual_info_regression(values, y, ei.T, n_neighbors, pair_random_state)
-        single = pair_mutual_info_regression(values, y, singles, n_neighbors, random_state)
-    at = np.searchsorted(nodes, ei)
-    keep = mi_pair > threshold * np.maximum(single[at[0]], single[at[1]])
-    return keep, mi_pair, {int(v): float(m) for v, m in zip(nodes, single)}
+        mi = np.concatenate([pair_mutual_info_regression(values, y, pairs[:n_edges], n_neighbors, pair_random_state),
+                             pair_mutual_info_regression(values, y, pairs[n_edges:], n_neighbors, random_state)])
+    return _pairs.decide(mi, nodes, ei, threshold)

@@ -23,7 +23,7 @@ from math import log
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _pairs
 from .mutual_info import MAX_SAMPLES
 
 MAX_NEIGHBORS = 16          # MLGNN_KRASKOV_MAX_NEIGHBORS of include/mlgnn.h (tests/test_kraskov_abi.py compares)
@@ -36,22 +36,6 @@ ENABLED = os.environ.get("MLGNN_EDGE_KNN_FUSED", "1" if DEFAULT_ENABLED else "0"
 
 # which leg edge_select_knn took.  A plain dict, not registered with _lib.stats, as for edge_select.EDGE_SELECT_STATS.
 EDGE_KNN_STATS = {"hip": 0, "host": 0}
-
-
-def _host(v):
-    return v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
-
-
-def _check_pairs(pairs, n_nodes):
-    p = _host(pairs)
-    if p.size == 0:
-        p = p.reshape(0, 2)
-    if p.ndim != 2 or p.shape[1] != 2:
-        raise ValueError("kraskov_mi: pairs must be [P, 2], got %s" % (p.shape,))
-    p = np.ascontiguousarray(p, dtype=np.int64)
-    if p.shape[0] and (p[:, 0].min() < 0 or p[:, 0].max() >= n_nodes or p[:, 1].min() < -1 or p[:, 1].max() >= n_nodes):
-        raise ValueError("kraskov_mi: node indices outside [0, %d) (-1 in column 1: a single column)" % n_nodes)
-    return p
 
 
 def kraskov_mi_supported(n, n_nodes, n_pairs, k=5, return_details=False):
@@ -70,37 +54,18 @@ def kraskov_mi(values, y, pairs, k=5, return_details=False):
     upcast of fp32 is exact, so every form of the same values gives the same bits); ``y [n]``: any real column.
     ``return_details``: also ``kd [P, n]`` fp64 (the distance to the ``k + 1``-th nearest joint sample, self included),
     ``nx [P, n]`` and ``ny [P, n]`` int32 (the marginal counts inside ``kd - 1e-15``, self included)."""
-    from scipy.special import digamma
-    x = values if torch.is_tensor(values) else torch.from_numpy(np.asarray(values))
-    if x.dim() != 2 or x.dtype not in (torch.float32, torch.float64):
-        raise ValueError("kraskov_mi: values must be [n, n_nodes] fp32 or fp64, got %s %s" % (tuple(x.shape), x.dtype))
-    n, n_nodes = int(x.shape[0]), int(x.shape[1])
-    label = np.ascontiguousarray(_host(y).reshape(-1), dtype=np.float64)
-    if label.shape != (n,):
-        raise ValueError("kraskov_mi: y has %d entries for %d samples" % (label.size, n))
-    p = _check_pairs(pairs, n_nodes)
-    n_pairs, k = int(p.shape[0]), int(k)
-    if not kraskov_mi_supported(n, n_nodes, n_pairs, k, return_details):
-        raise ValueError("kraskov_mi: unsupported shape (%d samples, %d nodes, %d pairs, k = %d; 1 <= k <= %d, "
-                         "k + 1 <= n <= %d, below 4 GiB)" % (n, n_nodes, n_pairs, k, MAX_NEIGHBORS, MAX_SAMPLES))
-    if not torch.cuda.is_available():
-        raise RuntimeError("mlgnn.kraskov.kraskov_mi has no CPU path (the kernel is HIP only); see kraskov_mi_host")
-    dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    mi = torch.zeros(n_pairs, dtype=torch.float64, device=dev)
-    kd = torch.zeros((n_pairs, n), dtype=torch.float64, device=dev) if return_details else None
-    nx = torch.zeros((n_pairs, n), dtype=torch.int32, device=dev) if return_details else None
-    ny = torch.zeros((n_pairs, n), dtype=torch.int32, device=dev) if return_details else None
-    if n_pairs:
-        base = float(digamma(k) + digamma(n))
-        psi = np.zeros(n + 1, dtype=np.float64)
-        psi[1:] = digamma(np.arange(1, n + 1))
-        xt = x.detach().to(dev).to(torch.float64).t().contiguous()    # [n_nodes, n]: upcast and transpose on the device
-        with torch.cuda.device(dev):
-            _lib.call("mlgnn_kraskov_mi", xt, torch.from_numpy(p.astype(np.int32)).to(dev), torch.from_numpy(label).to(dev),
-                      torch.from_numpy(psi).to(dev), base, mi, kd, nx, ny, n, n_nodes, n_pairs, k, _lib.stream())
-    if return_details:
-        return mi.cpu().numpy(), kd.cpu().numpy(), nx.cpu().numpy(), ny.cpu().numpy()
-    return mi.cpu().numpy()
+    k = int(k)
+
+    def prepare(label, n, n_nodes, n_pairs):
+        from scipy.special import digamma
+        if not kraskov_mi_supported(n, n_nodes, n_pairs, k, return_details):
+            raise ValueError("kraskov_mi: unsupported shape (%d samples, %d nodes, %d pairs, k = %d; 1 <= k <= %d, "
+                             "k + 1 <= n <= %d, below 4 GiB)" % (n, n_nodes, n_pairs, k, MAX_NEIGHBORS, MAX_SAMPLES))
+        return (label,), digamma(k) + digamma(n), ()
+
+    details = (torch.float64, torch.int32, torch.int32) if return_details else (None, None, None)
+    return _pairs.pair_op("mlgnn.kraskov.kraskov_mi", "mlgnn_kraskov_mi", values, y, np.float64, pairs, prepare, details, k,
+                          see="; see kraskov_mi_host")
 
 
 def _ksg_on_trees(cols, label, k):
@@ -138,13 +103,13 @@ def kraskov_mi_host(values, y, pairs, k=5):
     y), the ``k + 1`` query with ``p=inf``, ``query_ball_point`` at ``kd - 1e-15``, the three terms with their log parts
     (as means over the samples, where the reference adds sample by sample: another order of the same fp64 terms).
     Raises ``ValueError`` where some ``kd`` is 0, and for ``k > n - 1`` (the reference's assertion)."""
-    x = _host(values).astype(np.float64, copy=False)
+    x = _pairs.host(values).astype(np.float64, copy=False)
     if x.ndim != 2:
         raise ValueError("kraskov_mi_host: values must be [n, n_nodes]")
-    label = np.ascontiguousarray(_host(y).reshape(-1), dtype=np.float64)[:, None]
+    label = np.ascontiguousarray(_pairs.host(y).reshape(-1), dtype=np.float64)[:, None]
     if label.shape[0] != x.shape[0]:
         raise ValueError("kraskov_mi_host: y has %d entries for %d samples" % (label.shape[0], x.shape[0]))
-    p = _check_pairs(pairs, x.shape[1])
+    p = _pairs.check_pairs(pairs, x.shape[1], "kraskov_mi")
     k = int(k)
     if not 1 <= k <= x.shape[0] - 1:
         raise ValueError("kraskov_mi_host: k = %d needs 1 <= k <= n - 1 = %d" % (k, x.shape[0] - 1))
@@ -157,9 +122,8 @@ def kraskov_mi_host(values, y, pairs, k=5):
 def use_kernel(n, n_nodes, n_edges, k):
     """:func:`edge_select_knn`'s dispatch rule: the kernel when ``MLGNN_EDGE_KNN_FUSED`` is on, a GPU is present and
     :func:`kraskov_mi_supported` holds for the ``E`` pairs and at most ``min(2 E, n_nodes)`` singles of the launch."""
-    if not (ENABLED and torch.cuda.is_available()):
-        return False
-    return kraskov_mi_supported(n, n_nodes, n_edges + min(2 * n_edges, n_nodes), k)
+    return bool(ENABLED and torch.cuda.is_available()) and kraskov_mi_supported(
+        n, n_nodes, _pairs.kernel_budget(n_edges, n_nodes), k)
 
 
 def edge_select_knn(values, y, edge_index, threshold=1.0, k=5):
@@ -169,17 +133,8 @@ def edge_select_knn(values, y, edge_index, threshold=1.0, k=5):
     max(mi_node[src], mi_node[dst])``, decided on the host in fp64.  On the kernel ONE launch covers the ``E`` pairs and
     the ``U`` distinct end nodes; otherwise :func:`kraskov_mi_host` runs on the same list.  ``ValueError`` where a pair
     or an end node has ``k + 1`` coinciding samples.  ``EDGE_KNN_STATS`` counts the leg."""
-    ei = _host(edge_index)
-    if ei.ndim != 2 or ei.shape[0] != 2:
-        raise ValueError("edge_select_knn: edge_index must be [2, E], got %s" % (ei.shape,))
-    ei = ei.astype(np.int64)
-    if getattr(values, "ndim", 0) != 2:
-        raise ValueError("edge_select_knn: values must be [n, n_nodes]")
-    n, n_nodes, n_edges = int(values.shape[0]), int(values.shape[1]), int(ei.shape[1])
-    if n_edges and (ei.min() < 0 or ei.max() >= n_nodes):
-        raise ValueError("edge_select_knn: node indices outside [0, %d)" % n_nodes)
-    nodes = np.unique(ei)
-    pairs = np.concatenate([ei.T, np.stack([nodes, np.full_like(nodes, -1)], axis=1)], axis=0)
+    ei, n, n_nodes, n_edges = _pairs.check_edges(values, edge_index, "edge_select_knn")
+    nodes, pairs = _pairs.launch_list(ei)
     if use_kernel(n, n_nodes, n_edges, k):
         EDGE_KNN_STATS["hip"] += 1
         mi = kraskov_mi(values, y, pairs, k)
@@ -190,7 +145,4 @@ def edge_select_knn(values, y, edge_index, threshold=1.0, k=5):
     else:
         EDGE_KNN_STATS["host"] += 1
         mi = kraskov_mi_host(values, y, pairs, k)
-    mi_pair, single = mi[:n_edges], mi[n_edges:]
-    at = np.searchsorted(nodes, ei)
-    keep = mi_pair > threshold * np.maximum(single[at[0]], single[at[1]])
-    return keep, mi_pair, {int(v): float(m) for v, m in zip(nodes, single)}
+    return _pairs.decide(mi, nodes, ei, threshold)

@@ -71,20 +71,34 @@ def mutual_info_supported(n, n_features, k, counts_per_label):
     return bool(_lib.lib.mlgnn_mutual_info_supported(sum(kept), int(n_features), int(k), len(kept)))
 
 
-def prepare(x, y, random_state=None):
-    """``mutual_info_classif``'s preparation of dense continuous features, call for call -> ``(X [n, F] fp64, y [n])``."""
+def digamma_table(n):
+    """``psi[c] = digamma(c)`` for ``c = 1 .. n`` as fp64 ``[n + 1]`` (``psi[0] = 0`` is never read): the table every
+    mutual-information kernel looks its neighbour counts up in."""
+    from scipy.special import digamma
+    psi = np.zeros(n + 1, dtype=np.float64)
+    psi[1:] = digamma(np.arange(1, n + 1))
+    return psi
+
+
+def _scale_and_noise(X, rng):
+    """The lines of scikit-learn's ``_estimate_mi`` for dense continuous features: ``scale(with_mean=False)``, then noise
+    of ``1e-10 * max(1, mean|x|)`` per column, the first draw from ``rng`` -> a new fp64 array."""
     from sklearn.preprocessing import scale
-    from sklearn.utils import check_random_state
-    from sklearn.utils.validation import check_X_y
-    X, y = check_X_y(x, y, accept_sparse="csc", y_numeric=False)
     n_samples, n_features = X.shape
-    rng = check_random_state(random_state)
     continuous_mask = np.ones(n_features, dtype=bool)          # dense input: every feature is continuous
     X = X.astype(np.float64, copy=True)
     X[:, continuous_mask] = scale(X[:, continuous_mask], with_mean=False, copy=False)
     means = np.maximum(1, np.mean(np.abs(X[:, continuous_mask]), axis=0))
     X[:, continuous_mask] += 1e-10 * means * rng.standard_normal(size=(n_samples, np.sum(continuous_mask)))
-    return X, y
+    return X
+
+
+def prepare(x, y, random_state=None):
+    """``mutual_info_classif``'s preparation of dense continuous features, call for call -> ``(X [n, F] fp64, y [n])``."""
+    from sklearn.utils import check_random_state
+    from sklearn.utils.validation import check_X_y
+    X, y = check_X_y(x, y, accept_sparse="csc", y_numeric=False)
+    return _scale_and_noise(X, check_random_state(random_state)), y
 
 
 def mutual_info_cd(prepared, y, n_neighbors=3, return_counts=False):
@@ -113,13 +127,11 @@ def mutual_info_cd(prepared, y, n_neighbors=3, return_counts=False):
     count_i = c[d]
     k_i = np.minimum(k, count_i - 1)
     base = float(digamma(n) + np.mean(digamma(k_i)) - np.mean(digamma(count_i)))
-    psi = np.zeros(n + 1, dtype=np.float64)
-    psi[1:] = digamma(np.arange(1, n + 1))
     dev = torch.device("cuda", torch.cuda.current_device())
     rows = X if n == X.shape[0] else X[keep]
     xt = torch.from_numpy(rows).to(dev).t().contiguous()       # [F, n]: the transpose runs on the device
     labels = torch.from_numpy(d.astype(np.int32)).to(dev)
-    psi_d = torch.from_numpy(psi).to(dev)
+    psi_d = torch.from_numpy(digamma_table(n)).to(dev)
     mi = torch.empty(n_features, dtype=torch.float64, device=dev)
     counts = torch.empty((n_features, n), dtype=torch.int32, device=dev) if return_counts else None
     _lib.call("mlgnn_mutual_info_cd", xt, labels, psi_d, base, mi, counts, n, n_features, k, len(c), _lib.stream())
@@ -151,15 +163,10 @@ def prepare_regression(x, y, random_state=None):
     from sklearn.utils import check_random_state
     from sklearn.utils.validation import check_X_y
     X, y = check_X_y(x, y, accept_sparse="csc", y_numeric=True)
-    n_samples, n_features = X.shape
     rng = check_random_state(random_state)
-    continuous_mask = np.ones(n_features, dtype=bool)          # dense input: every feature is continuous
-    X = X.astype(np.float64, copy=True)
-    X[:, continuous_mask] = scale(X[:, continuous_mask], with_mean=False, copy=False)
-    means = np.maximum(1, np.mean(np.abs(X[:, continuous_mask]), axis=0))
-    X[:, continuous_mask] += 1e-10 * means * rng.standard_normal(size=(n_samples, np.sum(continuous_mask)))
+    X = _scale_and_noise(X, rng)
     y = scale(y, with_mean=False)
-    y += 1e-10 * np.maximum(1, np.mean(np.abs(y))) * rng.standard_normal(size=n_samples)
+    y += 1e-10 * np.maximum(1, np.mean(np.abs(y))) * rng.standard_normal(size=X.shape[0])
     return X, y
 
 
@@ -183,12 +190,10 @@ def mutual_info_cc(prepared, y_prepared, n_neighbors=3, return_counts=False):
         mi = np.zeros(0, dtype=np.float64)
         return (mi, np.zeros((0, n), dtype=np.int32), np.zeros((0, n), dtype=np.int32)) if return_counts else mi
     base = float(digamma(n) + digamma(k))
-    psi = np.zeros(n + 1, dtype=np.float64)
-    psi[1:] = digamma(np.arange(1, n + 1))
     dev = torch.device("cuda", torch.cuda.current_device())
     xt = torch.from_numpy(X).to(dev).t().contiguous()          # [F, n]: the transpose runs on the device
     y_d = torch.from_numpy(y).to(dev)
-    psi_d = torch.from_numpy(psi).to(dev)
+    psi_d = torch.from_numpy(digamma_table(n)).to(dev)
     mi = torch.empty(n_features, dtype=torch.float64, device=dev)
     nx = torch.empty((n_features, n), dtype=torch.int32, device=dev) if return_counts else None
     ny = torch.empty((n_features, n), dtype=torch.int32, device=dev) if return_counts else None

@@ -16,74 +16,27 @@ a lower bound of the loop's time), and the JSON says so.  Both legs' decisions a
 
 ``ships_enabled`` is the rule for the default of ``MLGNN_EDGE_SELECT_FUSED``: the kernel leg on ALL edges beats the scaled
 scikit-learn leg by more than that leg's scaled spread at both shapes.  Writes profiles/edge_select.json.  Development
-tool; run it under a time limit of its own (``timeout -k 10 600 python tools/bench_edge_select.py``)."""
-import argparse
+tool; every shape runs in a fresh child process under ``--step_limit`` (tools/_edge_bench.py)."""
 import importlib
-import json
 import os
-import sys
-import time
 
 import numpy as np
-import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
-from mlgnn import _lib  # noqa: E402
-from mlgnn.data import SyntheticTCGA  # noqa: E402
+import _edge_bench as frame
+from _edge_bench import make_fold, wall
 
 ES = importlib.import_module("mlgnn.edge_select")
-SHAPES = [("gbm", 200, 60000), ("kirc", 300, 60000)]
 SEED, K = 12345, 3
-
-
-def make_fold(n, n_edges):
-    """``(values [n, 3 node_num] fp32, labels [n], PPI edge_index [2, E'])`` of a cohort of ``n`` training patients."""
-    data = SyntheticTCGA(n, n_edges=n_edges, seed=0)
-    y = (torch.arange(n) < int(0.3 * n)).long()[torch.randperm(n, generator=torch.Generator().manual_seed(1))]
-    strength = 0.2 + 0.8 * torch.rand(data.NN, generator=torch.Generator().manual_seed(2))
-    x = data.x[:, :, 0] + y[:, None].float() * strength[None, :]
-    return x, y.numpy(), data.edge_index[:, data.n_cross:].numpy()
-
-
-def wall(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3, out
 
 
 def kernel_ms(x, y, ei, warmup, iters):
     """The launch of mlgnn_edge_mi alone (E pairs + U singles), operands resident on the device."""
     from scipy.special import digamma
     from sklearn.utils import check_random_state
-    n, n_nodes = x.shape
-    dev = torch.device("cuda:0")
-    nodes = np.unique(ei)
-    pairs = np.concatenate([ei.T, np.stack([nodes, np.full_like(nodes, -1)], axis=1)]).astype(np.int32)
     _, d, c = np.unique(y, return_inverse=True, return_counts=True)
-    psi = np.zeros(n + 1)
-    psi[1:] = digamma(np.arange(1, n + 1))
-    base = float(digamma(n) + np.mean(digamma(np.minimum(K, c[d] - 1))) - np.mean(digamma(c[d])))
-    xt = x.to(dev).double().t().contiguous()
-    ops = [torch.from_numpy(a).to(dev) for a in (pairs, check_random_state(SEED).standard_normal(n), d.astype(np.int32), psi)]
-    mi = torch.zeros(len(pairs), dtype=torch.float64, device=dev)
-
-    def launch():
-        _lib.call("mlgnn_edge_mi", xt, ops[0], ops[1], ops[2], ops[3], base, mi, None, None, n, n_nodes, len(pairs), K,
-                  len(c), _lib.stream())
-
-    for _ in range(warmup):
-        launch()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(iters):
-        launch()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / iters, len(pairs)
+    base = digamma(len(y)) + np.mean(digamma(np.minimum(K, c[d] - 1))) - np.mean(digamma(c[d]))
+    vectors = (check_random_state(SEED).standard_normal(len(y)), d.astype(np.int32))
+    return frame.kernel_ms("mlgnn_edge_mi", x, ei, vectors, base, K, 2, (len(c),), warmup, iters)
 
 
 def bench_shape(name, n, n_edges, sub, warmup, iters, repeats):
@@ -124,45 +77,24 @@ def bench_shape(name, n, n_edges, sub, warmup, iters, repeats):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--sklearn_edges", type=int, default=400)
-    ap.add_argument("--shapes", default=",".join(s[0] for s in SHAPES))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "edge_select.json"))
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_edge_select.py needs the GPU: there is no CPU path of the op to time")
-    import scipy
-    import sklearn
-    was = ES.ENABLED
+    a = frame.arguments("sklearn_edges", "edge_select.json")
+    if a.child:
+        import scipy
+        import sklearn
+        ES.ENABLED = True
+        return frame.run_child(os.path.basename(__file__), a.child,
+                               lambda n, n_edges: ES.edge_select(*make_fold(n, n_edges), 1.0, K, SEED),
+                               lambda *shape: bench_shape(*shape, a.sklearn_edges, a.warmup, a.iters, a.repeats),
+                               (sklearn, np, scipy))
     result = {"workload": "valid_pca_mutual_info for every PPI edge of a fold (PCA(n_components=1) of the two end columns, "
                           "mutual_info_classif of its score and of each end column, fp64): edge_select on the kernel of "
                           "csrc/edge_select.hip (MLGNN_EDGE_SELECT_FUSED=1) against the loop of scikit-learn calls, same "
                           "input and random_state",
-              "timing": "wall clock around each call with a device synchronise, the two legs alternating over %d repeats, "
-                        "one process; the kernel alone by device events, mean of %d launches after %d; one untimed call "
-                        "of the kernel leg first" % (a.repeats, a.iters, a.warmup),
-              "device": torch.cuda.get_device_name(0), "host_threads": torch.get_num_threads(),
-              "versions": {"sklearn": sklearn.__version__, "numpy": np.__version__, "scipy": scipy.__version__},
-              "shapes": []}
-    x, y, ei = make_fold(SHAPES[0][1], 2000)
-    ES.ENABLED = True
-    ES.edge_select(x, y, ei, 1.0, K, SEED)                                         # discarded: the code object loads
-    for name, n, n_edges in SHAPES:
-        if name not in a.shapes.split(","):
-            continue
-        entry = bench_shape(name, n, n_edges, a.sklearn_edges, a.warmup, a.iters, a.repeats)
-        result["shapes"].append(entry)
-        print(json.dumps(entry), flush=True)
-        result["ships_enabled"] = all(e["summary"]["beats_sklearn_by_more_than_its_spread"] for e in result["shapes"]) \
-            and len(result["shapes"]) == len(SHAPES)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            json.dump(result, fh, indent=1)
-            fh.write("\n")
-    ES.ENABLED = was
+              "timing": "one child process per shape under a limit of %g s; in it wall clock around each call with a "
+                        "device synchronise, the two legs alternating over %d repeats; the kernel alone by device events, "
+                        "mean of %d launches after %d; one untimed call of the kernel leg first"
+                        % (a.step_limit, a.repeats, a.iters, a.warmup)}
+    frame.drive(__file__, a, "sklearn_edges", result, "beats_sklearn_by_more_than_its_spread")
 
 
 if __name__ == "__main__":

@@ -15,77 +15,28 @@ node once: a lower bound of the loop's time -- and the JSON says so.  Both legs'
 subsample.
 
 ``ships_enabled`` is the rule for the default of ``MLGNN_EDGE_KNN_FUSED``: the kernel leg on ALL edges beats the scaled
-host leg by more than that leg's scaled spread at both shapes.  Writes profiles/edge_select_knn.json.  Development tool.
-
-Time limits: the tool itself never opens the GPU.  Every shape -- its untimed first call, its alternating legs and its
-event-timed launches -- runs in a fresh child process under ``--step_limit`` seconds (300); after a child that fails or
-runs out of time nothing more is started and the tool exits non-zero."""
-import argparse
+host leg by more than that leg's scaled spread at both shapes.  Writes profiles/edge_select_knn.json.  Development tool;
+every shape runs in a fresh child process under ``--step_limit`` (tools/_edge_bench.py)."""
 import importlib
-import json
 import os
-import subprocess
-import sys
-import time
 
 import numpy as np
-import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
-from mlgnn import _lib  # noqa: E402
-from mlgnn.data import SyntheticTCGA  # noqa: E402
+import _edge_bench as frame
+from _edge_bench import wall
 
 KN = importlib.import_module("mlgnn.kraskov")
-SHAPES = [("gbm", 200, 60000), ("kirc", 300, 60000)]
 K = 5
 
 
 def make_fold(n, n_edges):
-    """``(values [n, 3 node_num] fp32, label [n] fp64, PPI edge_index [2, E'])`` of a cohort of ``n`` training patients."""
-    data = SyntheticTCGA(n, n_edges=n_edges, seed=0)
-    y = (torch.arange(n) < int(0.3 * n)).long()[torch.randperm(n, generator=torch.Generator().manual_seed(1))]
-    strength = 0.2 + 0.8 * torch.rand(data.NN, generator=torch.Generator().manual_seed(2))
-    x = data.x[:, :, 0] + y[:, None].float() * strength[None, :]
-    return x, y.numpy().astype(np.float64), data.edge_index[:, data.n_cross:].numpy()
-
-
-def wall(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3, out
+    return frame.make_fold(n, n_edges, np.float64)
 
 
 def kernel_ms(x, y, ei, warmup, iters):
     """The launch of mlgnn_kraskov_mi alone (E pairs + U singles), operands resident on the device."""
     from scipy.special import digamma
-    n, n_nodes = x.shape
-    dev = torch.device("cuda:0")
-    nodes = np.unique(ei)
-    pairs = np.concatenate([ei.T, np.stack([nodes, np.full_like(nodes, -1)], axis=1)]).astype(np.int32)
-    psi = np.zeros(n + 1)
-    psi[1:] = digamma(np.arange(1, n + 1))
-    base = float(digamma(K) + digamma(n))
-    xt = x.to(dev).double().t().contiguous()
-    ops = [torch.from_numpy(a).to(dev) for a in (pairs, y, psi)]
-    mi = torch.zeros(len(pairs), dtype=torch.float64, device=dev)
-
-    def launch():
-        _lib.call("mlgnn_kraskov_mi", xt, ops[0], ops[1], ops[2], base, mi, None, None, None, n, n_nodes, len(pairs), K,
-                  _lib.stream())
-
-    for _ in range(warmup):
-        launch()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(iters):
-        launch()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / iters, len(pairs)
+    return frame.kernel_ms("mlgnn_kraskov_mi", x, ei, (y,), digamma(K) + digamma(len(y)), K, 3, (), warmup, iters)
 
 
 def bench_shape(name, n, n_edges, sub, warmup, iters, repeats):
@@ -93,8 +44,8 @@ def bench_shape(name, n, n_edges, sub, warmup, iters, repeats):
     E = ei.shape[1]
     pick = np.random.RandomState(3).choice(E, size=min(sub, E), replace=False)
     x_host = x.numpy()
-    singles = np.unique(ei[:, pick])
-    single_pairs = np.stack([singles, np.full_like(singles, -1)], axis=1)
+    singles, rows = frame.launch_list(ei[:, pick])
+    single_pairs = rows[len(pick):]
     entry = {"shape": name, "n": n, "E": E, "n_nodes": int(x.shape[1]), "k": K, "host_edges": int(len(pick)),
              "host_leg": "kraskov_mi_host on a fixed subsample of the edges; scaled to E at the PAIR calls alone (the "
                          "subsample's end-node calls are timed apart and left out: the whole fold computes each end node "
@@ -131,36 +82,14 @@ def bench_shape(name, n, n_edges, sub, warmup, iters, repeats):
     return entry
 
 
-def run_child(name, a):
-    """One shape in this process: the untimed first call, on the shape's own fold, then the measurement.  Prints the
-    result as the last line of standard output."""
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_edge_select_knn.py needs the GPU: there is no CPU path of the op to time")
-    import scipy
-    _, n, n_edges = next(shape for shape in SHAPES if shape[0] == name)
-    x, y, ei = make_fold(n, n_edges)
-    KN.ENABLED = True
-    KN.edge_select_knn(x, y, ei, 1.0, K)                      # discarded: the code object loads, the allocator grows
-    entry = bench_shape(name, n, n_edges, a.host_edges, a.warmup, a.iters, a.repeats)
-    print(json.dumps({"entry": entry, "device": torch.cuda.get_device_name(0), "host_threads": torch.get_num_threads(),
-                      "versions": {"numpy": np.__version__, "scipy": scipy.__version__}}), flush=True)
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--host_edges", type=int, default=400)
-    ap.add_argument("--shapes", default=",".join(s[0] for s in SHAPES))
-    ap.add_argument("--step_limit", type=float, default=300.0, help="seconds one shape's child process may take")
-    ap.add_argument("--child", default=None, help="(internal) measure this shape in this process")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "edge_select_knn.json"))
-    a = ap.parse_args()
+    a = frame.arguments("host_edges", "edge_select_knn.json")
     if a.child:
-        return run_child(a.child, a)
-    # This process never opens the GPU: every shape is measured by a fresh child under a time limit of its own, and
-    # after a child that failed or ran out of time nothing more is started.
+        import scipy
+        KN.ENABLED = True
+        return frame.run_child(os.path.basename(__file__), a.child,
+                               lambda n, n_edges: KN.edge_select_knn(*make_fold(n, n_edges), 1.0, K),
+                               lambda *shape: bench_shape(*shape, a.host_edges, a.warmup, a.iters, a.repeats), (np, scipy))
     result = {"workload": "valid_pca_mutual_info under --knn_mutual_info for every PPI edge of a fold (kraskov_mi of the two "
                           "raw end columns and of each end column against the label, k = 5, fp64): edge_select_knn on the "
                           "kernel of csrc/kraskov_mi.hip (MLGNN_EDGE_KNN_FUSED=1) against kraskov_mi_host (three cKDTree "
@@ -168,27 +97,8 @@ def main():
               "timing": "one child process per shape under a limit of %g s; in it wall clock around each call with a "
                         "device synchronise, the two legs alternating over %d repeats; the kernel alone by device events, "
                         "mean of %d launches after %d; one untimed call of the kernel leg first"
-                        % (a.step_limit, a.repeats, a.iters, a.warmup),
-              "shapes": []}
-    for name, _, _ in SHAPES:
-        if name not in a.shapes.split(","):
-            continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", name, "--warmup", str(a.warmup), "--iters", str(a.iters),
-               "--repeats", str(a.repeats), "--host_edges", str(a.host_edges)]
-        try:
-            done = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=a.step_limit, check=True, text=True)
-        except (subprocess.TimeoutExpired, subprocess.CalledProcessError) as err:
-            raise SystemExit("bench_edge_select_knn.py: shape %s: %s; nothing more is started" % (name, err))
-        child = json.loads(done.stdout.strip().splitlines()[-1])
-        result["shapes"].append(child.pop("entry"))
-        result.update(child)
-        print(json.dumps(result["shapes"][-1]), flush=True)
-        result["ships_enabled"] = all(e["summary"]["beats_host_by_more_than_its_spread"] for e in result["shapes"]) \
-            and len(result["shapes"]) == len(SHAPES)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            json.dump(result, fh, indent=1)
-            fh.write("\n")
+                        % (a.step_limit, a.repeats, a.iters, a.warmup)}
+    frame.drive(__file__, a, "host_edges", result, "beats_host_by_more_than_its_spread")
 
 
 if __name__ == "__main__":

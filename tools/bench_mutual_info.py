@@ -64,11 +64,9 @@ def kernel_ms(prepared, y, k, warmup, iters):
     n, F = prepared.shape
     dev = torch.device("cuda:0")
     _, d, c = np.unique(y, return_inverse=True, return_counts=True)
-    psi = np.zeros(n + 1)
-    psi[1:] = digamma(np.arange(1, n + 1))
     base = float(digamma(n) + np.mean(digamma(np.minimum(k, c[d] - 1))) - np.mean(digamma(c[d])))
     xt = torch.from_numpy(prepared).to(dev).t().contiguous()
-    labels, psi_d = torch.from_numpy(d.astype(np.int32)).to(dev), torch.from_numpy(psi).to(dev)
+    labels, psi_d = torch.from_numpy(d.astype(np.int32)).to(dev), torch.from_numpy(MI.digamma_table(n)).to(dev)
     mi = torch.empty(F, dtype=torch.float64, device=dev)
     stream = torch.cuda.current_stream().cuda_stream
 
@@ -93,11 +91,9 @@ def kernel_ms_regression(prepared, y_prepared, k, warmup, iters):
     from scipy.special import digamma
     n, F = prepared.shape
     dev = torch.device("cuda:0")
-    psi = np.zeros(n + 1)
-    psi[1:] = digamma(np.arange(1, n + 1))
     base = float(digamma(n) + digamma(k))
     xt = torch.from_numpy(prepared).to(dev).t().contiguous()
-    y_d, psi_d = torch.from_numpy(y_prepared).to(dev), torch.from_numpy(psi).to(dev)
+    y_d, psi_d = torch.from_numpy(y_prepared).to(dev), torch.from_numpy(MI.digamma_table(n)).to(dev)
     mi = torch.empty(F, dtype=torch.float64, device=dev)
     stream = torch.cuda.current_stream().cuda_stream
 
