@@ -1,20 +1,21 @@
-"""The frame the three edge-test benchmarks share (tools/bench_edge_select.py, bench_edge_select_knn.py,
-bench_edge_select_reg.py): the fold, the two clocks, the event-timed launch of a pair-list entry point on the library's own
-launch list and table, and the driver that measures every shape in a fresh child process.  Each tool keeps its legs, its
-comparison, its texts and its JSON keys.
+"""What the three edge-test benchmarks share beyond tools/_bench.py (tools/bench_edge_select.py, bench_edge_select_knn.py,
+bench_edge_select_reg.py): the shapes, the fold, the event-timed launch of a pair-list entry point on the library's own
+launch list and table, the flags, and the two ends of the frame's child driver as these tools use it.  Each tool keeps its
+legs, its comparison, its texts and its JSON keys.
 
 Time limits: the tool's own process never opens the GPU.  Every shape -- its untimed first call, its alternating legs and
 its event-timed launches -- runs in a fresh child process under ``--step_limit`` seconds (300); after a child that fails or
-runs out of time nothing more is started and the tool exits non-zero."""
+runs out of time nothing more is started and the tool exits non-zero (``_bench.drive``)."""
 import argparse
 import json
 import os
-import subprocess
 import sys
-import time
 
 import numpy as np
 import torch
+
+import _bench
+from _bench import event_ms
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
@@ -34,28 +35,6 @@ def make_fold(n, n_edges, label_dtype=np.int64):
     strength = 0.2 + 0.8 * torch.rand(data.NN, generator=torch.Generator().manual_seed(2))
     x = data.x[:, :, 0] + y[:, None].float() * strength[None, :]
     return x, y.numpy().astype(label_dtype), data.edge_index[:, data.n_cross:].numpy()
-
-
-def wall(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3, out
-
-
-def event_ms(launch, warmup, iters):
-    """The mean of ``iters`` calls of ``launch`` by device events, after ``warmup`` untimed ones."""
-    for _ in range(warmup):
-        launch()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(iters):
-        launch()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / iters
 
 
 def kernel_ms(entry, x, ei, vectors, base, k, n_outputs, tail, warmup, iters):
@@ -88,40 +67,28 @@ def arguments(subsample_flag, out_name):
     return ap.parse_args()
 
 
-def run_child(tool, name, first_call, bench_shape, versions):
+def run_shape(tool, name, first_call, bench_shape, versions):
     """One shape in this process: the untimed ``first_call(n, n_edges)`` of the kernel leg on the shape's own fold (the
-    code object loads, the allocator grows), then ``bench_shape(name, n, n_edges)``.  Prints the result as the last line
-    of standard output; ``versions``: the modules whose versions go with it."""
-    if not torch.cuda.is_available():
-        raise SystemExit("%s needs the GPU: there is no CPU path of the op to time" % tool)
+    code object loads, the allocator grows), then ``bench_shape(name, n, n_edges)``; ``versions``: the modules whose
+    versions go with the result."""
+    _bench.need_gpu(tool, "CPU path of the op")
     _, n, n_edges = next(shape for shape in SHAPES if shape[0] == name)
     first_call(n, n_edges)
     entry = bench_shape(name, n, n_edges)
-    print(json.dumps({"entry": entry, "device": torch.cuda.get_device_name(0), "host_threads": torch.get_num_threads(),
-                      "versions": {m.__name__: m.__version__ for m in versions}}), flush=True)
+    _bench.child_result({"entry": entry, "device": torch.cuda.get_device_name(0), "host_threads": torch.get_num_threads(),
+                         "versions": {m.__name__: m.__version__ for m in versions}})
 
 
 def drive(script, a, subsample_flag, result, beats):
-    """The parent: one fresh child of ``script`` per shape under ``--step_limit``, nothing started after one that fails or
-    times out; ``result`` (the tool's texts) grows by the children's entries and is rewritten to ``--out`` after every
-    shape; ``ships_enabled`` holds only when every shape ran and its summary says ``beats``."""
-    tool = os.path.basename(script)
+    """The parent: ``result`` (the tool's texts) grows by the children's entries; ``ships_enabled`` holds only when every
+    shape ran and its summary says ``beats``."""
     result["shapes"] = []
-    for name, _, _ in SHAPES:
-        if name not in a.shapes.split(","):
-            continue
-        cmd = [sys.executable, os.path.abspath(script), "--child", name, "--warmup", str(a.warmup), "--iters", str(a.iters),
-               "--repeats", str(a.repeats), "--" + subsample_flag, str(getattr(a, subsample_flag))]
-        try:
-            done = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=a.step_limit, check=True, text=True)
-        except (subprocess.TimeoutExpired, subprocess.CalledProcessError) as err:
-            raise SystemExit("%s: shape %s: %s; nothing more is started" % (tool, name, err))
-        child = json.loads(done.stdout.strip().splitlines()[-1])
+
+    def collect(_, child):
         result["shapes"].append(child.pop("entry"))
         result.update(child)
         print(json.dumps(result["shapes"][-1]), flush=True)
         result["ships_enabled"] = all(e["summary"][beats] for e in result["shapes"]) and len(result["shapes"]) == len(SHAPES)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            json.dump(result, fh, indent=1)
-            fh.write("\n")
+
+    flags = ["--warmup", a.warmup, "--iters", a.iters, "--repeats", a.repeats, "--" + subsample_flag, getattr(a, subsample_flag)]
+    _bench.drive(script, [s[0] for s in SHAPES if s[0] in a.shapes.split(",")], flags, a.step_limit, a.out, result, collect)

@@ -18,10 +18,11 @@ import argparse
 import json
 import os
 import sys
-import time
 from types import SimpleNamespace
 
 import torch
+
+from _bench import alternate, beats, event_ms, leg_summary, need_gpu, switched, wall, write_json
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
@@ -33,19 +34,6 @@ SHAPES = [("gbm", 32, 28032), ("kirc", 64, 42048), ("no_feature", 64, 0)]
 MODES = ["plain", "sample"]
 REPEATS = 3
 COEF = 1.0
-
-
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(iters):
-        fn()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / iters
 
 
 def device_kernels(fn):
@@ -104,19 +92,16 @@ def bench_shape(name, B, M, mode, dev, warmup, iters):
              "agreement": {"loss_hip": res["hip"][0], "loss_torch": res["torch"][0],
                            "grad_max_abs_diff_over_max_abs": [rel(a, b) for a, b in zip(res["hip"][1], res["torch"][1])]},
              "device_kernels": {leg: {"forward": device_kernels(fn), "forward_backward": device_kernels(step(fn))}
-                                for leg, fn in legs.items()},
-             "hip": {"forward_ms": [], "forward_backward_ms": []}, "torch": {"forward_ms": [], "forward_backward_ms": []}}
-    for _ in range(REPEATS):                                                 # the legs alternate
-        for leg, fn in legs.items():
-            entry[leg]["forward_ms"].append(timed(fn, warmup, iters))
-            entry[leg]["forward_backward_ms"].append(timed(step(fn), warmup, iters))
+                                for leg, fn in legs.items()}}
+    entry.update(alternate(REPEATS, legs, {"forward_ms": lambda fn: event_ms(fn, warmup, iters),           # the legs alternate
+                                           "forward_backward_ms": lambda fn: event_ms(step(fn), warmup, iters)}))
     entry["summary"] = {}
     for key in ("forward_ms", "forward_backward_ms"):
         hip, ref = entry["hip"][key], entry["torch"][key]
-        entry["summary"][key] = {"hip_mean": sum(hip) / REPEATS, "torch_mean": sum(ref) / REPEATS,
-                                 "torch_spread": max(ref) - min(ref), "hip_spread": max(hip) - min(hip),
-                                 "speedup_over_torch": sum(ref) / sum(hip),
-                                 "beats_torch_by_more_than_its_spread": sum(ref) / REPEATS - sum(hip) / REPEATS > max(ref) - min(ref)}
+        h, r = leg_summary(hip), leg_summary(ref)
+        entry["summary"][key] = {"hip_mean": h["mean"], "torch_mean": r["mean"], "torch_spread": r["spread"],
+                                 "hip_spread": h["spread"], "speedup_over_torch": sum(ref) / sum(hip),
+                                 "beats_torch_by_more_than_its_spread": beats(hip, ref)}
     return entry
 
 
@@ -163,21 +148,18 @@ def bench_step(shape, pca_loss, steps, warmup, dev):
         opt.step()
         return loss
 
+    def run(count):
+        for _ in range(count):
+            step()
+
     out = {"shape": shape, "batch": B, "steps": steps, "pca_loss": bool(args.pca_loss), "fused": [], "torch": []}
     for _ in range(REPEATS):
         for leg, on in (("fused", True), ("torch", False)):
-            C.ENABLED = on
-            for _ in range(warmup):
-                step()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                step()
-            torch.cuda.synchronize()
-            out[leg].append((time.perf_counter() - t0) / steps * 1e3)
-    C.ENABLED = C.DEFAULT_ENABLED
-    out["summary_ms_per_step"] = {"fused_mean": sum(out["fused"]) / REPEATS, "torch_mean": sum(out["torch"]) / REPEATS,
-                                  "torch_spread": max(out["torch"]) - min(out["torch"])}
+            with switched(C, "ENABLED", on):
+                run(warmup)
+                out[leg].append(wall(lambda: run(steps))[0] / steps)
+    out["summary_ms_per_step"] = {"fused_mean": leg_summary(out["fused"])["mean"], "torch_mean": leg_summary(out["torch"])["mean"],
+                                  "torch_spread": leg_summary(out["torch"])["spread"]}
     return out
 
 
@@ -188,8 +170,7 @@ def main():
     ap.add_argument("--steps", type=int, default=0, help="also time this many training steps per leg at the gbm and kirc shapes")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "criterion.json"))
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_criterion.py needs the GPU: there is no CPU path to time")
+    need_gpu("bench_criterion.py")
     dev = torch.device("cuda:0")
     result = {"workload": "BCELoss (plain / per-sample weights) + pca feature loss, fp32: the op of csrc/criterion.hip "
                           "against the torch lines (MLGNN_CRITERION_FUSED=0), same tensors",
@@ -208,10 +189,7 @@ def main():
                 entry = bench_step(shape, pca_loss, a.steps, 3, dev)
                 result["step"].append(entry)
                 print(json.dumps(entry), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(result, fh, indent=1)
-        fh.write("\n")
+    write_json(a.out, result)
 
 
 if __name__ == "__main__":

@@ -24,6 +24,8 @@ import sys
 
 import torch
 
+from _bench import alternate, event_ms, leg_summary, need_gpu, switched, write_json
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -46,19 +48,6 @@ def segments():
     return torch.sort(torch.randint(0, S, (G,), generator=gen))[0]
 
 
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(iters):
-        fn()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / iters
-
-
 def bench_case(case, seg, dev, warmup, iters, repeats):
     B, C, k, decoder_type, decoder_dim = case
     torch.manual_seed(1)
@@ -72,17 +61,14 @@ def bench_case(case, seg, dev, warmup, iters, repeats):
     max_hid, max_out, total = model._dec_limits
     assert total == G and D.decoder_supported(z, max_hid, max_out, total), "the op does not take this case"
 
-    def leg(on):
-        def fwd():
-            D.ENABLED = on
-            return model.foreach_decoder(z)
+    def fwd():
+        return model.foreach_decoder(z)
 
-        def step():
-            z.grad = None
-            for p in params:
-                p.grad = None
-            (fwd() * cot).sum().backward()
-        return fwd, step
+    def step():
+        z.grad = None
+        for p in params:
+            p.grad = None
+        (fwd() * cot).sum().backward()
 
     def pack():
         return [torch.cat([b[0].weight.reshape(-1) for b in blocks]), torch.cat([b[0].bias for b in blocks]),
@@ -104,28 +90,25 @@ def bench_case(case, seg, dev, warmup, iters, repeats):
     stats = dict(D.DECODER_STATS)
     outs, grads = {}, {}
     for on in (True, False):
-        fwd, step = leg(on)
-        outs[on] = fwd().detach()
-        step()
+        with switched(D, "ENABLED", on):
+            outs[on] = fwd().detach()
+            step()
         grads[on] = [z.grad.clone()] + [p.grad.clone() for p in params]
     assert D.DECODER_STATS["hip"] == stats["hip"] + 2 and D.DECODER_STATS["torch"] == stats["torch"] + 2
     rel = lambda a, b: float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
     entry["agreement"] = {"out_max_abs_diff_over_max_abs": rel(outs[True], outs[False]),
                           "worst_grad_max_abs_diff_over_max_abs": max(rel(a, b) for a, b in zip(grads[True], grads[False]))}
-    runs = {"hip": [], "torch": [], "packing": []}
-    for _ in range(repeats):                                   # the legs alternate inside every repeat
-        for name, on in (("hip", True), ("torch", False)):
-            fwd, step = leg(on)
-            runs[name].append({"forward_ms": timed(fwd, warmup, iters), "forward_backward_ms": timed(step, warmup, iters)})
-        runs["packing"].append({"forward_ms": timed(pack, warmup, iters), "forward_backward_ms": timed(pack_step, warmup, iters)})
-    D.ENABLED = True
+    # the legs alternate inside every repeat; (the switch's setting, forward, forward + backward) of each
+    runs = alternate(repeats, {"hip": (True, fwd, step), "torch": (False, fwd, step), "packing": (False, pack, pack_step)},
+                     {"forward_ms": lambda leg: event_ms(leg[1], warmup, iters),
+                      "forward_backward_ms": lambda leg: event_ms(leg[2], warmup, iters)},
+                     entering=lambda leg: switched(D, "ENABLED", leg[0]))
     for name, rs in runs.items():
-        entry[name] = {key: {"mean": sum(r[key] for r in rs) / len(rs), "min": min(r[key] for r in rs),
-                             "max": max(r[key] for r in rs)} for key in rs[0]}
+        entry[name] = {key: {stat: leg_summary(ms)[stat] for stat in ("mean", "min", "max")} for key, ms in rs.items()}
     # the claim: forward + backward through the op is not slower than the replaced path, within that path's own spread
-    t = entry["torch"]["forward_backward_ms"]
+    t = leg_summary(runs["torch"]["forward_backward_ms"])
     entry["speedup_over_torch"] = {key: entry["torch"][key]["mean"] / entry["hip"][key]["mean"] for key in entry["hip"]}
-    entry["not_slower_forward_backward"] = entry["hip"]["forward_backward_ms"]["mean"] <= t["mean"] + (t["max"] - t["min"])
+    entry["not_slower_forward_backward"] = entry["hip"]["forward_backward_ms"]["mean"] <= t["mean"] + t["spread"]
     return entry
 
 
@@ -137,8 +120,7 @@ def main():
     ap.add_argument("--cases", type=int, nargs="*", help="indices into the case table (default: all)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pathway_decoder.json"))
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_decoder.py needs the GPU: there is no CPU path to time")
+    need_gpu("bench_decoder.py")
     dev = torch.device("cuda:0")
     seg = segments()
     result = {"workload": "foreach_decoder of the pre-training models over 438 segments / 25 015 genes, fp32: one launch "
@@ -152,10 +134,7 @@ def main():
         entry = bench_case(case, seg, dev, a.warmup, a.iters, a.repeats)
         result["op"].append(entry)
         print(json.dumps(entry), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(result, fh, indent=1)
-        fh.write("\n")
+    write_json(a.out, result)
 
 
 if __name__ == "__main__":

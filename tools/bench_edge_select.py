@@ -16,14 +16,15 @@ a lower bound of the loop's time), and the JSON says so.  Both legs' decisions a
 
 ``ships_enabled`` is the rule for the default of ``MLGNN_EDGE_SELECT_FUSED``: the kernel leg on ALL edges beats the scaled
 scikit-learn leg by more than that leg's scaled spread at both shapes.  Writes profiles/edge_select.json.  Development
-tool; every shape runs in a fresh child process under ``--step_limit`` (tools/_edge_bench.py)."""
+tool; every shape runs in a fresh child process under ``--step_limit`` (``drive`` of tools/_bench.py)."""
 import importlib
 import os
 
 import numpy as np
 
 import _edge_bench as frame
-from _edge_bench import make_fold, wall
+from _bench import beats, leg_summary, switched, wall
+from _edge_bench import make_fold
 
 ES = importlib.import_module("mlgnn.edge_select")
 SEED, K = 12345, 3
@@ -50,11 +51,10 @@ def bench_shape(name, n, n_edges, sub, warmup, iters, repeats):
              "hip_end_to_end_ms": [], "sklearn_subsample_ms": [], "kernel_ms": []}
     got = want = None
     for _ in range(repeats):                                                  # the legs alternate
-        ES.ENABLED = True
         ms, got = wall(lambda: ES.edge_select(x, y, ei, 1.0, K, SEED))
         entry["hip_end_to_end_ms"].append(ms)
-        ES.ENABLED = False
-        ms, want = wall(lambda: ES.edge_select(x, y, ei[:, pick], 1.0, K, SEED))
+        with switched(ES, "ENABLED", False):
+            ms, want = wall(lambda: ES.edge_select(x, y, ei[:, pick], 1.0, K, SEED))
         entry["sklearn_subsample_ms"].append(ms)
         ms, launched = kernel_ms(x, y, ei, warmup, iters)
         entry["kernel_ms"].append(ms)
@@ -67,12 +67,13 @@ def bench_shape(name, n, n_edges, sub, warmup, iters, repeats):
     entry["kept_by_the_kernel_leg"] = int(got[0].sum())
     scale = E / len(pick) / 3.0
     hip, ref = entry["hip_end_to_end_ms"], [ms * scale for ms in entry["sklearn_subsample_ms"]]
-    entry["summary"] = {"hip_end_to_end_mean_ms": sum(hip) / repeats, "hip_spread_ms": max(hip) - min(hip),
-                        "sklearn_per_edge_ms": sum(entry["sklearn_subsample_ms"]) / repeats / len(pick),
-                        "sklearn_scaled_mean_ms": sum(ref) / repeats, "sklearn_scaled_spread_ms": max(ref) - min(ref),
-                        "kernel_mean_ms": sum(entry["kernel_ms"]) / repeats,
+    h, r = leg_summary(hip), leg_summary(ref)
+    entry["summary"] = {"hip_end_to_end_mean_ms": h["mean"], "hip_spread_ms": h["spread"],
+                        "sklearn_per_edge_ms": leg_summary(entry["sklearn_subsample_ms"])["mean"] / len(pick),
+                        "sklearn_scaled_mean_ms": r["mean"], "sklearn_scaled_spread_ms": r["spread"],
+                        "kernel_mean_ms": leg_summary(entry["kernel_ms"])["mean"],
                         "speedup_over_sklearn": sum(ref) / sum(hip),
-                        "beats_sklearn_by_more_than_its_spread": sum(ref) / repeats - sum(hip) / repeats > max(ref) - min(ref)}
+                        "beats_sklearn_by_more_than_its_spread": beats(hip, ref)}
     return entry
 
 
@@ -81,11 +82,11 @@ def main():
     if a.child:
         import scipy
         import sklearn
-        ES.ENABLED = True
-        return frame.run_child(os.path.basename(__file__), a.child,
-                               lambda n, n_edges: ES.edge_select(*make_fold(n, n_edges), 1.0, K, SEED),
-                               lambda *shape: bench_shape(*shape, a.sklearn_edges, a.warmup, a.iters, a.repeats),
-                               (sklearn, np, scipy))
+        with switched(ES, "ENABLED", True):
+            return frame.run_shape(os.path.basename(__file__), a.child,
+                                   lambda n, n_edges: ES.edge_select(*make_fold(n, n_edges), 1.0, K, SEED),
+                                   lambda *shape: bench_shape(*shape, a.sklearn_edges, a.warmup, a.iters, a.repeats),
+                                   (sklearn, np, scipy))
     result = {"workload": "valid_pca_mutual_info for every PPI edge of a fold (PCA(n_components=1) of the two end columns, "
                           "mutual_info_classif of its score and of each end column, fp64): edge_select on the kernel of "
                           "csrc/edge_select.hip (MLGNN_EDGE_SELECT_FUSED=1) against the loop of scikit-learn calls, same "

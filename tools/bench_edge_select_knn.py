@@ -16,14 +16,14 @@ subsample.
 
 ``ships_enabled`` is the rule for the default of ``MLGNN_EDGE_KNN_FUSED``: the kernel leg on ALL edges beats the scaled
 host leg by more than that leg's scaled spread at both shapes.  Writes profiles/edge_select_knn.json.  Development tool;
-every shape runs in a fresh child process under ``--step_limit`` (tools/_edge_bench.py)."""
+every shape runs in a fresh child process under ``--step_limit`` (``drive`` of tools/_bench.py)."""
 import importlib
 import os
 
 import numpy as np
 
 import _edge_bench as frame
-from _edge_bench import wall
+from _bench import beats, leg_summary, switched, wall
 
 KN = importlib.import_module("mlgnn.kraskov")
 K = 5
@@ -53,7 +53,6 @@ def bench_shape(name, n, n_edges, sub, warmup, iters, repeats):
              "hip_end_to_end_ms": [], "host_pair_calls_ms": [], "host_node_calls_ms": [], "kernel_ms": []}
     got = pair = node = None
     for _ in range(repeats):                                                  # the legs alternate
-        KN.ENABLED = True
         ms, got = wall(lambda: KN.edge_select_knn(x, y, ei, 1.0, K))
         entry["hip_end_to_end_ms"].append(ms)
         ms, pair = wall(lambda: KN.kraskov_mi_host(x_host, y, ei[:, pick].T, K))
@@ -73,12 +72,13 @@ def bench_shape(name, n, n_edges, sub, warmup, iters, repeats):
     entry["kept_by_the_kernel_leg"] = int(got[0].sum())
     scale = E / len(pick)
     hip, ref = entry["hip_end_to_end_ms"], [ms * scale for ms in entry["host_pair_calls_ms"]]
-    entry["summary"] = {"hip_end_to_end_mean_ms": sum(hip) / repeats, "hip_spread_ms": max(hip) - min(hip),
-                        "host_per_pair_call_ms": sum(entry["host_pair_calls_ms"]) / repeats / len(pick),
-                        "host_scaled_mean_ms": sum(ref) / repeats, "host_scaled_spread_ms": max(ref) - min(ref),
-                        "kernel_mean_ms": sum(entry["kernel_ms"]) / repeats,
+    h, r = leg_summary(hip), leg_summary(ref)
+    entry["summary"] = {"hip_end_to_end_mean_ms": h["mean"], "hip_spread_ms": h["spread"],
+                        "host_per_pair_call_ms": leg_summary(entry["host_pair_calls_ms"])["mean"] / len(pick),
+                        "host_scaled_mean_ms": r["mean"], "host_scaled_spread_ms": r["spread"],
+                        "kernel_mean_ms": leg_summary(entry["kernel_ms"])["mean"],
                         "speedup_over_host": sum(ref) / sum(hip),
-                        "beats_host_by_more_than_its_spread": sum(ref) / repeats - sum(hip) / repeats > max(ref) - min(ref)}
+                        "beats_host_by_more_than_its_spread": beats(hip, ref)}
     return entry
 
 
@@ -86,10 +86,10 @@ def main():
     a = frame.arguments("host_edges", "edge_select_knn.json")
     if a.child:
         import scipy
-        KN.ENABLED = True
-        return frame.run_child(os.path.basename(__file__), a.child,
-                               lambda n, n_edges: KN.edge_select_knn(*make_fold(n, n_edges), 1.0, K),
-                               lambda *shape: bench_shape(*shape, a.host_edges, a.warmup, a.iters, a.repeats), (np, scipy))
+        with switched(KN, "ENABLED", True):
+            return frame.run_shape(os.path.basename(__file__), a.child,
+                                   lambda n, n_edges: KN.edge_select_knn(*make_fold(n, n_edges), 1.0, K),
+                                   lambda *shape: bench_shape(*shape, a.host_edges, a.warmup, a.iters, a.repeats), (np, scipy))
     result = {"workload": "valid_pca_mutual_info under --knn_mutual_info for every PPI edge of a fold (kraskov_mi of the two "
                           "raw end columns and of each end column against the label, k = 5, fp64): edge_select_knn on the "
                           "kernel of csrc/kraskov_mi.hip (MLGNN_EDGE_KNN_FUSED=1) against kraskov_mi_host (three cKDTree "

@@ -19,14 +19,14 @@ so.  Both legs' values and decisions are compared on the subsample, seeded alike
 ``ships_enabled`` is the rule for the default of ``MLGNN_EDGE_REG_FUSED``: the kernel leg on ALL edges, in the slower of
 its two forms, beats the scaled host leg by more than that leg's scaled spread at both shapes.  Writes
 profiles/edge_select_reg.json.  Development tool; every shape runs in a fresh child process under ``--step_limit``
-(tools/_edge_bench.py)."""
+(``drive`` of tools/_bench.py)."""
 import importlib
 import os
 
 import numpy as np
 
 import _edge_bench as frame
-from _edge_bench import wall
+from _bench import beats, leg_summary, switched, wall
 
 ER = importlib.import_module("mlgnn.edge_select_reg")
 SEED, K = 12345, 3
@@ -74,7 +74,6 @@ def bench_shape(name, n, n_edges, sub, warmup, iters, repeats):
              "kernel_ms": []}
     got = pair = node = None
     for _ in range(repeats):                                                  # the legs alternate
-        ER.ENABLED = True
         ms, got = wall(lambda: ER.edge_select_regression(x, y, ei, 1.0, K, SEED, SEED))
         entry["hip_end_to_end_ms"].append(ms)
         ms, _ = wall(lambda: ER.edge_select_regression(x, y, ei, 1.0, K, SEED, None))
@@ -98,13 +97,14 @@ def bench_shape(name, n, n_edges, sub, warmup, iters, repeats):
     one, two = entry["hip_end_to_end_ms"], entry["hip_two_launches_ms"]
     hip = one if sum(one) >= sum(two) else two                                 # the slower form decides
     ref = [ms * scale for ms in entry["host_pair_calls_ms"]]
-    entry["summary"] = {"hip_end_to_end_mean_ms": sum(one) / repeats, "hip_spread_ms": max(one) - min(one),
-                        "hip_two_launches_mean_ms": sum(two) / repeats, "hip_two_launches_spread_ms": max(two) - min(two),
-                        "host_per_pair_call_ms": sum(entry["host_pair_calls_ms"]) / repeats / len(pick),
-                        "host_scaled_mean_ms": sum(ref) / repeats, "host_scaled_spread_ms": max(ref) - min(ref),
-                        "kernel_mean_ms": sum(entry["kernel_ms"]) / repeats,
+    h1, h2, r = leg_summary(one), leg_summary(two), leg_summary(ref)
+    entry["summary"] = {"hip_end_to_end_mean_ms": h1["mean"], "hip_spread_ms": h1["spread"],
+                        "hip_two_launches_mean_ms": h2["mean"], "hip_two_launches_spread_ms": h2["spread"],
+                        "host_per_pair_call_ms": leg_summary(entry["host_pair_calls_ms"])["mean"] / len(pick),
+                        "host_scaled_mean_ms": r["mean"], "host_scaled_spread_ms": r["spread"],
+                        "kernel_mean_ms": leg_summary(entry["kernel_ms"])["mean"],
                         "speedup_over_host": sum(ref) / sum(hip),
-                        "beats_host_by_more_than_its_spread": sum(ref) / repeats - sum(hip) / repeats > max(ref) - min(ref)}
+                        "beats_host_by_more_than_its_spread": beats(hip, ref)}
     return entry
 
 
@@ -113,11 +113,11 @@ def main():
     if a.child:
         import scipy
         import sklearn
-        ER.ENABLED = True
-        return frame.run_child(os.path.basename(__file__), a.child,
-                               lambda n, n_edges: ER.edge_select_regression(*make_fold(n, n_edges), 1.0, K, SEED, SEED),
-                               lambda *shape: bench_shape(*shape, a.host_edges, a.warmup, a.iters, a.repeats),
-                               (sklearn, np, scipy))
+        with switched(ER, "ENABLED", True):
+            return frame.run_shape(os.path.basename(__file__), a.child,
+                                   lambda n, n_edges: ER.edge_select_regression(*make_fold(n, n_edges), 1.0, K, SEED, SEED),
+                                   lambda *shape: bench_shape(*shape, a.host_edges, a.warmup, a.iters, a.repeats),
+                                   (sklearn, np, scipy))
     result = {"workload": "valid_pca_mutual_info with mutual_classif false for every PPI edge of a fold "
                           "(PCA(n_components=1) of the two end columns, mutual_info_regression of its score and of each end "
                           "column against the label, k = 3, fp64): edge_select_regression on the kernel of "

@@ -14,6 +14,8 @@ import sys
 import torch
 import torch.nn.functional as F
 
+from _bench import event_ms, need_gpu, switched, write_json
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
 import mlgnn.gat  # noqa: E402
@@ -56,19 +58,6 @@ def op_bytes(N, E, H, C):
     return dict(forward=scores + fwd, backward=pre + main + finish)
 
 
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(iters):
-        fn()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / iters
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", type=int, default=64)
@@ -80,8 +69,7 @@ def main():
     ap.add_argument("--no-torch-ops", action="store_true", help="skip the torch-op formulation (per-kernel profiles)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gat_layer.json"))
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_gat.py needs the GPU: there is no CPU path to time")
+    need_gpu("bench_gat.py")
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(2024)
     B, n = a.graphs, a.nodes
@@ -122,11 +110,11 @@ def main():
         for name, op in (("hip", REAL_OP), ("torch_ops", torch_gat_aggregate)):
             if name == "torch_ops" and a.no_torch_ops:
                 continue
-            mlgnn.gat.gat_aggregate = op
-            t = {"layer_forward_ms": timed(layer_fwd, a.warmup, a.iters), "layer_forward_backward_ms": timed(layer_step, a.warmup, a.iters),
-                 "op_forward_ms": timed(op_fwd, a.warmup, a.iters), "op_forward_backward_ms": timed(op_step, a.warmup, a.iters)}
-            entry[name] = t
-        mlgnn.gat.gat_aggregate = REAL_OP
+            with switched(mlgnn.gat, "gat_aggregate", op):
+                entry[name] = {"layer_forward_ms": event_ms(layer_fwd, a.warmup, a.iters),
+                               "layer_forward_backward_ms": event_ms(layer_step, a.warmup, a.iters),
+                               "op_forward_ms": event_ms(op_fwd, a.warmup, a.iters),
+                               "op_forward_backward_ms": event_ms(op_step, a.warmup, a.iters)}
         hip, ab = entry["hip"], entry["algorithmic_bytes"]
         bwd_ms = hip["op_forward_backward_ms"] - hip["op_forward_ms"]
         entry["hip_share_of_hbm_peak"] = {"op_forward": ab["forward"] / (hip["op_forward_ms"] * 1e-3) / HBM_PEAK,
@@ -135,10 +123,7 @@ def main():
             entry["speedup_over_torch_ops"] = {k: entry["torch_ops"][k] / hip[k] for k in hip}
         result["layers"].append(entry)
         print(json.dumps(entry), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(result, fh, indent=1)
-        fh.write("\n")
+    write_json(a.out, result)
 
 
 if __name__ == "__main__":

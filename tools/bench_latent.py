@@ -21,6 +21,8 @@ import sys
 
 import torch
 
+from _bench import alternate, event_ms, leg_summary, need_gpu, switched, write_json
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
 from mlgnn import latent as L  # noqa: E402
@@ -56,19 +58,6 @@ class Head(torch.nn.Module):
         return h, losses[0], losses[2], kld
 
 
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(iters):
-        fn()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / iters
-
-
 def bench_shape(shape, dev, warmup, iters):
     B, H = shape
     torch.manual_seed(1)
@@ -78,29 +67,23 @@ def bench_shape(shape, dev, warmup, iters):
     g_one = [torch.tensor(v, device=dev) for v in (1.0, 1.0, 0.1)]
     params = list(head.parameters())
 
-    def forward(on):
-        def run():
-            L.ENABLED = on
-            return head(pooled)
-        return run
+    def forward():
+        return head(pooled)
 
-    def step(on):
-        fwd = forward(on)
-
-        def run():
-            pooled.grad = None
-            for p in params:
-                p.grad = None
-            torch.autograd.backward(list(fwd()), [g_h] + g_one)
-        return run
+    def step():
+        pooled.grad = None
+        for p in params:
+            p.grad = None
+        torch.autograd.backward(list(forward()), [g_h] + g_one)
 
     res = {}
     for on in (True, False):
-        before = dict(L.LATENT_STATS)
-        step(on)()
-        took = "hip" if on else "torch"
-        assert L.LATENT_STATS[took] == before[took] + 1, "the %s leg did not run" % took
-        out = [t.detach() for t in forward(on)()]
+        with switched(L, "ENABLED", on):
+            before = dict(L.LATENT_STATS)
+            step()
+            took = "hip" if on else "torch"
+            assert L.LATENT_STATS[took] == before[took] + 1, "the %s leg did not run" % took
+            out = [t.detach() for t in forward()]
         res[on] = (out, [pooled.grad.clone()] + [p.grad.clone() for p in params])
     rel = lambda a, b: float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
     entry = {"B": B, "P": P, "H": H,
@@ -110,19 +93,17 @@ def bench_shape(shape, dev, warmup, iters):
                            "loss_std_hip": float(res[True][0][1]), "loss_std_torch": float(res[False][0][1]),
                            "loss_corr_hip": float(res[True][0][2]), "loss_corr_torch": float(res[False][0][2]),
                            "kld_hip": float(res[True][0][3]), "kld_torch": float(res[False][0][3]),
-                           "grad_max_abs_diff_over_max_abs": [rel(a, b) for a, b in zip(res[True][1], res[False][1])]},
-             "hip": {"forward_ms": [], "forward_backward_ms": []}, "torch": {"forward_ms": [], "forward_backward_ms": []}}
-    for _ in range(REPEATS):                                        # the legs alternate
-        for leg, on in (("hip", True), ("torch", False)):
-            entry[leg]["forward_ms"].append(timed(forward(on), warmup, iters))
-            entry[leg]["forward_backward_ms"].append(timed(step(on), warmup, iters))
-    L.ENABLED = True
+                           "grad_max_abs_diff_over_max_abs": [rel(a, b) for a, b in zip(res[True][1], res[False][1])]}}
+    entry.update(alternate(REPEATS, {"hip": True, "torch": False},           # the legs alternate
+                           {"forward_ms": lambda on: event_ms(forward, warmup, iters),
+                            "forward_backward_ms": lambda on: event_ms(step, warmup, iters)},
+                           entering=lambda on: switched(L, "ENABLED", on)))
     entry["summary"] = {}
     for key in ("forward_ms", "forward_backward_ms"):
         hip, ref = entry["hip"][key], entry["torch"][key]
-        entry["summary"][key] = {"hip_mean": sum(hip) / REPEATS, "torch_mean": sum(ref) / REPEATS,
-                                 "torch_spread": max(ref) - min(ref), "hip_spread": max(hip) - min(hip),
-                                 "speedup_over_torch": sum(ref) / sum(hip)}
+        h, r = leg_summary(hip), leg_summary(ref)
+        entry["summary"][key] = {"hip_mean": h["mean"], "torch_mean": r["mean"], "torch_spread": r["spread"],
+                                 "hip_spread": h["spread"], "speedup_over_torch": sum(ref) / sum(hip)}
     return entry
 
 
@@ -132,8 +113,7 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "vae_latent.json"))
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_latent.py needs the GPU: there is no CPU path to time")
+    need_gpu("bench_latent.py")
     dev = torch.device("cuda:0")
     result = {"workload": "the tail of VAE.encoder plus the KL term of VAE.vae_loss, fp32: the op of csrc/vae_latent.hip "
                           "against the torch lines (MLGNN_VAE_LATENT_FUSED=0), same latent, parameters and cotangents",
@@ -144,10 +124,7 @@ def main():
         entry = bench_shape(shape, dev, a.warmup, a.iters)
         result["op"].append(entry)
         print(json.dumps(entry), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(result, fh, indent=1)
-        fh.write("\n")
+    write_json(a.out, result)
 
 
 if __name__ == "__main__":

@@ -17,6 +17,8 @@ from types import SimpleNamespace
 
 import torch
 
+from _bench import event_ms, need_gpu, write_json
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
 from mlgnn import mmd as M  # noqa: E402
@@ -25,19 +27,6 @@ from models import get_model  # noqa: E402
 SHAPES = [(32, 438, 64), (64, 438, 64), (64, 438, 2)]
 KINDS = ["imq", "rbf"]
 METHODS = ("compute_mmd", "compute_kernel", "compute_rbf", "compute_inv_mult_quad")
-
-
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(iters):
-        fn()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / iters
 
 
 def bench_shape(shape, kind, dev, warmup, iters, z_var=2.0):
@@ -70,7 +59,7 @@ def bench_shape(shape, kind, dev, warmup, iters, z_var=2.0):
              "agreement": {"mmd_mean_hip": float(a), "mmd_mean_loop": float(b),
                            "grad_max_abs_diff_over_max_abs": float((ga - gb).abs().max() / gb.abs().max())}}
     for leg, fn in (("hip", hip), ("loop", loop)):
-        entry[leg] = {"forward_ms": timed(fn, warmup, iters), "forward_backward_ms": timed(step(fn), warmup, iters)}
+        entry[leg] = {"forward_ms": event_ms(fn, warmup, iters), "forward_backward_ms": event_ms(step(fn), warmup, iters)}
     entry["speedup_over_loop"] = {k: entry["loop"][k] / entry["hip"][k] for k in entry["hip"]}
     return entry
 
@@ -81,8 +70,7 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mmd_loss.json"))
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_mmd.py needs the GPU: there is no CPU path to time")
+    need_gpu("bench_mmd.py")
     dev = torch.device("cuda:0")
     result = {"workload": "MMD term of VAE.vae_loss over all pathways, fp32: one launch per direction against the "
                           "per-pathway loop (MLGNN_MMD_FUSED=0), same z and prior",
@@ -93,10 +81,7 @@ def main():
             entry = bench_shape(shape, kind, dev, a.warmup, a.iters)
             result["op"].append(entry)
             print(json.dumps(entry), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(result, fh, indent=1)
-        fh.write("\n")
+    write_json(a.out, result)
 
 
 if __name__ == "__main__":

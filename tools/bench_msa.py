@@ -17,23 +17,12 @@ import sys
 import torch
 import torch.nn as nn
 
+from _bench import event_ms, need_gpu, write_json
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
 from mlgnn import mha_attention  # noqa: E402
 from models.deepergcn import MSAReadout, torch_attention  # noqa: E402
-
-
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(iters):
-        fn()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / iters
 
 
 def main():
@@ -47,8 +36,7 @@ def main():
     ap.add_argument("--op-only", action="store_true", help="the HIP attention op alone (per-kernel profiles)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "msa_readout.json"))
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_msa.py needs the GPU: there is no CPU path to time")
+    need_gpu("bench_msa.py")
     dev = torch.device("cuda:0")
     B, P, H = a.graphs, a.tokens, a.heads
     result = {"workload": "%d graphs x %d tokens, %d heads, fp32, dim_feedforward 2048, dropout 0, training mode" % (B, P, H),
@@ -67,8 +55,8 @@ def main():
         entry = {"d": d, "head_width": d // H}
         ops = (("hip", mha_attention),) if a.op_only else (("hip", mha_attention), ("torch_ops", torch_attention))
         for name, op in ops:
-            entry["attention_" + name] = {"forward_ms": timed(lambda: op(qkv, B, H), a.warmup, a.iters),
-                                          "forward_backward_ms": timed(lambda: op_step(op), a.warmup, a.iters)}
+            entry["attention_" + name] = {"forward_ms": event_ms(lambda: op(qkv, B, H), a.warmup, a.iters),
+                                          "forward_backward_ms": event_ms(lambda: op_step(op), a.warmup, a.iters)}
         if not a.op_only:
             ours = MSAReadout(d, H, batch_first=True, dropout=0.0).to(dev).train()
             stock = nn.TransformerEncoderLayer(d, H, batch_first=True, dropout=0.0).to(dev).train()
@@ -80,18 +68,15 @@ def main():
                 torch.autograd.backward(layer(x), cot3)
 
             for name, layer in (("msa_readout", ours), ("stock_layer", stock)):
-                entry["layer_" + name] = {"forward_ms": timed(lambda: layer(x), a.warmup, a.iters),
-                                          "forward_backward_ms": timed(lambda: layer_step(layer), a.warmup, a.iters)}
+                entry["layer_" + name] = {"forward_ms": event_ms(lambda: layer(x), a.warmup, a.iters),
+                                          "forward_backward_ms": event_ms(lambda: layer_step(layer), a.warmup, a.iters)}
             entry["attention_speedup_over_torch_ops"] = {k: entry["attention_torch_ops"][k] / entry["attention_hip"][k]
                                                          for k in entry["attention_hip"]}
             entry["layer_speedup_over_stock"] = {k: entry["layer_stock_layer"][k] / entry["layer_msa_readout"][k]
                                                  for k in entry["layer_msa_readout"]}
         result["widths"].append(entry)
         print(json.dumps(entry), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(result, fh, indent=1)
-        fh.write("\n")
+    write_json(a.out, result)
 
 
 if __name__ == "__main__":

@@ -27,10 +27,11 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
+
+from _bench import beats, event_ms, leg_summary, need_gpu, wall, write_json
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
@@ -50,14 +51,6 @@ def make_data(n, F, seed):
     return x.astype(np.float32), y
 
 
-def wall(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3, out
-
-
 def kernel_ms(prepared, y, k, warmup, iters):
     """The launch of mlgnn_mutual_info_cd alone, operands resident on the device."""
     from scipy.special import digamma
@@ -74,16 +67,7 @@ def kernel_ms(prepared, y, k, warmup, iters):
         _lib.check(_lib.lib.mlgnn_mutual_info_cd(xt.data_ptr(), labels.data_ptr(), psi_d.data_ptr(), base, mi.data_ptr(), None,
                                                  n, F, k, len(c), stream), "mlgnn_mutual_info_cd")
 
-    for _ in range(warmup):
-        launch()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(iters):
-        launch()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / iters
+    return event_ms(launch, warmup, iters)
 
 
 def kernel_ms_regression(prepared, y_prepared, k, warmup, iters):
@@ -101,16 +85,7 @@ def kernel_ms_regression(prepared, y_prepared, k, warmup, iters):
         _lib.check(_lib.lib.mlgnn_mutual_info_cc(xt.data_ptr(), y_d.data_ptr(), psi_d.data_ptr(), base, mi.data_ptr(), None,
                                                  None, n, F, k, stream), "mlgnn_mutual_info_cc")
 
-    for _ in range(warmup):
-        launch()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(iters):
-        launch()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / iters
+    return event_ms(launch, warmup, iters)
 
 
 def bench_shape_regression(name, n, F, k, warmup, iters, repeats):
@@ -129,7 +104,7 @@ def bench_shape_regression(name, n, F, k, warmup, iters, repeats):
         ms, (prepared, y_prepared) = wall(lambda: MI.prepare_regression(x, y, SEED))
         entry["prepare_ms"].append(ms)
         entry["kernel_ms"].append(kernel_ms_regression(prepared, y_prepared, k, warmup, iters))
-    return summarise(entry, got, want, repeats)
+    return compared(entry, got, want)
 
 
 def bench_shape(name, n, F, k, warmup, iters, repeats):
@@ -148,19 +123,21 @@ def bench_shape(name, n, F, k, warmup, iters, repeats):
         ms, (prepared, _) = wall(lambda: MI.prepare(x, y, SEED))
         entry["prepare_ms"].append(ms)
         entry["kernel_ms"].append(kernel_ms(prepared, y, k, warmup, iters))
-    return summarise(entry, got, want, repeats)
+    return compared(entry, got, want)
 
 
-def summarise(entry, got, want, repeats):
+def compared(entry, got, want):
+    """``entry`` with the agreement of the two legs and its summary."""
     entry["max_abs_diff_to_sklearn"] = float(np.abs(got - want).max())
     entry["masks_equal_at_the_mean_threshold"] = bool(np.array_equal(got < got.mean(), want < want.mean()))
     hip, ref = entry["hip_end_to_end_ms"], entry["sklearn_ms"]
-    entry["summary"] = {"hip_end_to_end_mean_ms": sum(hip) / repeats, "hip_spread_ms": max(hip) - min(hip),
-                        "sklearn_mean_ms": sum(ref) / repeats, "sklearn_spread_ms": max(ref) - min(ref),
-                        "prepare_mean_ms": sum(entry["prepare_ms"]) / repeats,
-                        "kernel_mean_ms": sum(entry["kernel_ms"]) / repeats,
+    h, r = leg_summary(hip), leg_summary(ref)
+    entry["summary"] = {"hip_end_to_end_mean_ms": h["mean"], "hip_spread_ms": h["spread"],
+                        "sklearn_mean_ms": r["mean"], "sklearn_spread_ms": r["spread"],
+                        "prepare_mean_ms": leg_summary(entry["prepare_ms"])["mean"],
+                        "kernel_mean_ms": leg_summary(entry["kernel_ms"])["mean"],
                         "speedup_over_sklearn": sum(ref) / sum(hip),
-                        "beats_sklearn_by_more_than_its_spread": sum(ref) / repeats - sum(hip) / repeats > max(ref) - min(ref)}
+                        "beats_sklearn_by_more_than_its_spread": beats(hip, ref)}
     return entry
 
 
@@ -177,8 +154,7 @@ def main():
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "mutual_info_regression.json" if a.regression else "mutual_info.json")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_mutual_info.py needs the GPU: there is no CPU path of the op to time")
+    need_gpu("bench_mutual_info.py", "CPU path of the op")
     import scipy
     import sklearn
     workload = ("mutual_info_regression over every gene column (generate_mutual_mask with mutual_classif false; the "
@@ -208,10 +184,7 @@ def main():
         verdict = "beats_sklearn_at_every_shape" if a.regression else "ships_enabled"
         result[verdict] = all(e["summary"]["beats_sklearn_by_more_than_its_spread"] for e in result["shapes"]) \
             and len(result["shapes"]) == len(SHAPES)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            json.dump(result, fh, indent=1)
-            fh.write("\n")
+        write_json(a.out, result)
 
 
 if __name__ == "__main__":

@@ -19,25 +19,14 @@ from types import SimpleNamespace
 
 import torch
 
+from _bench import event_ms, need_gpu, switched, write_json
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
 from mlgnn import conv  # noqa: E402
 from mlgnn.optim import FlatAdam  # noqa: E402
 from models import get_model  # noqa: E402
 import train_harness  # noqa: E402
-
-
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(iters):
-        fn()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / iters
 
 
 def bench_op(B, H, W, cin, cout, k, dev, warmup, iters):
@@ -52,10 +41,9 @@ def bench_op(B, H, W, cin, cout, k, dev, warmup, iters):
 
     entry = {"cin": cin, "cout": cout, "k": k, "gflop_forward": 2e-9 * B * H * W * cin * cout * k * k}
     for name, on in (("hip", True), ("library", False)):
-        conv.ENABLED = on
-        entry[name] = {"forward_ms": timed(lambda: m(x, relu=True), warmup, iters),
-                       "forward_backward_ms": timed(step, warmup, iters)}
-    conv.ENABLED = True
+        with switched(conv, "ENABLED", on):
+            entry[name] = {"forward_ms": event_ms(lambda: m(x, relu=True), warmup, iters),
+                           "forward_backward_ms": event_ms(step, warmup, iters)}
     entry["speedup_over_library"] = {k_: entry["library"][k_] / entry["hip"][k_] for k_ in entry["hip"]}
     return entry
 
@@ -69,9 +57,7 @@ def bench_step(B, pca_dim, dev, warmup, iters, more_conv):
     batch = SimpleNamespace(raw_data=torch.rand(B, G, generator=gen).to(dev), raw_indice=seg[None, :].expand(B, G).to(dev),
                             age=torch.rand(B, generator=gen).to(dev))
     target = torch.nn.functional.one_hot(torch.randint(0, 2, (B,), generator=gen), 2).float().to(dev)
-    entry = {"more_conv": more_conv}
-    for name, on in (("hip", True), ("library", False)):
-        conv.ENABLED = on
+    def train_step_ms():
         torch.manual_seed(3)
         model = get_model("pathcnn")(args)
         mask = torch.ones(G)
@@ -92,8 +78,12 @@ def bench_step(B, pca_dim, dev, warmup, iters, more_conv):
             bucket.all_reduce_mean()
             opt.step()
 
-        entry[name] = {"train_step_ms": timed(step, warmup, iters)}
-    conv.ENABLED = True
+        return event_ms(step, warmup, iters)
+
+    entry = {"more_conv": more_conv}
+    for name, on in (("hip", True), ("library", False)):
+        with switched(conv, "ENABLED", on):
+            entry[name] = {"train_step_ms": train_step_ms()}
     entry["speedup_over_library"] = entry["library"]["train_step_ms"] / entry["hip"]["train_step_ms"]
     return entry
 
@@ -106,8 +96,7 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pathcnn.json"))
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_pathcnn.py needs the GPU: there is no CPU path to time")
+    need_gpu("bench_pathcnn.py")
     dev = torch.device("cuda:0")
     B, H, W = a.patients, 146, 3 * a.pca_dim
     result = {"workload": "PathCNN, %d patients x 146 x %d image, k = 3, fp32" % (B, W),
@@ -122,10 +111,7 @@ def main():
         entry = bench_step(B, a.pca_dim, dev, a.warmup, a.iters, more_conv)
         result["train_step"].append(entry)
         print(json.dumps(entry), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(result, fh, indent=1)
-        fh.write("\n")
+    write_json(a.out, result)
 
 
 if __name__ == "__main__":

@@ -17,6 +17,8 @@ import sys
 
 import torch
 
+from _bench import alternate, beats, event_ms, leg_summary, need_gpu, switched, write_json
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
 from mlgnn import pathway_conv as pc  # noqa: E402
@@ -24,21 +26,9 @@ from mlgnn.dense import linear  # noqa: E402
 from models.gcn_lib.sparse.torch_vertex import PathwayConv  # noqa: E402
 
 
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(iters):
-        fn()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / iters
-
-
 def spread(values):
-    return {"mean_ms": sum(values) / len(values), "min_ms": min(values), "max_ms": max(values), "runs_ms": values}
+    s = leg_summary(values)
+    return {"mean_ms": s["mean"], "min_ms": s["min"], "max_ms": s["max"], "runs_ms": values}
 
 
 def main():
@@ -53,8 +43,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pathway_conv.json"))
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_pathway_conv.py needs the GPU: there is no CPU path to time")
+    need_gpu("bench_pathway_conv.py")
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(2025)
     B, n = a.graphs, a.genes + a.pathways
@@ -86,16 +75,17 @@ def main():
                     p.grad = None
                 torch.autograd.backward(layer_fwd(), cot)
 
-            legs = {"kernels": {"forward": [], "forward_backward": []}, "torch_ops": {"forward": [], "forward_backward": []}}
-            keep = pc.PATHWAY_CONV
             outs = {}
-            for _ in range(a.repeats):
-                for name, flag in (("kernels", True), ("torch_ops", False)):
-                    pc.PATHWAY_CONV = flag
-                    legs[name]["forward"].append(timed(layer_fwd, a.warmup, a.iters))
-                    legs[name]["forward_backward"].append(timed(layer_step, a.warmup, a.iters))
-                    outs[name] = layer_fwd().detach()
-            pc.PATHWAY_CONV = keep
+
+            def forward_backward_ms(flag):
+                ms = event_ms(layer_step, a.warmup, a.iters)
+                outs[flag] = layer_fwd().detach()                   # untimed, for the agreement of the legs
+                return ms
+
+            legs = alternate(a.repeats, {"kernels": True, "torch_ops": False},
+                             {"forward": lambda flag: event_ms(layer_fwd, a.warmup, a.iters),
+                              "forward_backward": forward_backward_ms},
+                             entering=lambda flag: switched(pc, "PATHWAY_CONV", flag))
             y = linear(x.detach(), torch.cat([W[:, 0::2], W[:, 1::2]], dim=0)).detach().requires_grad_(True)
             rcot = torch.randn(R, d, device=dev)
 
@@ -106,26 +96,22 @@ def main():
                 y.grad = None
                 torch.autograd.backward(op_fwd(), rcot)
 
-            op_f, op_fb = timed(op_fwd, a.warmup, a.iters), timed(op_step, a.warmup, a.iters)
+            op_f, op_fb = event_ms(op_fwd, a.warmup, a.iters), event_ms(op_step, a.warmup, a.iters)
             gather = E * 2 * d * 4
             entry = {"d": d, "aggr": aggr,
                      "legs": {k: {m: spread(v) for m, v in leg.items()} for k, leg in legs.items()},
-                     "max_abs_difference_of_the_legs": float((outs["kernels"] - outs["torch_ops"]).abs().max()),
+                     "max_abs_difference_of_the_legs": float((outs[True] - outs[False]).abs().max()),
                      "op_forward_ms": op_f, "op_forward_backward_ms": op_fb, "op_gather_bytes": gather,
                      "op_distinct_source_rows_bytes": int(torch.unique(ei[0]).numel()) * 2 * d * 4,
                      "op_forward_gather_bytes_per_s": gather / (op_f * 1e-3)}
             k, t = entry["legs"]["kernels"], entry["legs"]["torch_ops"]
             entry["speedup_over_torch_ops"] = {m: t[m]["mean_ms"] / k[m]["mean_ms"] for m in k}
             # the switch's rule: forward + backward beats the torch leg by more than that leg's own spread
-            entry["kernels_win_beyond_the_torch_spread"] = bool(
-                t["forward_backward"]["mean_ms"] - k["forward_backward"]["mean_ms"]
-                > t["forward_backward"]["max_ms"] - t["forward_backward"]["min_ms"])
+            entry["kernels_win_beyond_the_torch_spread"] = beats(legs["kernels"]["forward_backward"],
+                                                                 legs["torch_ops"]["forward_backward"])
             result["cases"].append(entry)
             print(json.dumps(entry), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(result, fh, indent=1)
-        fh.write("\n")
+    write_json(a.out, result)
 
 
 if __name__ == "__main__":

@@ -15,16 +15,17 @@ per shape and repeat:
   * that both legs agree (max |difference| of ``pca_components`` and of the fp32 image), the largest sweep count.
 
 Every repeat of a shape is a step of its own: a fresh child process under its own time limit (``--step-timeout``); the
-first step that fails ends the run.  Results are written after every step.  Writes profiles/pathway_pca.json, whose
+first step that fails or runs out of time ends the run (``drive`` of tools/_bench.py).  Results are written after every
+step.  Writes profiles/pathway_pca.json, whose
 ``ships_enabled`` is the rule for the default of ``MLGNN_PCA_FUSED``: the kernel leg beats the scikit-learn leg by more
 than that leg's spread at the masked N = 300 and N = 470 shapes.  Development tool; run it under a time limit of its own
 (``timeout -k 10 900 python tools/bench_pathway_pca.py``)."""
 import argparse
 import json
 import os
-import subprocess
 import sys
-import time
+
+from _bench import beats, child_result, drive, event_ms, leg_summary, need_gpu, switched, wall
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
@@ -40,15 +41,6 @@ def shapes():
 
 def shape_name(n, masked, sim):
     return "N%d_%s_sim%d" % (n, "masked" if masked else "unmasked", sim)
-
-
-def wall(fn):
-    import torch
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3, out
 
 
 def kernel_ms(raw, plan, sim, warmup, iters):
@@ -73,17 +65,9 @@ def kernel_ms(raw, plan, sim, warmup, iters):
         _lib.call("mlgnn_pathway_pca", xt, cols, ptr, ks, *outs, work, need, n, n_features, total, n_seg, most, sim,
                   _lib.stream())
 
-    for _ in range(warmup):
-        launch()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(iters):
-        launch()
-    e.record()
-    torch.cuda.synchronize()
+    ms = event_ms(launch, warmup, iters)
     info = outs[4].cpu().numpy()
-    return s.elapsed_time(e) / iters, int(info[:, 0].max()), int((info[:, 0] < 0).sum())
+    return ms, int(info[:, 0].max()), int((info[:, 0] < 0).sum())
 
 
 def run_step(n, masked, sim, warmup, iters):
@@ -93,8 +77,7 @@ def run_step(n, masked, sim, warmup, iters):
     import mlgnn
     from mlgnn import pca as P
     from mlgnn.data import SyntheticTCGA
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_pathway_pca.py needs the GPU: there is no CPU path of the op to time")
+    need_gpu("bench_pathway_pca.py", "CPU path of the op")
     data = SyntheticTCGA(n, seed=SEED)
     raw = data.raw_matrix()                                        # fp32 [N, 25015] on the host, as the harness has it
     mask = None
@@ -104,13 +87,14 @@ def run_step(n, masked, sim, warmup, iters):
     pca_dim = 2
 
     def leg(enabled):
-        P.ENABLED = enabled
-        return P.fold_pca(raw, data.raw_indice, mask, sim, pca_dim)
+        """-> (ms, result): the switch is set outside the timed call."""
+        with switched(P, "ENABLED", enabled):
+            return wall(lambda: P.fold_pca(raw, data.raw_indice, mask, sim, pca_dim))
 
     leg(True)                                                      # discarded: the code object loads
     before = dict(P.PCA_STATS)
-    hip_ms, got = wall(lambda: leg(True))
-    ref_ms, want = wall(lambda: leg(False))
+    hip_ms, got = leg(True)
+    ref_ms, want = leg(False)
     assert P.PCA_STATS == dict(hip=before["hip"] + 1, sklearn=before["sklearn"] + 1), P.PCA_STATS
     plan = P.FoldPlan(data.raw_indice, mask, sim, 438)
     k_ms, sweeps, capped = kernel_ms(raw, plan, sim, warmup, iters)
@@ -122,13 +106,13 @@ def run_step(n, masked, sim, warmup, iters):
             "device": torch.cuda.get_device_name(0), "host_threads": torch.get_num_threads()}
 
 
-def summarise(entry):
+def with_summary(entry):
     hip, ref = entry["hip_end_to_end_ms"], entry["sklearn_ms"]
-    r = len(hip)
-    entry["summary"] = {"hip_end_to_end_mean_ms": sum(hip) / r, "hip_spread_ms": max(hip) - min(hip),
-                        "sklearn_mean_ms": sum(ref) / r, "sklearn_spread_ms": max(ref) - min(ref),
-                        "kernel_mean_ms": sum(entry["kernel_ms"]) / r, "speedup_over_sklearn": sum(ref) / sum(hip),
-                        "beats_sklearn_by_more_than_its_spread": sum(ref) / r - sum(hip) / r > max(ref) - min(ref)}
+    h, r = leg_summary(hip), leg_summary(ref)
+    entry["summary"] = {"hip_end_to_end_mean_ms": h["mean"], "hip_spread_ms": h["spread"],
+                        "sklearn_mean_ms": r["mean"], "sklearn_spread_ms": r["spread"],
+                        "kernel_mean_ms": leg_summary(entry["kernel_ms"])["mean"], "speedup_over_sklearn": sum(ref) / sum(hip),
+                        "beats_sklearn_by_more_than_its_spread": beats(hip, ref)}
     return entry
 
 
@@ -139,12 +123,11 @@ def main():
     ap.add_argument("--repeats", type=int, default=REPEATS)
     ap.add_argument("--step-timeout", type=float, default=240.0, help="seconds, per repeat of a shape")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pathway_pca.json"))
-    ap.add_argument("--step", default=None, help="(internal) N,masked,sim: run one repeat and print its JSON line")
+    ap.add_argument("--child", default=None, help="(internal) run one repeat of this shape and print its result line")
     a = ap.parse_args()
-    if a.step:
-        n, masked, sim = (int(v) for v in a.step.split(","))
-        print("STEP " + json.dumps(run_step(n, bool(masked), sim, a.warmup, a.iters)), flush=True)
-        return
+    by_name = {shape_name(*shape): shape for shape in shapes()}
+    if a.child:
+        return child_result(run_step(*by_name[a.child], a.warmup, a.iters))
     import numpy as np
     import scipy
     import sklearn
@@ -156,33 +139,29 @@ def main():
                         "device events, mean of %d launches after %d" % (a.step_timeout, a.iters, a.warmup),
               "versions": {"sklearn": sklearn.__version__, "numpy": np.__version__, "scipy": scipy.__version__},
               "shapes": []}
-    for n, masked, sim in shapes():
-        entry = {"shape": shape_name(n, masked, sim), "N": n, "masked": masked, "pca_sim_dim": sim,
-                 "hip_end_to_end_ms": [], "sklearn_ms": [], "kernel_ms": []}
-        for _ in range(a.repeats):
-            cmd = [sys.executable, os.path.abspath(__file__), "--step", "%d,%d,%d" % (n, int(masked), sim),
-                   "--warmup", str(a.warmup), "--iters", str(a.iters)]
-            out = subprocess.run(cmd, capture_output=True, text=True, timeout=a.step_timeout)
-            lines = [ln for ln in out.stdout.splitlines() if ln.startswith("STEP ")]
-            if out.returncode != 0 or len(lines) != 1:
-                sys.stderr.write(out.stdout + out.stderr)
-                raise SystemExit("step %s failed with status %d: nothing more is started" % (entry["shape"], out.returncode))
-            step = json.loads(lines[0][5:])
-            for key in ("hip_end_to_end_ms", "sklearn_ms", "kernel_ms"):
-                entry[key].append(step.pop(key))
-            for key in ("device", "host_threads"):
-                result[key] = step.pop(key)
-            for key, v in step.items():
-                entry[key] = max(entry.get(key, v), v)
-        result["shapes"].append(summarise(entry))
+    entries = {}
+
+    def collect(name, step):
+        """One repeat of shape ``name``; the shape's entry goes to the result with its last repeat."""
+        n, masked, sim = by_name[name]
+        entry = entries.setdefault(name, {"shape": name, "N": n, "masked": masked, "pca_sim_dim": sim,
+                                          "hip_end_to_end_ms": [], "sklearn_ms": [], "kernel_ms": []})
+        for key in ("hip_end_to_end_ms", "sklearn_ms", "kernel_ms"):
+            entry[key].append(step.pop(key))
+        for key in ("device", "host_threads"):
+            result[key] = step.pop(key)
+        for key, v in step.items():
+            entry[key] = max(entry.get(key, v), v)
+        if len(entry["kernel_ms"]) < a.repeats:
+            return
+        result["shapes"].append(with_summary(entry))
         print(json.dumps(entry), flush=True)
         decisive = [e for e in result["shapes"] if e["masked"] and e["N"] in (300, 470)]
         result["ships_enabled"] = len(decisive) == 4 and all(e["summary"]["beats_sklearn_by_more_than_its_spread"]
                                                              for e in decisive)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            json.dump(result, fh, indent=1)
-            fh.write("\n")
+
+    drive(__file__, [name for name in by_name for _ in range(a.repeats)], ["--warmup", a.warmup, "--iters", a.iters],
+          a.step_timeout, a.out, result, collect)
 
 
 if __name__ == "__main__":

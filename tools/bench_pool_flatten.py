@@ -16,30 +16,18 @@ import argparse
 import importlib
 import json
 import os
-import subprocess
 import sys
 
 import torch
 import torch.nn as nn
+
+from _bench import event_ms, need_gpu, run_child, switched, write_json
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
 pf = importlib.import_module("mlgnn.pool_flatten")  # noqa: E402
 
 SHAPES = {"gbm": (32, 64, 146, 6, (4, 2), True), "lgg": (64, 64, 146, 9, (4, 2), True), "kirc": (64, 64, 146, 9, (1, 1), False)}
-
-
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(iters):
-        fn()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / iters
 
 
 def bench_op(name, dev, warmup, iters):
@@ -63,24 +51,24 @@ def bench_op(name, dev, warmup, iters):
     entry = {"shape": name, "B": B, "C": C, "H": H, "W": W, "window": list(window), "age": with_age,
              "mbytes_per_direction": (4 * B * C * H * W + per * B * n) / 1e6}
     for leg, on in (("hip", True), ("torch", False)):
-        pf.ENABLED = on
         before = dict(pf.POOL_STATS)
-        entry[leg] = {"forward_ms": timed(forward, warmup, iters), "forward_backward_ms": timed(step, warmup, iters)}
+        with switched(pf, "ENABLED", on):
+            entry[leg] = {"forward_ms": event_ms(forward, warmup, iters), "forward_backward_ms": event_ms(step, warmup, iters)}
         assert pf.POOL_STATS["torch" if on else "hip"] == before["torch" if on else "hip"]
-    pf.ENABLED = True
     entry["speedup_over_torch"] = {k: entry["torch"][k] / entry["hip"][k] for k in entry["hip"]}
     return entry
 
 
 def bench_step(shape, steps, warmup, limit):
-    """tools/bench_tcga.py in a fresh process per switch setting."""
+    """tools/bench_tcga.py in a fresh process per switch setting, under ``limit`` seconds; nothing is started after one
+    that fails or runs out of time (``run_child`` of tools/_bench.py)."""
     entry = {"shape": shape}
     for leg, flag in (("hip", "1"), ("torch", "0")):
         cmd = [sys.executable, os.path.join(ROOT, "tools", "bench_tcga.py"), "--shape", shape, "--steps", str(steps),
                "--warmup", str(warmup)]
-        run = subprocess.run(cmd, env=dict(os.environ, MLGNN_POOL_FLATTEN=flag), timeout=limit, check=True,
-                             stdout=subprocess.PIPE, text=True)
-        line = [ln for ln in run.stdout.splitlines() if ln.startswith("{")][-1]
+        out = run_child("bench_pool_flatten.py", "training step %s, MLGNN_POOL_FLATTEN=%s" % (shape, flag), cmd, limit,
+                        env=dict(os.environ, MLGNN_POOL_FLATTEN=flag))
+        line = [ln for ln in out.splitlines() if ln.startswith("{")][-1]
         entry[leg] = {"train_step_ms": json.loads(line)["ms_per_step"]}
     entry["speedup_over_torch"] = entry["torch"]["train_step_ms"] / entry["hip"]["train_step_ms"]
     return entry
@@ -94,8 +82,7 @@ def main():
     ap.add_argument("--step-limit", type=int, default=240, help="seconds each training-step process may take")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pool_flatten.json"))
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_pool_flatten.py needs the GPU: there is no CPU path to time")
+    need_gpu("bench_pool_flatten.py")
     dev = torch.device("cuda:0")
     result = {"workload": "pooled pathway readout: max-pool, Dropout(0.25) (training), flatten, age; fp32, channel-last input",
               "timing": "device events, mean of %d runs after %d warm-up runs; 'torch' = the replaced lines "
@@ -110,10 +97,7 @@ def main():
             entry = bench_step(shape, 20, 5, a.step_limit)
             result["train_step"].append(entry)
             print(json.dumps(entry), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(result, fh, indent=1)
-        fh.write("\n")
+    write_json(a.out, result)
 
 
 if __name__ == "__main__":

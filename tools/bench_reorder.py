@@ -14,17 +14,17 @@ and, since the PCA ran on the kernel, is also charged the download it needs (rep
   * the three launches alone, by device events (mean of ``--iters`` calls of the entry point after ``--warmup``);
   * that both legs give the same order.
 
-Every shape runs in a child process of its own under a time limit (``--step-timeout``); the first one that fails ends
-the run.  Results are written after every shape.  Writes profiles/pathway_order.json, whose ``ships_enabled`` is the rule
+Every shape runs in a child process of its own under a time limit (``--step-timeout``); the first one that fails or runs
+out of time ends the run (``drive`` of tools/_bench.py).  Results are written after every shape.  Writes profiles/pathway_order.json, whose ``ships_enabled`` is the rule
 for the default of ``MLGNN_REORDER_FUSED``: the kernel leg beats the numpy leg by more than that leg's spread at every
 shape measured.  Development tool; run it under a time limit of its own."""
 import argparse
 import gc
 import json
 import os
-import subprocess
 import sys
-import time
+
+from _bench import beats, child_result, drive, event_ms, leg_summary, need_gpu, switched, wall
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
@@ -41,15 +41,6 @@ def shapes():
 
 def shape_name(n, masked, sim):
     return "N%d_%s_sim%d" % (n, "masked" if masked else "unmasked", sim)
-
-
-def wall(fn):
-    import torch
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3, out
 
 
 def kernel_ms(scores, warmup, iters):
@@ -70,16 +61,7 @@ def kernel_ms(scores, warmup, iters):
         _lib.call("mlgnn_pathway_order", x, rows, n, 3 * sim, x.stride(0), x.stride(1), corr, order, info, work, need,
                   _lib.stream())
 
-    for _ in range(warmup):
-        launch()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(iters):
-        launch()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / iters, int(info[0])
+    return event_ms(launch, warmup, iters), int(info[0])
 
 
 def run_shape(n, masked, sim, repeats, warmup, iters):
@@ -89,22 +71,22 @@ def run_shape(n, masked, sim, repeats, warmup, iters):
     from mlgnn import pca as P
     from mlgnn import reorder as R
     from mlgnn.data import SyntheticTCGA
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_reorder.py needs the GPU: there is no CPU path of the op to time")
+    need_gpu("bench_reorder.py", "CPU path of the op")
     data = SyntheticTCGA(n, seed=SEED)
     raw = data.raw_matrix()
     mask = None
     if masked:
         mi = mlgnn.mutual_info_classif(raw.numpy(), data.labels.numpy(), n_neighbors=3, random_state=12345)
         mask = torch.from_numpy((mi >= mi.mean()).astype(np.float32))[:, None]
-    P.ENABLED = True
-    scores = P.fold_pca_scores(raw, data.raw_indice, mask, sim, 2)[2]
+    with switched(P, "ENABLED", True):
+        scores = P.fold_pca_scores(raw, data.raw_indice, mask, sim, 2)[2]
     assert scores.is_cuda and scores.dtype == torch.float64
     host_scores = scores.cpu()
 
     def leg(enabled, source):
-        R.ENABLED = enabled
-        return R.fold_reorder(source)
+        """-> (ms, order): the switch is set outside the timed call."""
+        with switched(R, "ENABLED", enabled):
+            return wall(lambda: R.fold_reorder(source))
 
     leg(True, scores)                                              # discarded: the code object loads
     leg(False, scores)                                             # discarded: the first download sets up its staging
@@ -114,11 +96,11 @@ def run_shape(n, masked, sim, repeats, warmup, iters):
     gc.collect()
     gc.disable()                                                   # (as timeit does: no collection inside a timed call)
     for _ in range(repeats):
-        ms, got = wall(lambda: leg(True, scores))
+        ms, got = leg(True, scores)
         out["hip_ms"].append(ms)
-        ms, want = wall(lambda: leg(False, host_scores))
+        ms, want = leg(False, host_scores)
         out["host_ms"].append(ms)
-        ms, want2 = wall(lambda: leg(False, scores))               # the download the host leg needs after the PCA kernel
+        ms, want2 = leg(False, scores)                             # the download the host leg needs after the PCA kernel
         out["host_with_download_ms"].append(ms)
         orders.append((got, want, want2))
     gc.enable()
@@ -131,14 +113,14 @@ def run_shape(n, masked, sim, repeats, warmup, iters):
     return out
 
 
-def summarise(entry):
+def with_summary(entry):
     hip, ref = entry["hip_ms"], entry["host_with_download_ms"]
-    r = len(hip)
-    entry["summary"] = {"hip_mean_ms": sum(hip) / r, "hip_spread_ms": max(hip) - min(hip),
-                        "host_mean_ms": sum(entry["host_ms"]) / r,
-                        "host_with_download_mean_ms": sum(ref) / r, "host_with_download_spread_ms": max(ref) - min(ref),
+    h, r = leg_summary(hip), leg_summary(ref)
+    entry["summary"] = {"hip_mean_ms": h["mean"], "hip_spread_ms": h["spread"],
+                        "host_mean_ms": leg_summary(entry["host_ms"])["mean"],
+                        "host_with_download_mean_ms": r["mean"], "host_with_download_spread_ms": r["spread"],
                         "speedup_over_host": sum(ref) / sum(hip),
-                        "beats_host_by_more_than_its_spread": sum(ref) / r - sum(hip) / r > max(ref) - min(ref)}
+                        "beats_host_by_more_than_its_spread": beats(hip, ref)}
     return entry
 
 
@@ -149,12 +131,11 @@ def main():
     ap.add_argument("--repeats", type=int, default=REPEATS)
     ap.add_argument("--step-timeout", type=float, default=120.0, help="seconds, per shape")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pathway_order.json"))
-    ap.add_argument("--step", default=None, help="(internal) N,masked,sim: run one shape and print its JSON line")
+    ap.add_argument("--child", default=None, help="(internal) run this shape and print its result line")
     a = ap.parse_args()
-    if a.step:
-        n, masked, sim = (int(v) for v in a.step.split(","))
-        print("STEP " + json.dumps(run_shape(n, bool(masked), sim, a.repeats, a.warmup, a.iters)), flush=True)
-        return
+    by_name = {shape_name(*shape): shape for shape in shapes()}
+    if a.child:
+        return child_result(run_shape(*by_name[a.child], a.repeats, a.warmup, a.iters))
     import numpy as np
     result = {"workload": "fold_reorder (np.corrcoef of the 146 pathways' PCA scores minus I and the greedy chain, fp64) on "
                           "the fold_pca scores of SyntheticTCGA: the kernels of csrc/pathway_order.hip from device scores "
@@ -164,28 +145,20 @@ def main():
                         "launches alone by device events, mean of %d calls after %d"
                         % (a.repeats, a.step_timeout, a.iters, a.warmup),
               "versions": {"numpy": np.__version__}, "shapes": []}
-    for n, masked, sim in shapes():
-        entry = {"shape": shape_name(n, masked, sim), "N": n, "masked": masked, "pca_sim_dim": sim}
-        cmd = [sys.executable, os.path.abspath(__file__), "--step", "%d,%d,%d" % (n, int(masked), sim),
-               "--warmup", str(a.warmup), "--iters", str(a.iters), "--repeats", str(a.repeats)]
-        out = subprocess.run(cmd, capture_output=True, text=True, timeout=a.step_timeout)
-        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("STEP ")]
-        if out.returncode != 0 or len(lines) != 1:
-            sys.stderr.write(out.stdout + out.stderr)
-            raise SystemExit("shape %s failed with status %d: nothing more is started" % (entry["shape"], out.returncode))
-        step = json.loads(lines[0][5:])
+    def collect(name, step):
+        n, masked, sim = by_name[name]
+        entry = {"shape": name, "N": n, "masked": masked, "pca_sim_dim": sim}
         for key in ("device", "host_threads"):
             result[key] = step.pop(key)
         entry.update(step)
-        result["shapes"].append(summarise(entry))
+        result["shapes"].append(with_summary(entry))
         print(json.dumps(entry), flush=True)
         result["ships_enabled"] = len(result["shapes"]) == len(shapes()) and all(
             e["summary"]["beats_host_by_more_than_its_spread"] and (e["same_order"] or not e["start_pair_upper_triangular"])
             for e in result["shapes"])                            # (numpy starting [j, i], j > i: DESIGN section 7)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            json.dump(result, fh, indent=1)
-            fh.write("\n")
+
+    drive(__file__, list(by_name), ["--warmup", a.warmup, "--iters", a.iters, "--repeats", a.repeats], a.step_timeout, a.out,
+          result, collect)
 
 
 if __name__ == "__main__":

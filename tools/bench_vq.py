@@ -18,6 +18,8 @@ import sys
 
 import torch
 
+from _bench import alternate, event_ms, leg_summary, need_gpu, switched, write_json
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multilevel-gnn_amd"))
 from mlgnn import vq as V  # noqa: E402
@@ -26,19 +28,6 @@ from models.vae import VectorQuantizer  # noqa: E402
 SHAPES = [(64, 2, 512), (64, 64, 512), (32, 64, 512)]
 P = 438
 REPEATS = 3
-
-
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(iters):
-        fn()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / iters
 
 
 def bench_shape(shape, dev, warmup, iters):
@@ -50,25 +39,19 @@ def bench_shape(shape, dev, warmup, iters):
     g_loss = torch.tensor(1.0, device=dev)
     w = layer.embedding.weight
 
-    def forward(on):
-        def run():
-            V.ENABLED = on
-            return layer(z)
-        return run
+    def forward():
+        return layer(z)
 
-    def step(on):
-        fwd = forward(on)
-
-        def run():
-            z.grad = w.grad = None
-            q, loss = fwd()
-            torch.autograd.backward([q, loss], [g_out, g_loss])
-        return run
+    def step():
+        z.grad = w.grad = None
+        q, loss = forward()
+        torch.autograd.backward([q, loss], [g_out, g_loss])
 
     res = {}
     for on in (True, False):
-        step(on)()
-        q, loss = forward(on)()
+        with switched(V, "ENABLED", on):
+            step()
+            q, loss = forward()
         res[on] = (q.detach(), float(loss.detach()), z.grad.clone(), w.grad.clone())
     N = B * P
     entry = {"B": B, "P": P, "D": D, "K": K, "rows": N,
@@ -81,19 +64,17 @@ def bench_shape(shape, dev, warmup, iters):
                            "grad_z_max_abs_diff_over_max_abs":
                                float((res[True][2] - res[False][2]).abs().max() / res[False][2].abs().max()),
                            "grad_codebook_max_abs_diff_over_max_abs":
-                               float((res[True][3] - res[False][3]).abs().max() / res[False][3].abs().max())},
-             "hip": {"forward_ms": [], "forward_backward_ms": []}, "torch": {"forward_ms": [], "forward_backward_ms": []}}
-    for _ in range(REPEATS):                                        # the legs alternate
-        for leg, on in (("hip", True), ("torch", False)):
-            entry[leg]["forward_ms"].append(timed(forward(on), warmup, iters))
-            entry[leg]["forward_backward_ms"].append(timed(step(on), warmup, iters))
-    V.ENABLED = True
+                               float((res[True][3] - res[False][3]).abs().max() / res[False][3].abs().max())}}
+    entry.update(alternate(REPEATS, {"hip": True, "torch": False},           # the legs alternate
+                           {"forward_ms": lambda on: event_ms(forward, warmup, iters),
+                            "forward_backward_ms": lambda on: event_ms(step, warmup, iters)},
+                           entering=lambda on: switched(V, "ENABLED", on)))
     entry["summary"] = {}
     for key in ("forward_ms", "forward_backward_ms"):
         hip, ref = entry["hip"][key], entry["torch"][key]
-        entry["summary"][key] = {"hip_mean": sum(hip) / REPEATS, "torch_mean": sum(ref) / REPEATS,
-                                 "torch_spread": max(ref) - min(ref), "hip_spread": max(hip) - min(hip),
-                                 "speedup_over_torch": sum(ref) / sum(hip)}
+        h, r = leg_summary(hip), leg_summary(ref)
+        entry["summary"][key] = {"hip_mean": h["mean"], "torch_mean": r["mean"], "torch_spread": r["spread"],
+                                 "hip_spread": h["spread"], "speedup_over_torch": sum(ref) / sum(hip)}
     return entry
 
 
@@ -103,8 +84,7 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "vq_layer.json"))
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_vq.py needs the GPU: there is no CPU path to time")
+    need_gpu("bench_vq.py")
     dev = torch.device("cuda:0")
     result = {"workload": "VectorQuantizer.forward of the VQ-VAE, fp32: the op of csrc/vq.hip against the torch lines "
                           "(MLGNN_VQ_FUSED=0), same latent, codebook and cotangents",
@@ -115,10 +95,7 @@ def main():
         entry = bench_shape(shape, dev, a.warmup, a.iters)
         result["op"].append(entry)
         print(json.dumps(entry), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(result, fh, indent=1)
-        fh.write("\n")
+    write_json(a.out, result)
 
 
 if __name__ == "__main__":
