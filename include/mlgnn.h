@@ -1285,6 +1285,41 @@ int mlgnn_pathway_order(const double* x, int64_t rows, int64_t outer, int64_t in
                         int64_t workspace_bytes, void* stream);
 
 /*
+ * The evaluation pass (csrc/eval_metrics.hip; the reference's train.py:71-109 and :338-356): the mean BCE loss of the
+ * batches, the accuracy and scikit-learn's roc_auc_score of R independent rows of samples -- a row is one split, or one
+ * pooled prediction vector -- in ONE launch on the caller's stream, one workgroup per row, no host step.
+ *   pred, y [n_total, 2] fp32; row_ptr [R + 1]: row r holds the samples [row_ptr[r], row_ptr[r + 1]);
+ *   batch_ptr [n_batches + 1]: batch b holds the samples [batch_ptr[b], batch_ptr[b + 1]); row_batch_ptr [R + 1]: row r
+ *   owns the batches [row_batch_ptr[r], row_batch_ptr[r + 1]), which lie inside the row.  All three int32, ascending.
+ *     label t_i = (y[i, 0] >= 0.5),  score s_i = pred[i, 0],  decision (s_i > 0.5)
+ *     acc  = #{(s_i > 0.5) == t_i} / n
+ *     loss = the fp64 mean, in batch order, of the batches' BCELoss values: per batch the fp64 sum in a fixed order of
+ *            its 2 n_b fp32 terms -(y max(log p, -100) + (1 - y) max(log(1 - p), -100)) (ATen's clamp; a NaN stays a
+ *            NaN), divided by 2 n_b and rounded to fp32
+ *     auc  = num / den, one IEEE division of exact integers: the row is sorted by score (descending, a bitonic network
+ *            in LDS padded to a power of two chosen from n_max; -0.0 and +0.0 are one threshold),
+ *            num = sum over negatives j of (2 #{positives with s > s_j} + #{positives with s == s_j}), den = 2 P N_neg:
+ *            roc_auc_score's trapezoid over distinct thresholds, ties sharing one.  NaN when P = 0 or N_neg = 0, and
+ *            when a score of the row is not finite.
+ *   out_f64 [R, 3] = (auc, acc, loss): NaNs for an empty row, loss NaN for a row without batches;
+ *   out_i64 [R, 6] = (n, n_pos, n_correct, n_nonfinite, num, den): zeros for an empty row.
+ *   EVERY element of both is written, whatever they held before.  No float atomics, every float sum in a fixed order:
+ *   bitwise reproducible.  n_max is the caller's statement of the longest row: it selects the padded length, and a row
+ *   longer than that length is cut there.  Every row, batch and sample index is clamped to its range before it is used:
+ *   no address depends on what the pointer arrays, pred or y hold; there is no assert and no printf in the kernel.
+ * Shapes (mlgnn_eval_metrics_supported): 1 <= R <= 65536, 0 <= n_max <= 2048, 0 <= n_total <= R n_max,
+ * 0 <= n_batches <= n_total.  mlgnn_eval_metrics_workspace_bytes answers 0 for such a shape (the op needs no workspace;
+ * `work` may be NULL) and MLGNN_E_SHAPE otherwise.  MLGNN_E_NULL for a NULL operand, then MLGNN_E_SHAPE, MLGNN_E_ALIGN
+ * (pred, y, out_f64, out_i64: 8 bytes; the pointer arrays: 4), MLGNN_E_WORKSPACE (work_bytes < 0); all before anything
+ * is launched.
+ */
+int mlgnn_eval_metrics_supported(int64_t R, int64_t n_max, int64_t n_total, int64_t n_batches);
+int64_t mlgnn_eval_metrics_workspace_bytes(int64_t R, int64_t n_max, int64_t n_total, int64_t n_batches);
+int mlgnn_eval_metrics(const float* pred, const float* y, const int32_t* row_ptr, const int32_t* batch_ptr,
+                       const int32_t* row_batch_ptr, int64_t R, int64_t n_max, int64_t n_total, int64_t n_batches,
+                       double* out_f64, int64_t* out_i64, void* work, int64_t work_bytes, void* stream);
+
+/*
  * PathwayConv's message + aggregation (csrc/pathway_conv.hip; the reference's torch_vertex.py:107-178): the second
  * message-passing step over the gene -> pathway-node membership edges, for MLGNN_AGGR_MAX and MLGNN_AGGR_SOFTMAX (add and
  * mean are two weighted sums of the existing aggregation by linearity; MLGNN_E_MODE here).  fp32, no atomics, every

@@ -22,6 +22,7 @@
 // the batch mode's W); the others own a tile of columns x a run of rows of
 //   grad_feat[b, m] = std_m == 0 ? 0 : g (-coef) / (M mean_std) (x - mean_m) inv_m          a select, as ATen masks it
 // g and mean_std are read on the device.  No atomics, every sum in a fixed order: bitwise reproducible.
+#include "bce_term.h"
 #include "common.h"
 #include "launch.h"
 #include "mlgnn.h"
@@ -81,13 +82,6 @@ __device__ __forceinline__ void row_weights(const BceArgs& a, int b, float y1, f
   } else if (a.mode == kSample) {
     w0 = w1 = a.cw[(size_t)b * a.cw_stride + (y1 == 1.f ? 1 : 0)];
   }
-}
-
-// std::max(l, -100) as ATen writes it: a NaN stays
-__device__ __forceinline__ float clamp_log(float l) { return l < -100.f ? -100.f : l; }
-
-__device__ __forceinline__ float bce_value(float p, float y) {
-  return (y - 1.f) * clamp_log(log1pf(-p)) - y * clamp_log(logf(p));
 }
 
 // VEC == 4: lane l owns the columns c0 + 4 l .. + 3 (one 16-byte load); VEC == 1: c0 + l, + 64, + 128, + 192

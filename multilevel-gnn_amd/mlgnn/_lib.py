@@ -145,6 +145,9 @@ SIGNATURES = {
     "mlgnn_pathway_order_supported": (_INT, [_I64] * 3),
     "mlgnn_pathway_order_workspace_bytes": (_I64, [_I64] * 3),
     "mlgnn_pathway_order": (_INT, [_P] + [_I64] * 5 + [_P] * 4 + [_I64, _P]),
+    "mlgnn_eval_metrics_supported": (_INT, [_I64] * 4),
+    "mlgnn_eval_metrics_workspace_bytes": (_I64, [_I64] * 4),
+    "mlgnn_eval_metrics": (_INT, [_P] * 5 + [_I64] * 4 + [_P] * 3 + [_I64, _P]),
     "mlgnn_pathway_conv_supported": (_INT, [_I64] * 3),
     "mlgnn_pathway_conv_fwd": (_INT, [_P] * 9 + [_I64] * 4 + [_INT, _F, _P, _P]),
     "mlgnn_pathway_conv_bwd_workspace_floats": (_I64, [_I64] * 4 + [_INT]),

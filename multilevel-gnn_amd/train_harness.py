@@ -25,6 +25,7 @@ sys.path.insert(0, HERE)
 
 from mlgnn.data import DataLoader, SyntheticMultiOmix, SyntheticTCGA  # noqa: E402
 from mlgnn.dist import broadcast_parameters  # noqa: E402
+from mlgnn.metrics import EvalBuffer  # noqa: E402
 from mlgnn.optim import FlatAdam, StepLR  # noqa: E402
 from models import get_model  # noqa: E402
 
@@ -66,6 +67,9 @@ def parse_opts(argv=None):
                     help="prepare the fold as train.py:293-299 does: mutual-information mask, per-pathway PCA of the members "
                          "it keeps, projection started from the principal axes, PCA image in pathway_node_attr, topology "
                          "narrowed to the kept nodes (and by --edge_select)")
+    ap.add_argument("--eval_all_splits", action="store_true",
+                    help="evaluate as train.py:158-201 does: the held-back 30 %% is cut into valid and test, every epoch "
+                         "scores train, valid and test in one pass and run() returns (history, Selection)")
     for k, v in DEFAULTS.items():
         if isinstance(v, bool):
             ap.add_argument("--" + k, action="store_true", default=v)
@@ -118,22 +122,110 @@ def train_epoch(model, device, loader, optimizer, criterion, criterion_weight, a
 
 
 @torch.no_grad()
-def evaluate(model, device, loader, criterion):
-    """``train.py:71-109``: accuracy on ``pred[:,0] > 0.5``, AUC on ``pred[:,0]`` against ``y[:,0] >= 0.5``."""
-    from sklearn.metrics import accuracy_score, roc_auc_score
+def _collect(model, device, loader, buf):
+    """One split into ``buf`` as one row: the forward of every batch, no synchronise."""
     model.eval()
-    ys, ps, losses = [], [], []
     for batch in loader:
         batch = batch.to(device)
         pred, _ = _predict(model, batch)
-        target = batch.y.reshape(-1, 2).to(torch.float32)
-        losses.append(criterion(pred.to(torch.float32), target))
-        ys.append(target)
-        ps.append(pred)
-    y = torch.cat(ys).cpu().numpy()[:, 0] >= 0.5
-    p = torch.cat(ps).cpu().numpy()[:, 0]
-    auc = roc_auc_score(y, p) if len(set(y.tolist())) > 1 else float("nan")
-    return accuracy_score(y, p > 0.5), auc, float(torch.stack(losses).mean())
+        buf.append(pred, batch.y.reshape(-1, 2))
+    buf.close_row()
+
+
+def evaluate(model, device, loader, criterion):
+    """``train.py:71-109``: accuracy on ``pred[:,0] > 0.5``, AUC on ``pred[:,0]`` against ``y[:,0] >= 0.5``, the mean of
+    the batches' BCE losses -> ``(acc, auc, loss)``, Python floats.  The batches are collected on the device and leave
+    through :meth:`mlgnn.metrics.EvalBuffer.finish`: one launch and one read-back under ``MLGNN_EVAL_FUSED``, the
+    reference's host lines otherwise.  The loss is the plain ``BCELoss()`` either way (``criterion`` is what the
+    reference passes there, ``criterion_weightless``; it is not called)."""
+    buf = EvalBuffer(len(loader.dataset), device)
+    _collect(model, device, loader, buf)
+    res = buf.finish()[0]
+    return res.acc, res.auc, res.loss
+
+
+def evaluate_splits(model, device, loaders, buffer=None):
+    """The reference's three ``eval`` calls of an epoch (``train.py:162-166``) as one: ``loaders`` is a dict of loaders,
+    every split is a row of one buffer, one dispatch and one read-back -> a dict of :class:`mlgnn.metrics.EvalResult`
+    under the same names.  ``buffer``: an :class:`EvalBuffer` to reuse; its ``pred`` / ``y`` keep the rows afterwards."""
+    buf = buffer if buffer is not None else EvalBuffer(sum(len(ld.dataset) for ld in loaders.values()), device)
+    for loader in loaders.values():
+        _collect(model, device, loader, buf)
+    return dict(zip(loaders, buf.finish()))
+
+
+class Selection:
+    """The ``results`` dict of the reference's ``run`` (``train.py:126-201``), key for key, and its comparisons in its
+    order.  ``metrics``: ``'auc'`` or ``'acc'``, the reference's ``evaluator``."""
+
+    def __init__(self, check_epochs=(), metrics="auc"):
+        if metrics not in ("auc", "acc"):
+            raise ValueError("metrics must be 'auc' or 'acc', got %r" % (metrics,))
+        self.metrics = metrics
+        self.check_epochs = list(check_epochs)
+        self.results = {"highest_valid": -1, "highest_valid_loss": 100, "final_train": -1, "final_test": -1,
+                        "highest_train": -1, "result_y": {}, "epoch_result": {}, "epoch_result_by_loss": {},
+                        "epoch_result_by_epoch": {}}
+
+    def __getitem__(self, key):
+        return self.results[key]
+
+    def evaluator(self, res):
+        return res.auc if self.metrics == "auc" else res.acc
+
+    def update(self, epoch, train, valid, test, test_scores, test_labels):
+        """One epoch's three :class:`EvalResult` and the test split's scores and labels (``train.py:178-201``)."""
+        results = self.results
+        train_eval, valid_eval, test_eval = self.evaluator(train), self.evaluator(valid), self.evaluator(test)
+        test_res = {"y_true": test_labels, "y_pred": test_scores}
+        if train_eval > results["highest_train"]:
+            results["highest_train"] = train_eval
+        if valid.loss < results["highest_valid_loss"]:
+            results["highest_valid_loss"] = valid.loss
+            results["final_test_by_loss"] = test_eval
+            results["result_y_by_loss"] = test_res
+        if valid_eval > results["highest_valid"]:
+            results["highest_valid"] = valid_eval
+            results["final_train"] = train_eval
+            results["final_test"] = test_eval
+            results["result_y"] = test_res
+        if epoch in self.check_epochs:
+            # (the reference reads result_y_by_loss unguarded: a KeyError while no valid loss has been below 100)
+            results["epoch_result_by_loss"][epoch] = results.get("result_y_by_loss", {})
+            results["epoch_result"][epoch] = results["result_y"]
+            results["epoch_result_by_epoch"][epoch] = test_res
+        return results
+
+
+def pooled_metrics(labels_by_fold, preds_by_fold_by_key, device=None):
+    """``train.py:338-356``: for every key -- a ``(check_epoch, selection)`` pair -- the folds' scores are concatenated
+    and scored against the concatenated labels -> ``{key: (auc, acc)}``.  All keys go as rows of one launch where the
+    kernel applies (``MLGNN_EVAL_FUSED``, a GPU, at most 2048 pooled samples); scikit-learn's lines otherwise."""
+    import numpy as np
+    from mlgnn import metrics as M
+    label = np.concatenate([np.asarray(v).reshape(-1) for v in labels_by_fold]).astype(bool)
+    keys = list(preds_by_fold_by_key)
+    preds = [np.concatenate([np.asarray(v, dtype=np.float32).reshape(-1) for v in preds_by_fold_by_key[k]]) for k in keys]
+    if any(p.shape != label.shape for p in preds):
+        raise ValueError("pooled_metrics: every key needs one score per label (%d)" % label.size)
+    n = int(label.size)
+    rows, batches = [n] * len(keys), [[n]] * len(keys)
+    if device is None:
+        device = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
+    if keys and torch.device(device).type == "cuda":
+        score = torch.from_numpy(np.stack(preds)).reshape(-1, 1)
+        y0 = torch.from_numpy(np.tile(label, len(keys))).to(torch.float32).reshape(-1, 1)
+        # (the second columns only enter the loss, which is not reported)
+        pred, y = torch.cat([score, 1 - score], dim=1).to(device), torch.cat([y0, 1 - y0], dim=1).to(device)
+        if M.use_kernel(pred, rows, batches):
+            res = M.binary_metrics(pred, y, batches, rows)
+            M.EVAL_STATS["hip"] += 1
+            return {k: (r.auc, r.acc) for k, r in zip(keys, res)}
+    from sklearn.metrics import roc_auc_score
+    M.EVAL_STATS["host"] += bool(keys)
+    single = label.all() or not label.any()
+    return {k: (float("nan") if single else float(roc_auc_score(label, p)), float(sum(label == (p > 0.5)) / len(label)))
+            for k, p in zip(keys, preds)}
 
 
 def run(args):
@@ -166,6 +258,9 @@ def run(args):
     n_train = int(0.7 * len(data)) // (args.batch_size * world) * (args.batch_size * world)
     idx = torch.randperm(len(data), generator=torch.Generator().manual_seed(args.seed)).tolist()
     train_idx, valid_idx = idx[:n_train][rank::world], idx[n_train:]
+    eval_all = getattr(args, "eval_all_splits", False)
+    if eval_all:                                # the held-back part, cut into valid and test
+        valid_idx, test_idx = valid_idx[:len(valid_idx) // 2], valid_idx[len(valid_idx) // 2:]
     train_loader = DataLoader(torch.utils.data.Subset(data, train_idx), batch_size=args.batch_size, shuffle=True,
                               drop_last=True, num_workers=args.num_workers)
     valid_loader = DataLoader(torch.utils.data.Subset(data, valid_idx), batch_size=args.batch_size, shuffle=False,
@@ -228,6 +323,12 @@ def run(args):
     else:
         criterion = torch.nn.BCELoss()
     plain = torch.nn.BCELoss()
+    if eval_all:
+        test_loader = DataLoader(torch.utils.data.Subset(data, test_idx), batch_size=args.batch_size, shuffle=False,
+                                 num_workers=args.num_workers)
+        loaders = {"train": train_loader, "valid": valid_loader, "test": test_loader}
+        eval_buf = EvalBuffer(len(train_idx) + len(valid_idx) + len(test_idx), device)
+        selection = Selection(range(5, args.epochs + 1, 5), args.metrics)          # train.py:238
 
     history = []
     for epoch in range(1, args.epochs + 1):
@@ -236,17 +337,31 @@ def run(args):
         loss = train_epoch(model, device, train_loader, optimizer, criterion, cw, args, bucket)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        acc, auc, vloss = evaluate(model, device, valid_loader, plain)
+        if eval_all:
+            res = evaluate_splits(model, device, loaders, buffer=eval_buf)
+            acc, auc, vloss = res["valid"].acc, res["valid"].auc, res["valid"].loss
+            # the test split is the buffer's last row: its scores and labels as train.py:103-107 keeps them
+            at = res["train"].n + res["valid"].n
+            test_rows = torch.stack([eval_buf.pred[at:at + res["test"].n, 0], eval_buf.y[at:at + res["test"].n, 0]]).cpu()
+            selection.update(epoch, res["train"], res["valid"], res["test"], test_rows[0].numpy(),
+                             test_rows[1].numpy() >= 0.5)
+        else:
+            acc, auc, vloss = evaluate(model, device, valid_loader, plain)
         if scheduler is not None:
             scheduler.step()
         rec = dict(epoch=epoch, train_loss=loss, valid_loss=vloss, valid_acc=acc, valid_auc=auc,
                    graphs_per_s=len(train_idx) * world / dt)
+        if eval_all:                            # the reference's six numbers (train.py:169-176), next to Valid_loss above
+            rec.update(train_acc=res["train"].acc, test_acc=res["test"].acc, train_auc=res["train"].auc,
+                       test_auc=res["test"].auc)
         history.append(rec)
         if rank == 0:
             logging.info(rec)
             print(rec, flush=True)
     if world > 1:
         dist.destroy_process_group()
+    if eval_all:
+        return history, selection
     return history
 
 
