@@ -1320,6 +1320,47 @@ int mlgnn_eval_metrics(const float* pred, const float* y, const int32_t* row_ptr
                        double* out_f64, int64_t* out_i64, void* work, int64_t work_bytes, void* stream);
 
 /*
+ * The log-rank screen (csrc/survival_screen.hip; the reference's utils/km_util.py:63-105 and :117-129): R rows of
+ * per-patient scores over one cohort of n patients, each split into two groups at its median or at the caller's
+ * threshold, the groups compared by the log-rank test and, on request, described by their Kaplan-Meier curves -- in ONE
+ * launch on the caller's stream, one workgroup per row, fp64, no host step.
+ *   scores: element (r, i) at scores[r row_stride + i patient_stride] (strides in elements, 0 <= stride < 2^31), fp32
+ *   (score_is_f64 = 0) or fp64 (1; anything else MLGNN_E_DTYPE), read as fp64 values.  Shared by all rows, int32:
+ *   order [n], the stable ascending order of the survival times; event_sorted [n], the event flags in that order;
+ *   group_start [M + 1], the first position of each of the M distinct times in that order, group_start[M] = n;
+ *   deaths [M], the events at each distinct time (0 for a time at which patients were only censored).
+ *     threshold_r = threshold[r] when threshold is given; otherwise numpy.median of the row: the scores are sorted by a
+ *                   bitonic network in LDS padded with +inf to a power of two chosen from n, the middle value for odd n,
+ *                   (a + b) / 2 of the two middle values for even n
+ *     group 1     = { i : score_i < threshold_r } (strictly), group 2 the rest
+ *     per distinct time j:  n_j = n - group_start[j],  n1_j = the members of group 1 at risk,  d_j = deaths[j],
+ *                   d1_j = the events of group 1 at that time (integer prefix sums along the time order)
+ *     O1 = sum_j d1_j,   E1 = sum_j d_j n1_j / n_j,   V = sum_j d_j n1_j (n_j - n1_j)(n_j - d_j) / (n_j^2 (n_j - 1)):
+ *                   every term one IEEE division of two exact integers (0 where d_j = 0, the V term 0 where n_j = 1),
+ *                   the terms added in a fixed order
+ *     chi2        = (O1 - E1)^2 / V, NaN when V = 0 (a group is empty, no events, n < 2)
+ *     S_g(t_j)    = prod_{i <= j} (n_gi - d_gi) / n_gi for g = 1, 2 (want_km = 1): every factor one division of two exact
+ *                   integers, 1 where n_gi = 0; a prefix product in a fixed bracketing
+ *   out_f64 [R, 4] = (threshold, E1, V, chi2);  out_i64 [R, 5] = (n1, n2, O1, O2, the number of non-finite scores);
+ *   km [R, 2, M] (want_km = 1; not touched and may be NULL otherwise).  EVERY element of the outputs is written, whatever
+ *   they held before.  No float atomics: bitwise reproducible, and a row's bits do not depend on the other rows of the
+ *   launch.  The p-value is not formed here: erfc(sqrt(chi2 / 2)) on the host (mlgnn/survival.py).  A row with a
+ *   non-finite score has unspecified floating-point outputs (the count says so).  Every index read from a table is
+ *   clamped to its range before it is used; there is no assert and no printf in the kernel.
+ * Shapes (mlgnn_survival_screen_supported): 1 <= R <= 65536, 1 <= n <= 2048, 1 <= M <= n, want_km 0 or 1.
+ * mlgnn_survival_screen_workspace_bytes answers 0 for such a shape (the op needs no workspace; `work` may be NULL) and
+ * MLGNN_E_SHAPE otherwise.  MLGNN_E_NULL for a NULL operand (threshold may be NULL, km under want_km = 0), then
+ * MLGNN_E_SHAPE (the strides included), MLGNN_E_DTYPE, MLGNN_E_ALIGN (scores: its element size; threshold, out_f64,
+ * out_i64, km: 8 bytes; the tables: 4), MLGNN_E_WORKSPACE (work_bytes < 0); all before anything is launched.
+ */
+int mlgnn_survival_screen_supported(int64_t R, int64_t n, int64_t M, int want_km);
+int64_t mlgnn_survival_screen_workspace_bytes(int64_t R, int64_t n, int64_t M, int want_km);
+int mlgnn_survival_screen(const void* scores, int score_is_f64, int64_t row_stride, int64_t patient_stride,
+                          const int32_t* order, const int32_t* event_sorted, const int32_t* group_start,
+                          const int32_t* deaths, const double* threshold, int64_t R, int64_t n, int64_t M, int want_km,
+                          double* out_f64, int64_t* out_i64, double* km, void* work, int64_t work_bytes, void* stream);
+
+/*
  * PathwayConv's message + aggregation (csrc/pathway_conv.hip; the reference's torch_vertex.py:107-178): the second
  * message-passing step over the gene -> pathway-node membership edges, for MLGNN_AGGR_MAX and MLGNN_AGGR_SOFTMAX (add and
  * mean are two weighted sums of the existing aggregation by linearity; MLGNN_E_MODE here).  fp32, no atomics, every

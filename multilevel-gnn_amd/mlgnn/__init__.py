@@ -22,6 +22,9 @@ from .pca import fold_pca, fold_pca_scores, pathway_pca, pathway_pca_supported  
 from .reorder import fold_reorder, pathway_order, pathway_order_host, pathway_order_supported  # noqa: F401
 from .metrics import (EvalBuffer, EvalResult, binary_metrics, binary_metrics_host,  # noqa: F401
                       eval_metrics_supported)
+from .survival import (ScreenResult, logrank_screen, logrank_screen_host, survival_screen_supported,  # noqa: F401
+                       survival_table)
+from .explain import explain_cohort, integrated_gradients, pathway_scores  # noqa: F401
 from .edge_select import edge_select, edge_select_supported, pair_mutual_info  # noqa: F401
 from .edge_select_reg import (edge_select_regression, edge_select_regression_supported,  # noqa: F401
                               pair_mutual_info_regression)

@@ -148,6 +148,9 @@ SIGNATURES = {
     "mlgnn_eval_metrics_supported": (_INT, [_I64] * 4),
     "mlgnn_eval_metrics_workspace_bytes": (_I64, [_I64] * 4),
     "mlgnn_eval_metrics": (_INT, [_P] * 5 + [_I64] * 4 + [_P] * 3 + [_I64, _P]),
+    "mlgnn_survival_screen_supported": (_INT, [_I64] * 3 + [_INT]),
+    "mlgnn_survival_screen_workspace_bytes": (_I64, [_I64] * 3 + [_INT]),
+    "mlgnn_survival_screen": (_INT, [_P, _INT, _I64, _I64] + [_P] * 5 + [_I64] * 3 + [_INT] + [_P] * 4 + [_I64, _P]),
     "mlgnn_pathway_conv_supported": (_INT, [_I64] * 3),
     "mlgnn_pathway_conv_fwd": (_INT, [_P] * 9 + [_I64] * 4 + [_INT, _F, _P, _P]),
     "mlgnn_pathway_conv_bwd_workspace_floats": (_I64, [_I64] * 4 + [_INT]),

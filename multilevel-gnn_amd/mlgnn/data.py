@@ -183,9 +183,27 @@ class SyntheticTCGA(torch.utils.data.Dataset):
         self.pca_components = None                     # set by recalculate_pca_bo_selected_gene
         self._pathway_image = None                     # [n_patients, 146, 3 * pca_dim] once it has run
         self.reorder_idxs = None                       # set under reorder_pathway (get_reorder_idxs)
+        self.seed = seed
+        self._explain_data = None                      # drawn on the first get_explain_data
 
     def __len__(self):
         return self.x.shape[0]
+
+    def get_explain_data(self):
+        """The clinical columns ``MyData.get_explain_data`` (multiloader.py:909-933) hands out for the survival screen:
+        ``(survive_time [n] float64, in months; survive_state [n] int64, 1 = the event was observed)`` per patient.
+        Drawn once from a generator of their own (seeded from ``seed``), so no other draw of the cohort moves: the time
+        is exponential with a mean of 24 months for label 1 and 60 for label 0, rounded to whole months (so that ties
+        occur), the state an event with probability 0.7."""
+        if self._explain_data is None:
+            own = torch.Generator().manual_seed(int(self.seed) + 0x5EED)
+            n = len(self)
+            mean = torch.where(self.labels == 1, 24.0, 60.0).to(torch.float64)
+            u = torch.rand(n, generator=own, dtype=torch.float64)
+            time = torch.round(-torch.log1p(-u) * mean)
+            state = (torch.rand(n, generator=own, dtype=torch.float64) < 0.7).long()
+            self._explain_data = (time, state)
+        return self._explain_data
 
     def __getitem__(self, i):
         y = torch.tensor([1.0 - float(self.labels[i]), float(self.labels[i])])

@@ -70,6 +70,11 @@ def parse_opts(argv=None):
     ap.add_argument("--eval_all_splits", action="store_true",
                     help="evaluate as train.py:158-201 does: the held-back 30 %% is cut into valid and test, every epoch "
                          "scores train, valid and test in one pass and run() returns (history, Selection)")
+    ap.add_argument("--explain", action="store_true",
+                    help="after the last epoch, what utils/km_util.py does with a trained model: integrated gradients over "
+                         "the whole cohort, the 438 (pathway, omics) scores, the log-rank screen against the synthetic "
+                         "survival columns; logs the hit counts per omics and the ten smallest p-values")
+    ap.add_argument("--explain_steps", type=int, default=50, help="quadrature nodes of --explain (captum's n_steps)")
     for k, v in DEFAULTS.items():
         if isinstance(v, bool):
             ap.add_argument("--" + k, action="store_true", default=v)
@@ -228,6 +233,33 @@ def pooled_metrics(labels_by_fold, preds_by_fold_by_key, device=None):
             for k, p in zip(keys, preds)}
 
 
+def explain(model, device, data, args):
+    """``--explain``: :func:`mlgnn.explain.explain_cohort` over the whole cohort in dataset order, against the cohort's
+    ``get_explain_data``; logs what ``statistic.txt`` holds (km_util.py:106-110) and the ten smallest p-values with their
+    row (pathway ``row // 3``, omics ``row % 3``).  -> the :class:`mlgnn.explain.CohortExplanation`."""
+    from mlgnn.explain import OMICS, explain_cohort
+    if not hasattr(data, "get_explain_data"):
+        raise SystemExit("--explain needs a cohort with survival columns (not --model %s)" % args.model)
+    time_, state = data.get_explain_data()
+    loader = DataLoader(data, batch_size=args.batch_size, shuffle=False, num_workers=args.num_workers)
+    t0 = time.perf_counter()
+    res = explain_cohort(model, loader, time_, state, device=device, n_steps=args.explain_steps)
+    torch.cuda.synchronize()
+    lines = ["explain: %d patients, %d nodes, %.2f s" % (len(data), args.explain_steps, time.perf_counter() - t0),
+             "total pathway num:%d" % res.hits["total"][1]]
+    for name in OMICS:
+        lines.append("%s hit rate: %d/%d" % (name, res.hits[name][0], res.hits[name][1]))
+    ranked = sorted((r.p, i) for i, r in enumerate(res.records) if r.p == r.p)[:10]
+    for p, i in ranked:
+        r = res.records[i]
+        lines.append("row %d (pathway %d, %s): p %.3e chi2 %.4g n1 %d n2 %d O1 %d E1 %.4g"
+                     % (i, i // 3, OMICS[i % 3], p, r.chi2, r.n1, r.n2, r.O1, r.E1))
+    for line in lines:
+        logging.info(line)
+        print(line, flush=True)
+    return res
+
+
 def run(args):
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -358,6 +390,8 @@ def run(args):
         if rank == 0:
             logging.info(rec)
             print(rec, flush=True)
+    if getattr(args, "explain", False) and rank == 0:
+        explain(model, device, data, args)
     if world > 1:
         dist.destroy_process_group()
     if eval_all:
